@@ -13,6 +13,11 @@ multi-GPU group (fr_group_*: RCCL ncclSend/ncclRecv of the traced pixels to the 
 ranks); --views N renders one view per rank instead (weak scaling). value = ray segments of all ranks
 (the G-buffer counted once per view) / max elapsed over ranks.
 
+A plain run sets up, warms up, times --steps frames and prints the result line. --full adds, after the timed
+frames, the measurements the headline figure does not need (latency pipeline mode, serialised stage table and
+rooflines, BVH rebuilds, CPU baseline). --dump-outputs DIR writes the images of the last timed frame as .npy.
+The textures are the reference's files when assets/ holds them and procedural otherwise (config.textures).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -29,6 +34,9 @@ import numpy as np  # noqa: E402
 import fovrt  # noqa: E402
 
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, spec)
+ASSET_FILES = ("CedarCity.hdr", "grid.ppm", "bunny/bunny.PPM", "vokselia_spawn/vokselia_spawn.png")
+DUMP_BUFFERS = ("SHADING", "SIBSON", "PULLPUSH", "ATROUS")
+DUMP_MAX_PIXELS = 1 << 18  # per image: 4 MiB of RGBA32F and 4 MiB of marks; 34 MiB for four images and the index
 
 
 def stage_bytes(W, H, rho, spp, jfa_passes):
@@ -204,6 +212,36 @@ def load_traffic(kernels, config):
     return None, None
 
 
+def dump_outputs(out_dir, tracers, ranks):
+    """--dump-outputs: the images the last frame left in each context (what fr_read_buffer hands a caller), float32
+    .npy. An image over DUMP_MAX_PIXELS pixels is written as the rows of a fixed sample of its pixels (seed 0, sorted
+    flat indices y * W + x, the same for every image and every run: sample_index.npy, float64).
+    Over hundreds of accumulated frames of a still camera the reconstructed images come to hold NaN at some
+    pixels (measured: none up to 200 frames, about 3 % of PULLPUSH and ATROUS from 1000 on). So that the written
+    arrays compare and average as numbers and nothing is lost, <name>.npy holds 0 where the image is not finite
+    and <name>_nonfinite.npy marks those entries (1 NaN, 2 +inf, 3 -inf, else 0). Returns the marked entries
+    per image."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = {}
+    for r, t in zip(ranks, tracers):
+        suffix = "" if len(ranks) == 1 and r == 0 else f"_rank{r}"
+        index = None
+        for name in DUMP_BUFFERS:
+            img = t.read(getattr(fovrt.TextureName, name))
+            px = img.reshape(-1, img.shape[-1])
+            if px.shape[0] > DUMP_MAX_PIXELS:
+                if index is None:
+                    index = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_MAX_PIXELS, replace=False))
+                    np.save(os.path.join(out_dir, f"sample_index{suffix}.npy"), index.astype(np.float64))
+                img = px[index]
+            img = np.ascontiguousarray(img, np.float32)
+            marks = np.where(np.isnan(img), 1, np.where(np.isposinf(img), 2, np.where(np.isneginf(img), 3, 0)))
+            counts[f"{name.lower()}{suffix}"] = int(np.count_nonzero(marks))
+            np.save(os.path.join(out_dir, f"{name.lower()}{suffix}.npy"), np.where(marks != 0, np.float32(0), img))
+            np.save(os.path.join(out_dir, f"{name.lower()}{suffix}_nonfinite.npy"), marks.astype(np.float32))
+    return counts
+
+
 def load_issue(kernel, config):
     """The SIMD issue picture of `kernel` from the newest profiles/*_pmc_issue.json recorded on the same
     workload (scripts/pmc_sq.sh + scripts/pmc_issue.py), else None."""
@@ -273,6 +311,15 @@ def main():
                          "so the mask is recomputed every frame (an eye-tracked frame): 'circle' (the bare flag) "
                          "circles the screen centre at a quarter of the height, one degree per frame; 'saccade' "
                          "jumps 90 degrees along the same circle every 30 frames")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the latency "
+                         "pipeline mode, the serialised per-stage table and the rooflines, the BVH rebuilds and the "
+                         "CPU baseline (a plain run times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step (SHADING, SIBSON, PULLPUSH, ATROUS; float32) as "
+                         "DIR/<name>.npy; images over 2^18 pixels as a fixed seeded sample of their pixels, whose "
+                         "indices are DIR/sample_index.npy. Entries that are not finite are written as 0 and marked "
+                         "in DIR/<name>_nonfinite.npy (1 NaN, 2 +inf, 3 -inf)")
     args = ap.parse_args()
     args.mask = fovrt.MASKS[args.mask]
     scene = fovrt.SCENES[args.scene]
@@ -307,8 +354,12 @@ def main():
     my_ranks = [rank] if world > 1 else list(range(R))
     layouts = [view_layout(r, R, views) for r in my_ranks]
     G = layouts[0][2]
+    # the reference's texture files when all of them are in assets/ (they are not part of the repository), else
+    # the procedural textures: the rule of the test-suite and of __graft_entry__.smoke()
+    have_assets = all(os.path.exists(os.path.join(fovrt.DEFAULT_ASSET_DIR, p)) for p in ASSET_FILES)
     cfg_kw = dict(width=W, height=H, scene=scene, mask_mode=args.mask, spp=args.spp, diffuse_max_depth=args.dmd,
-                  refraction_max_depth=args.refraction_max_depth, bvh_builder=1 if args.bvh == "gpu" else 0)
+                  refraction_max_depth=args.refraction_max_depth, bvh_builder=1 if args.bvh == "gpu" else 0,
+                  texture_mode=0 if have_assets else 1)
     tracers = []
     for r in my_ranks:
         t = fovrt.PathTracer(fovrt.Config(device=(local_rank if world > 1 else 0) % ndev, **cfg_kw))
@@ -419,6 +470,89 @@ def main():
     elapsed, total_segs = reduce_over_ranks(dist, dev, elapsed, segs)
     _, total_redundant = reduce_over_ranks(dist, dev, 0.0, redundant)
 
+    dumped = dump_outputs(args.dump_outputs, tracers, my_ranks) if args.dump_outputs else None
+
+    def foveal_density():
+        """Every rank's active pixels of the last frame (a rank traces only its tiles) over the views' pixels."""
+        count_sum = float(sum(t.ray_count() for t in tracers))
+        return reduce_over_ranks(dist, dev, 0.0, count_sum)[1] / views / (W * H)
+
+    K = args.steps
+    rho = foveal_density()
+    n_ranks = R
+    n_jfa = args.jfa_ranks or (2 if not args.no_split and G >= 6 else 1)  # group.cpp's auto rule
+    jfa_vranks = [0] + list(range(2, n_jfa + 1))
+    if R == 1:
+        parallelism = "one view on one GPU"
+    elif G == 1:
+        parallelism = f"{views} views, one per rank (weak scaling), no data-path collective"
+    else:
+        parallelism = (f"{views} view(s) x {G}-way {args.tile}px tile sharding (fr_group, tiles dealt by reconstruction "
+                       f"load); traced pixels (20 B each) to the view's reconstruction ranks over RCCL "
+                       f"ncclSend/ncclRecv; " + ("both chains on view rank 0" if args.no_split else
+                                                 f"JFA -> Sibson on view rank(s) {jfa_vranks} in turns, pull-push -> "
+                                                 "A-Trous on view rank 1") +
+                       (" (every rank receives every rank's pixels: moving camera)" if args.pan else
+                        "" if args.no_front_local else "; tracing ranks run tile-local front stages"))
+    if args.local_ranks > 1:
+        parallelism += f"; REHEARSAL: {R} ranks as contexts of one process on one device (not a scaling measurement)"
+    result = {
+        "metric": "Mrays/s + reconstructed fps @4K, 10% foveal density, 1/2/4/8 GPU",
+        "value": round(total_segs / elapsed / 1e6, 3),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / K * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if G == 1 else "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{args.scene} {W}x{H}, {args.spp} spp, diffuse_max_depth {args.dmd}, "
+                               f"log-polar mask ({'signed, ~10%' if args.mask == 4 else 'mode %d' % args.mask}), "
+                               "JFA + Sibson + pull-push + A-Trous",
+                   "scene": args.scene, "width": W, "height": H, "spp": args.spp, "diffuse_max_depth": args.dmd,
+                   "mask_mode": args.mask, "foveal_density": round(rho, 5), "views": views, "ranks": n_ranks,
+                   "composite": bool(args.composite and views > 1), "camera_step": args.pan,
+                   "gaze": {None: "screen centre",
+                            "circle": "scripted cursor circle, one degree per frame, mask recomputed every frame",
+                            "saccade": "scripted saccades: 90 degrees along the cursor circle every 30 frames, mask "
+                                       "recomputed every frame"}[args.gaze_path],
+                   "parallelism": parallelism,
+                   "textures": "the reference's files in assets/" if have_assets else "procedural (no assets/)",
+                   "procedural_meshes": "box/bunny/earth stand-ins (the reference's .obj files are absent)"},
+        "fps": round(K / elapsed, 2),
+        "fps_definition": "pipelined throughput: K frames enqueued back to back, frame N's reconstruction "
+                          "overlapping frame N+1's trace half (frames per second of the timed region); "
+                          "fps_serial is SURVEY §8(d)'s 1 / (wall time of one whole frame)",
+        "frames_per_s_total": round(views * K / elapsed, 2),
+        "frame_clock_pipelined": clock,
+        "frame_clock_note": "every frame of the timed region: latency = from where its G-buffer may start (the "
+                            "gaze sample) to the end of its Sibson and A-Trous; interval = between consecutive "
+                            "frames' ends (what a display sees). HIP events, one context",
+        "rays": {k: st[k] for k in ("gbuffer_primary", "primary", "shadow", "diffuse_bounce", "mirror",
+                                    "refraction", "reflection", "truncated", "overflow")},
+        "rays_note": "rank 0's counters over the timed frames",
+        "gbuffer_redundant_segments": int(total_redundant),
+        "rank0_role": roles[0],
+    }
+    if dumped is not None:  # entries of each written image that were not finite (written as 0 and marked)
+        result["dump_outputs_nonfinite"] = dumped
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        for t in tracers:
+            t.destroy()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline figure and what its timed steps recorded on the way
+        if group:
+            group.destroy()
+        return finish()
+
     # The latency-bounded mode (fr_set_pipeline_mode LATENCY: one trace half in flight, the previous frame's
     # reconstruction beside the next trace half) on the same workload: K more frames after a few warm-ups,
     # wall-clock fps and the frame clock. Measured after `value`'s timed region, never inside it.
@@ -467,14 +601,11 @@ def main():
     serial = pct(np.asarray(totals, np.float64))
     for t in tracers:
         t.synchronize()
-    # foveal density: every rank's active pixels of the last frame (a rank traces only its tiles)
-    count_sum = float(sum(t.ray_count() for t in tracers))
-    _, count_sum = reduce_over_ranks(dist, dev, 0.0, count_sum)
 
-    K = args.steps
     # (per stage over the frames that ran it: with jfa_ranks > 1 rank 0 runs JFA -> Sibson every m-th frame)
     avg = {k[:-3]: v / max(1, stage_n[k]) for k, v in stage_ms.items()}
-    rho = count_sum / views / (W * H)
+    rho = foveal_density()  # of the last serialised frame
+    result["config"]["foveal_density"] = round(rho, 5)
     L = jfa_passes(W, H)
     sb = stage_bytes(W, H, rho, args.spp, L)
     # (a rank that runs no reconstruction chain reports 0 ms for those stages)
@@ -497,69 +628,14 @@ def main():
     image_stages = ["sampling", "optimize", "jfa", "sibson", "pullpush", "atrous"]
     img_bytes = sum(sb[k] for k in image_stages)
     img_ms = sum(avg[k] for k in image_stages)
-    n_ranks = R
-    n_jfa = args.jfa_ranks or (2 if not args.no_split and G >= 6 else 1)  # group.cpp's auto rule
-    jfa_vranks = [0] + list(range(2, n_jfa + 1))
-    if R == 1:
-        parallelism = "one view on one GPU"
-    elif G == 1:
-        parallelism = f"{views} views, one per rank (weak scaling), no data-path collective"
-    else:
-        parallelism = (f"{views} view(s) x {G}-way {args.tile}px tile sharding (fr_group, tiles dealt by reconstruction "
-                       f"load); traced pixels (20 B each) to the view's reconstruction ranks over RCCL "
-                       f"ncclSend/ncclRecv; " + ("both chains on view rank 0" if args.no_split else
-                                                 f"JFA -> Sibson on view rank(s) {jfa_vranks} in turns, pull-push -> "
-                                                 "A-Trous on view rank 1") +
-                       (" (every rank receives every rank's pixels: moving camera)" if args.pan else
-                        "" if args.no_front_local else "; tracing ranks run tile-local front stages"))
-    if args.local_ranks > 1:
-        parallelism += f"; REHEARSAL: {R} ranks as contexts of one process on one device (not a scaling measurement)"
-    result = {
-        "metric": "Mrays/s + reconstructed fps @4K, 10% foveal density, 1/2/4/8 GPU",
-        "value": round(total_segs / elapsed / 1e6, 3),
-        "unit": "Mrays/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / K * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak" if G == 1 else "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"{args.scene} {W}x{H}, {args.spp} spp, diffuse_max_depth {args.dmd}, "
-                               f"log-polar mask ({'signed, ~10%' if args.mask == 4 else 'mode %d' % args.mask}), "
-                               "JFA + Sibson + pull-push + A-Trous",
-                   "scene": args.scene, "width": W, "height": H, "spp": args.spp, "diffuse_max_depth": args.dmd,
-                   "mask_mode": args.mask, "foveal_density": round(rho, 5), "views": views, "ranks": n_ranks,
-                   "composite": bool(args.composite and views > 1), "camera_step": args.pan,
-                   "gaze": {None: "screen centre",
-                            "circle": "scripted cursor circle, one degree per frame, mask recomputed every frame",
-                            "saccade": "scripted saccades: 90 degrees along the cursor circle every 30 frames, mask "
-                                       "recomputed every frame"}[args.gaze_path],
-                   "parallelism": parallelism,
-                   "procedural_meshes": "box/bunny/earth stand-ins (the reference's .obj files are absent)"},
-        "fps": round(K / elapsed, 2),
-        "fps_definition": "pipelined throughput: K frames enqueued back to back, frame N's reconstruction "
-                          "overlapping frame N+1's trace half (frames per second of the timed region); "
-                          "fps_serial is SURVEY §8(d)'s 1 / (wall time of one whole frame)",
-        "frames_per_s_total": round(views * K / elapsed, 2),
+    result.update({
         "frame_ms_serial": serial,
         "fps_serial": round(1e3 / serial["p50"], 2),
         "fps_serial_mean": round(1e3 / float(np.mean(totals)), 2),
         "frame_ms_serial_note": f"HIP events around one synchronised frame (update -> A-Trous, the two reconstruction "
                                 f"chains on their own streams), {n_timed} frames after 5 warm-ups, rank 0"
                                 + ("" if group is None else "; a group frame includes the exchange"),
-        "frame_clock_pipelined": clock,
         "pipeline_latency_mode": latency_mode,
-        "frame_clock_note": "every frame of the timed region: latency = from where its G-buffer may start (the "
-                            "gaze sample) to the end of its Sibson and A-Trous; interval = between consecutive "
-                            "frames' ends (what a display sees). HIP events, one context",
-        "rays": {k: st[k] for k in ("gbuffer_primary", "primary", "shadow", "diffuse_bounce", "mirror",
-                                    "refraction", "reflection", "truncated", "overflow")},
-        "rays_note": "rank 0's counters over the timed frames",
-        "gbuffer_redundant_segments": int(total_redundant),
-        "rank0_role": roles[0],
         "stages": stage_table,
         "stages_note": f"rank 0's HIP events, {n_timed} serialised frames; the timed region pipelines frame N's "
                        "reconstruction with frame N+1's trace half, so ms_per_step < the sum of the stages",
@@ -578,7 +654,7 @@ def main():
         "roofline_image_passes": {"bound": "hbm", "achieved": round(img_bytes / (img_ms * 1e-3) / 1e9, 1),
                                   "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                   "frac": round(img_bytes / (img_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)},
-    }
+    })
     traffic, src = load_traffic(stage_kernels.get(dominant, []), result["config"]) if R == 1 else (None, None)
     if traffic is not None:
         result["roofline"]["traffic"] = int(traffic)
@@ -615,12 +691,7 @@ def main():
                 "pipelined": round(result["fps"] / result["cpu_baseline"]["fps"], 1)}
         except Exception as e:  # report, never fake
             result["cpu_baseline"] = {"value": None, "error": repr(e)}
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    for t in tracers:
-        t.destroy()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

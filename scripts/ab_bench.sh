@@ -2,19 +2,20 @@
 # Interleaved A/B of the bench under environment settings (FOVRT_LIB=abv/lib_x.so selects a library build):
 #   scripts/ab_bench.sh <tag> <reps> "name:VAR=val VAR2=val" ...  [BENCH_ARGS="--gaze-path" ...]
 # Every rep runs each variant once (box drift hits them alike); one summary line per run in
-# gpurun_out/<tag>_summary.txt: Mrays/s, pipelined fps, megakernel ms (timed region / serialised), latency-mode fps,
+# $OUT/<tag>_summary.txt: Mrays/s, pipelined fps, megakernel ms (timed region / serialised), latency-mode fps,
 # serial fps (mean).
 set -o pipefail
+OUT=${FOVRT_OUT:-bench_out}  # where the logs go
 TAG=${1:?tag}; R=${2:?reps}; shift 2
-mkdir -p gpurun_out
-S=gpurun_out/${TAG}_summary.txt
+mkdir -p $OUT
+S=$OUT/${TAG}_summary.txt
 : > "$S"
 for i in $(seq 1 "$R"); do
   for spec in "$@"; do
     n=${spec%%:*}; vars=${spec#*:}
     [ "$vars" = "-" ] && vars=""
-    L=gpurun_out/${TAG}_${n}_$i.json
-    env $vars timeout -k 10 200 python bench.py --no-cpu-baseline --steps 40 --warmup 20 --serial-frames 20 $BENCH_ARGS > "$L" 2> "${L%.json}.err" || { tail -5 "${L%.json}.err"; exit 2; }
+    L=$OUT/${TAG}_${n}_$i.json
+    env $vars timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 40 --warmup 20 --serial-frames 20 $BENCH_ARGS > "$L" 2> "${L%.json}.err" || { tail -5 "${L%.json}.err"; exit 2; }
     python3 - "$L" "$n" "$i" <<'PY' | tee -a "$S"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

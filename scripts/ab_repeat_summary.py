@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Mean / min / max fps and megakernel ms per variant of an ab_repeat.sh run (gpurun_out/rep_*.log)."""
-import collections, glob, json, re, statistics
+"""Mean / min / max fps and megakernel ms per variant of an ab_repeat.sh run (rep_*.log under $FOVRT_OUT, default bench_out)."""
+import collections, glob, json, os, re, statistics
 
+OUT = os.environ.get("FOVRT_OUT", "bench_out")
 runs = collections.defaultdict(list)
-for f in glob.glob("gpurun_out/rep_*.log"):
-    name = re.match(r"gpurun_out/rep_(.*)_\d+\.log", f).group(1)
+for f in glob.glob(os.path.join(OUT, "rep_*.log")):
+    name = re.match(r"rep_(.*)_\d+\.log", os.path.basename(f)).group(1)
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Prints value / fps / stage ms of the bench logs an A/B or sweep run left under gpurun_out/."""
-import glob, json, sys
-for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ab_*.log")):
+"""Prints value / fps / stage ms of the bench logs an A/B or sweep run left under $FOVRT_OUT (default bench_out)."""
+import glob, json, os, sys
+for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.environ.get("FOVRT_OUT", "bench_out"), "ab_*.log"))):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

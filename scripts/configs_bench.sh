@@ -1,12 +1,13 @@
 #!/bin/bash
 # One bench line per BASELINE.json config that fits one GPU (configs[3]/[4] as their one-GPU share:
 # one 4K vokselia view; the 4/8-GPU tilings themselves run under the driver's multi-GPU bench):
-#   scripts/configs_bench.sh  ->  gpurun_out/cfg_C*.log (summary: scripts/configs_summary.py)
+#   scripts/configs_bench.sh  ->  $OUT/cfg_C*.log (summary: scripts/configs_summary.py)
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${FOVRT_OUT:-bench_out}  # where the logs go
+mkdir -p $OUT
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-frames 1 "$@" > gpurun_out/cfg_$name.log 2>&1 || { tail -5 gpurun_out/cfg_$name.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-frames 1 "$@" > $OUT/cfg_$name.log 2>&1 || { tail -5 $OUT/cfg_$name.log; exit 1; }
   echo "$name done"
 }
 run C1 --scene box --width 512 --height 512 --spp 1 --dmd 1 --mask uniform

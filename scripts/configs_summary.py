@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Condenses gpurun_out/cfg_C*.log (scripts/configs_bench.sh) into one JSON line per config."""
-import glob, json, re, sys
+"""Condenses cfg_C*.log under $FOVRT_OUT, default bench_out (scripts/configs_bench.sh) into one JSON line per config."""
+import glob, json, os, re, sys
 
 out = []
-for f in sorted(glob.glob("gpurun_out/cfg_C*.log")):
+for f in sorted(glob.glob(os.path.join(os.environ.get("FOVRT_OUT", "bench_out"), "cfg_C*.log"))):
     name = re.search(r"cfg_(C\d\w*)\.log", f).group(1)
     lines = [l for l in open(f) if l.startswith("{")]
     if not lines:

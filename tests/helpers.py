@@ -4,7 +4,8 @@ import os
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASSET_DIR = os.path.join(ROOT, "assets")
+# The suite's textures are stored with it (tests/golden/textures/README.md), so every checkout tests the same scenes.
+ASSET_DIR = os.path.join(ROOT, "tests", "golden", "textures")
 ASSETS_PRESENT = all(os.path.exists(os.path.join(ASSET_DIR, p))
                      for p in ("CedarCity.hdr", "grid.ppm", "bunny/bunny.PPM", "vokselia_spawn/vokselia_spawn.png"))
 TEXTURE_MODE = 0 if ASSETS_PRESENT else 1
