@@ -1943,6 +1943,25 @@ int fr__pack_texture(const float* rgba, int n, uint32_t* out) {
   return kind;
 }
 
+// Test hook (not part of include/fovrt.h): the tree in use, whichever builder made it, copied to the host:
+// fr_scene_export's bvh_nodes BvhNode, then num_tris TriGeo and num_tris leaf-order primitive indices.
+int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size_t tri_bytes, int32_t* prim,
+                 size_t prim_bytes) {
+  if (!c || !nodes || !tri_geo || !prim) return FR_E_INVALID;
+  const Bvh& b = c->bvh;
+  const size_t nn = (size_t)(b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size());
+  const size_t nt = (size_t)c->scene.num_tris();
+  if (nodes_bytes < nn * sizeof(BvhNode) || tri_bytes < nt * sizeof(TriGeo) || prim_bytes < nt * sizeof(int32_t))
+    return fail(c, FR_E_INVALID, "fr__bvh_read: buffer too small");
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(nodes, c->d_nodes, nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(tri_geo, c->d_tri, nt * sizeof(TriGeo), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(prim, c->d_prim, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return FR_OK;
+}
+
 int fr_kernel_timing(fr_ctx* c, int enable) {
   if (!c) return FR_E_INVALID;
   if (enable && !c->kt_ev[0][0])
@@ -2075,6 +2094,19 @@ int fr_scene_create(const fr_config* cfg_in, fr_scene** out) {
 int fr_scene_get_arrays(fr_scene* sc, fr_scene_arrays* o) {
   if (!sc || !o) return FR_E_INVALID;
   fill_arrays(sc->scene, sc->bvh, sc->scene.light_emission, sc->mat_pairs, sc->tex_dims, sc->tex_ptrs, o);
+  return FR_OK;
+}
+
+// Test hook (not part of include/fovrt.h): the host-built tree of an fr_scene (pointers into it, valid until
+// fr_scene_destroy): num_nodes BvhNode, then num_leaf_tris TriGeo and leaf-order primitive indices.
+int fr__scene_bvh(fr_scene* sc, const void** nodes, int* num_nodes, const void** tri_geo, const int32_t** prim,
+                  int* num_leaf_tris) {
+  if (!sc || !nodes || !num_nodes || !tri_geo || !prim || !num_leaf_tris) return FR_E_INVALID;
+  *nodes = sc->bvh.nodes.data();
+  *num_nodes = (int)sc->bvh.nodes.size();
+  *tri_geo = sc->bvh.tri_geo.data();
+  *prim = sc->bvh.tri_prim.data();
+  *num_leaf_tris = (int)sc->bvh.tri_prim.size();
   return FR_OK;
 }
 
