@@ -493,7 +493,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     if (dalloc((T**)dst, vec.size()) != hipSuccess) return false;
     return hipMemcpy(*dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
   };
-  if (!up(&c->d_shade, shade) || !up(&c->d_pos, s.pos)) {
+  if (!up(&c->d_shade, shade) || !up(&c->d_pos, s.pos) || dalloc(&c->spare_pos, s.pos.size()) != hipSuccess) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
@@ -672,7 +672,7 @@ int fr_destroy(fr_ctx* c) {
   if (c->stream5) hipStreamSynchronize(c->stream5);
   auto fr = [](void* p) { if (p) hipFree(p); };
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
-  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim);
+  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   for (auto p : c->d_tex) fr(p);
   fr(c->d_mats); fr(c->d_texs);
@@ -1770,36 +1770,113 @@ int fr_rebuild_bvh(fr_ctx* c, float* ms) {
   return rc;
 }
 
-static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
-int fr_set_positions(fr_ctx* c, const float* xyz, size_t ntris) {
-  if (!c || !xyz) return FR_E_INVALID;
-  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, "fr_set_positions: triangle count differs");
-  for (size_t i = 0; i < ntris * 9; i++)
-    if (!std::isfinite(xyz[i])) return fail(c, FR_E_INVALID, "fr_set_positions: position not finite");
+static int tree_nodes(const Bvh& b) {
+  return b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size();
+}
+
+// Refit of the tree in use (either builder's) over `pos` (device), in place (k_bvh.hip). The caller has joined
+// and synchronised the context stream.
+static int gpu_refit(fr_ctx* c, const f3* pos) {
+  std::string err;
+  const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->d_nodes, nn, c->d_tri, c->d_prim, c->stream, err)) {
+    c->err = err;
+    return c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED;
+  }
+  return FR_OK;
+}
+
+int fr_refit_bvh(fr_ctx* c, float* ms) {
+  if (!c) return FR_E_INVALID;
   join_recon(c);
   hipSetDevice(c->cfg.device);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // the BVH is built from the device copy; the context commits the new positions (host mirror,
-  // bounding box) only once the rebuild succeeded, and puts the old device copy back otherwise
-  const size_t bytes = ntris * 9 * sizeof(float);
-  HIP_TRY(c, hipMemcpy(c->d_pos, xyz, bytes, hipMemcpyHostToDevice));
-  if (const int rc = gpu_rebuild(c)) {
-    const std::string why = c->err;
-    if (hipMemcpy(c->d_pos, c->scene.pos.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(c, FR_E_HIP, "fr_set_positions: rebuild failed (" + why + ") and the old positions could not be restored");
-    return fail(c, rc, "fr_set_positions: rebuild failed, scene unchanged: " + why);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = gpu_refit(c, c->d_pos);
+  if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int fr_bvh_sah_cost(fr_ctx* c, float* cost) {
+  if (!c || !cost) return FR_E_INVALID;
+  if (c->bvh.root_count > 0) { *cost = (float)c->bvh.root_count; return FR_OK; }  // one leaf: its triangles
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  std::string err;
+  if (!gpu_bvh_cost(c->bvh_work, c->d_nodes, tree_nodes(c->bvh), cost, c->stream, err))
+    return fail(c, c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED, err);
+  return FR_OK;
+}
+
+static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
+// What fr_set_positions and fr_update_positions share. Everything that can reject the update runs before
+// anything of the scene is written: the new positions go to the spare device array, which becomes d_pos only
+// when the tree over it exists (a failed rebuild leaves d_pos, the tree, the box and the mirror as they were).
+static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how, const char* fn) {
+  const std::string name = fn;
+  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
+  if (where != FR_MEM_HOST && where != FR_MEM_DEVICE) return fail(c, FR_E_INVALID, name + ": bad memory kind");
+  if (how != FR_BVH_REBUILD && how != FR_BVH_REFIT) return fail(c, FR_E_INVALID, name + ": bad update kind");
+  if (where == FR_MEM_HOST) {
+    const float* h = static_cast<const float*>(xyz);
+    for (size_t i = 0; i < ntris * 9; i++)
+      if (!std::isfinite(h[i])) return fail(c, FR_E_INVALID, name + ": position not finite");
   }
-  memcpy(c->scene.pos.data(), xyz, bytes);
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+  if (where == FR_MEM_DEVICE) {
+    // finiteness and the scene box in one kernel over the caller's array, read back before d_pos changes
+    bool finite = false;
+    float box[6];
+    std::string err;
+    if (!gpu_check_positions(c->bvh_work, static_cast<const float*>(xyz), (int)ntris, &finite, box, c->stream, err))
+      return fail(c, c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED, name + ": " + err);
+    if (!finite) return fail(c, FR_E_INVALID, name + ": position not finite");
+    lo = mk3(box[0], box[1], box[2]);
+    hi = mk3(box[3], box[4], box[5]);
+  }
+  const size_t bytes = ntris * 9 * sizeof(float);
+  // (a device-to-device hipMemcpy returns before the copy ran, and the context stream is non-blocking: the
+  // copy goes on the context stream, ahead of the kernels that read it)
+  if (where == FR_MEM_HOST) HIP_TRY(c, hipMemcpy(c->spare_pos, xyz, bytes, hipMemcpyHostToDevice));
+  else HIP_TRY(c, hipMemcpyAsync(c->spare_pos, xyz, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (how == FR_BVH_REBUILD) {
+    std::swap(c->d_pos, c->spare_pos);  // gpu_rebuild builds over d_pos
+    if (const int rc = gpu_rebuild(c)) {
+      std::swap(c->d_pos, c->spare_pos);
+      return fail(c, rc, name + ": rebuild failed, scene unchanged: " + c->err);
+    }
+  } else {
+    if (const int rc = gpu_refit(c, c->spare_pos)) return fail(c, rc, name + ": " + c->err);
+    std::swap(c->d_pos, c->spare_pos);
+  }
+  if (where == FR_MEM_HOST) {
+    memcpy(c->scene.pos.data(), xyz, bytes);
+    c->pos_mirror_stale = false;
+    for (const f3& v : c->scene.pos) {
+      lo = mk3(fminf(lo.x, v.x), fminf(lo.y, v.y), fminf(lo.z, v.z));
+      hi = mk3(fmaxf(hi.x, v.x), fmaxf(hi.y, v.y), fmaxf(hi.z, v.z));
+    }
+  } else {
+    c->pos_mirror_stale = true;  // refreshed by the next fr_scene_export
+  }
   // bbox_min / bbox_max (the depth-saliency theta of k_sampling) follow the geometry, as the
   // reference's scene AABB does at load time (FR/PathTracer.cpp:601-602,663)
-  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
-  for (const f3& v : c->scene.pos) {
-    lo = mk3(fminf(lo.x, v.x), fminf(lo.y, v.y), fminf(lo.z, v.z));
-    hi = mk3(fmaxf(hi.x, v.x), fmaxf(hi.y, v.y), fmaxf(hi.z, v.z));
-  }
   c->scene.bbox_min = c->dsc.bbox_min = lo;
   c->scene.bbox_max = c->dsc.bbox_max = hi;
   return FR_OK;
+}
+
+int fr_set_positions(fr_ctx* c, const float* xyz, size_t ntris) {
+  if (!c || !xyz) return FR_E_INVALID;
+  return update_positions(c, xyz, ntris, FR_MEM_HOST, FR_BVH_REBUILD, "fr_set_positions");
+}
+
+int fr_update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how) {
+  if (!c || !xyz) return FR_E_INVALID;
+  return update_positions(c, xyz, ntris, where, how, "fr_update_positions");
 }
 
 #ifdef FR_STAMPS
@@ -1949,7 +2026,7 @@ int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size
                  size_t prim_bytes) {
   if (!c || !nodes || !tri_geo || !prim) return FR_E_INVALID;
   const Bvh& b = c->bvh;
-  const size_t nn = (size_t)(b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size());
+  const size_t nn = (size_t)tree_nodes(b);
   const size_t nt = (size_t)c->scene.num_tris();
   if (nodes_bytes < nn * sizeof(BvhNode) || tri_bytes < nt * sizeof(TriGeo) || prim_bytes < nt * sizeof(int32_t))
     return fail(c, FR_E_INVALID, "fr__bvh_read: buffer too small");
@@ -2068,6 +2145,11 @@ extern "C" {
 
 int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
   if (!c || !o) return FR_E_INVALID;
+  if (c->pos_mirror_stale) {  // positions last came from device memory (fr_update_positions): fetch them now
+    hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipMemcpy(c->scene.pos.data(), c->d_pos, c->scene.pos.size() * sizeof(f3), hipMemcpyDeviceToHost));
+    c->pos_mirror_stale = false;
+  }
   fill_arrays(c->scene, c->bvh, c->dsc.light_emission, c->mat_pairs, c->tex_dims, c->tex_ptrs, o);
   return FR_OK;
 }

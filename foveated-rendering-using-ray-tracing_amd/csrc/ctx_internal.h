@@ -58,6 +58,9 @@ bool gpu_build_bvh(BvhWork**, const f3*, int, BvhNode*, TriGeo*, int32_t*, int*,
 void bvh_work_free(BvhWork*);
 bool bvh_work_prepare(BvhWork**, int, hipStream_t, std::string&);
 bool bvh_builder_warm(BvhWork*, hipStream_t, std::string&);
+bool gpu_refit_bvh(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, hipStream_t, std::string&);
+bool gpu_bvh_cost(BvhWork*, const BvhNode*, int, float*, hipStream_t, std::string&);
+bool gpu_check_positions(BvhWork*, const float*, int, bool*, float*, hipStream_t, std::string&);
 #ifdef FR_STAMPS
 void launch_trace_queries(const DevScene&, const f4*, uint32_t, f4*, uint32_t*, hipStream_t, int);
 void diag_record_queries(f4*, uint32_t, hipStream_t);
@@ -174,6 +177,12 @@ struct fr_ctx {
   BvhNode* spare_nodes = nullptr;
   TriGeo* spare_tri = nullptr;
   int32_t* spare_prim = nullptr;
+  // fr_update_positions writes new positions here and swaps with d_pos once the update succeeded: the old
+  // positions survive a failed rebuild on the device, without the host mirror
+  f3* spare_pos = nullptr;
+  // scene.pos (the host mirror of d_pos) is behind: positions came from device memory and were not copied
+  // back. fr_scene_export refreshes it; nothing else reads it.
+  bool pos_mirror_stale = false;
   fr::BvhWork* bvh_work = nullptr;
   bool tree_full_cap = false;  // d_nodes / d_tri / d_prim hold one entry per triangle (a device-built tree)
   TriShade* d_shade = nullptr;

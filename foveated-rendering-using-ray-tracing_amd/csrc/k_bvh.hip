@@ -15,6 +15,10 @@
 // binary hierarchy -> bottom-up boxes (one atomic per internal node) -> level-synchronous collapse
 // into four-wide nodes (the host's rule: open the largest-area inner entry until four) -> per-node
 // leaf triangle counts, exclusive scan, triangle relayout.
+//
+// Also here, for geometry that moves without regrouping: the refit of an existing four-wide tree of either
+// builder (gpu_refit_bvh: same topology, new boxes and leaf triangles), the tree's SAH cost (gpu_bvh_cost) and
+// the check of positions handed over in device memory (gpu_check_positions).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -270,8 +274,17 @@ __global__ void k_leaf_counts(const BvhNode* __restrict__ nodes, int nn, uint32_
   cnt[i] = s;
 }
 
-// Leaf children of node i -> one contiguous range starting at off[i]; TriGeo with the host's
-// operations (scene.cpp: e0 = p1 - p0, e1 = p0 - p2, n = cross(e1, e0)).
+// TriGeo of primitive p with the host's operations (scene.cpp: e0 = p1 - p0, e1 = p0 - p2, n = cross(e1, e0),
+// unfused); the builder's leaves and the refit share it.
+FR_DEV void store_tri_geo(const f3* __restrict__ pos, int p, TriGeo* __restrict__ out) {
+  const f3 p0 = pos[3 * p], p1 = pos[3 * p + 1], p2 = pos[3 * p + 2];
+  const f3 e0 = p1 - p0, e1 = p0 - p2, nn3 = cross(e1, e0);
+  out->a = mk4(p0.x, p0.y, p0.z, e0.x);
+  out->b = mk4(e0.y, e0.z, e1.x, e1.y);
+  out->c = mk4(e1.z, nn3.x, nn3.y, nn3.z);
+}
+
+// Leaf children of node i -> one contiguous range starting at off[i].
 __global__ void k_emit_leaves(BvhNode* __restrict__ nodes, int nn, const uint32_t* __restrict__ off,
                               const int32_t* __restrict__ ids, const f3* __restrict__ pos, TriGeo* __restrict__ tri,
                               int32_t* __restrict__ prim) {
@@ -286,12 +299,131 @@ __global__ void k_emit_leaves(BvhNode* __restrict__ nodes, int nn, const uint32_
     for (int j = 0; j < cnt; j++, o++) {
       const int p = ids[first + j];
       prim[o] = p;
-      const f3 p0 = pos[3 * p], p1 = pos[3 * p + 1], p2 = pos[3 * p + 2];
-      const f3 e0 = p1 - p0, e1 = p0 - p2, nn3 = cross(e1, e0);
-      tri[o].a = mk4(p0.x, p0.y, p0.z, e0.x);
-      tri[o].b = mk4(e0.y, e0.z, e1.x, e1.y);
-      tri[o].c = mk4(e1.z, nn3.x, nn3.y, nn3.z);
+      store_tri_geo(pos, p, &tri[o]);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Refit: new boxes and leaf triangles for an existing four-wide tree (either builder's); child, count,
+// prim and the node order stay.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_refit_tris(const f3* __restrict__ pos, const int32_t* __restrict__ prim, int n, TriGeo* __restrict__ tri) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) store_tri_geo(pos, prim[j], &tri[j]);
+}
+
+// Parent links (node, not slot) from the nodes themselves, and the arrival counters back to zero.
+__global__ void k_refit_links(const BvhNode* __restrict__ nodes, int nn, int* __restrict__ parent,
+                              uint32_t* __restrict__ arrivals) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  arrivals[i] = 0u;
+  if (i == 0) parent[0] = -1;
+  for (int k = 0; k < 4; k++)
+    if (nodes[i].count[k] == 0) parent[nodes[i].child[k]] = i;
+}
+
+FR_DEV void store_agent(f4* p, f3 v) {
+  float* q = reinterpret_cast<float*>(p);
+  __hip_atomic_store(q, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(q + 1, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(q + 2, v.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Bottom-up boxes over the four-wide tree, k_boxes_up's scheme: a node without inner slots starts a walk; a
+// thread that finishes a node arrives at its parent, and the last of the parent's inner children to arrive
+// (which then sees every child's raw box) goes on with the parent. nlo / nhi hold the raw (uninflated) box of
+// each node; a slot stores inflate(raw). Nobody waits: a walk that is not the last arrival ends.
+__global__ void k_refit_up(BvhNode* nodes, int nn, const f3* __restrict__ pos, const int32_t* __restrict__ prim,
+                           const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  int node = i;
+  {
+    const int* cnt = nodes[i].count;
+    if (cnt[0] == 0 || cnt[1] == 0 || cnt[2] == 0 || cnt[3] == 0) return;
+  }
+  for (;;) {
+    BvhNode* nd = nodes + node;
+    float* LX = &nd->lox.x; float* HX = &nd->hix.x;
+    float* LY = &nd->loy.x; float* HY = &nd->hiy.x;
+    float* LZ = &nd->loz.x; float* HZ = &nd->hiz.x;
+    f3 nlo3 = mk3(INFINITY), nhi3 = mk3(-INFINITY);
+    for (int k = 0; k < 4; k++) {
+      const int cnt = nd->count[k], ch = nd->child[k];
+      if (cnt < 0) continue;  // an empty slot stays +inf / -inf / child 0
+      f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+      if (cnt == 0) {
+        lo = xyz(load_agent(nlo + ch));
+        hi = xyz(load_agent(nhi + ch));
+      } else {
+        for (int j = 0; j < cnt; j++) {
+          const int p = prim[ch + j];
+          for (int v = 0; v < 3; v++) {
+            const f3 q = pos[3 * p + v];
+            lo = mk3(fminf(lo.x, q.x), fminf(lo.y, q.y), fminf(lo.z, q.z));
+            hi = mk3(fmaxf(hi.x, q.x), fmaxf(hi.y, q.y), fmaxf(hi.z, q.z));
+          }
+        }
+      }
+      LX[k] = inflate_lo_d(lo.x); HX[k] = inflate_hi_d(hi.x);
+      LY[k] = inflate_lo_d(lo.y); HY[k] = inflate_hi_d(hi.y);
+      LZ[k] = inflate_lo_d(lo.z); HZ[k] = inflate_hi_d(hi.z);
+      nlo3 = mk3(fminf(nlo3.x, lo.x), fminf(nlo3.y, lo.y), fminf(nlo3.z, lo.z));
+      nhi3 = mk3(fmaxf(nhi3.x, hi.x), fmaxf(nhi3.y, hi.y), fmaxf(nhi3.z, hi.z));
+    }
+    const int up = parent[node];
+    if (up < 0) return;
+    store_agent(nlo + node, nlo3);
+    store_agent(nhi + node, nhi3);
+    const int* pc = nodes[up].count;
+    const uint32_t inner = (uint32_t)(pc[0] == 0) + (uint32_t)(pc[1] == 0) + (uint32_t)(pc[2] == 0) + (uint32_t)(pc[3] == 0);
+    if (__hip_atomic_fetch_add(&arrivals[up], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u != inner) return;
+    node = up;
+  }
+}
+
+// SAH cost terms: part[i] = sum over node i's non-empty slots of area(stored box) * (1 for an inner slot, count
+// for a leaf slot); *root_area = the area of the union of node 0's slot boxes.
+__global__ void k_cost_terms(const BvhNode* __restrict__ nodes, int nn, float* __restrict__ part,
+                             float* __restrict__ root_area) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  const BvhNode nd = nodes[i];
+  const float* LX = &nd.lox.x; const float* HX = &nd.hix.x;
+  const float* LY = &nd.loy.x; const float* HY = &nd.hiy.x;
+  const float* LZ = &nd.loz.x; const float* HZ = &nd.hiz.x;
+  float s = 0.0f;
+  f4 ulo = mk4(INFINITY, INFINITY, INFINITY, 0.0f), uhi = mk4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+  for (int k = 0; k < 4; k++) {
+    if (nd.count[k] < 0) continue;
+    const f4 lo = mk4(LX[k], LY[k], LZ[k], 0.0f), hi = mk4(HX[k], HY[k], HZ[k], 0.0f);
+    s += area_of(lo, hi) * (nd.count[k] > 0 ? (float)nd.count[k] : 1.0f);
+    ulo = mk4(fminf(ulo.x, lo.x), fminf(ulo.y, lo.y), fminf(ulo.z, lo.z), 0.0f);
+    uhi = mk4(fmaxf(uhi.x, hi.x), fmaxf(uhi.y, hi.y), fmaxf(uhi.z, hi.z), 0.0f);
+  }
+  part[i] = s;
+  if (i == 0) *root_area = area_of(ulo, uhi);
+}
+
+// A caller's device positions before they are taken over: cb[0..5] = the box of all vertices (order-mapped, as
+// in k_prim_boxes), cb[6] != 0 when a coordinate is not finite.
+__global__ void k_check_positions(const float* __restrict__ xyz, size_t nverts, uint32_t* __restrict__ cb) {
+  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+  bool bad = false;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nverts; i += (size_t)gridDim.x * blockDim.x) {
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    bad |= !(isfinite(x) && isfinite(y) && isfinite(z));
+    lo = mk3(fminf(lo.x, x), fminf(lo.y, y), fminf(lo.z, z));
+    hi = mk3(fmaxf(hi.x, x), fmaxf(hi.y, y), fmaxf(hi.z, z));
+  }
+  const float r[6] = {wave_min(lo.x), wave_min(lo.y), wave_min(lo.z), wave_max(hi.x), wave_max(hi.y), wave_max(hi.z)};
+  const bool any_bad = __any(bad);
+  if ((threadIdx.x & 63) == 0) {
+    for (int k = 0; k < 3; k++) atomicMin(&cb[k], ord(r[k]));
+    for (int k = 3; k < 6; k++) atomicMax(&cb[k], ord(r[k]));
+    if (any_bad) atomicOr(&cb[6], 1u);
   }
 }
 
@@ -315,7 +447,7 @@ struct BvhWork {
   CollapseItem *qa = nullptr, *qb = nullptr;
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
-  uint32_t* host = nullptr;  // pinned: ncur, node count, max stack, levels
+  uint32_t* host = nullptr;  // pinned, 8 words: the builder's counters; the position check's box and flag; the cost's sums
 };
 
 void bvh_work_free(BvhWork* w) {
@@ -332,7 +464,7 @@ static bool bvh_work_reserve(BvhWork*& w, int n, hipStream_t s, std::string& err
   if (w && w->cap >= n) return true;
   bvh_work_free(w);
   w = new BvhWork();
-  if (alloc(&w->blo, n) || alloc(&w->bhi, n) || alloc(&w->nlo, n) || alloc(&w->nhi, n) || alloc(&w->cb, 6) ||
+  if (alloc(&w->blo, n) || alloc(&w->bhi, n) || alloc(&w->nlo, n) || alloc(&w->nhi, n) || alloc(&w->cb, 8) ||
       alloc(&w->codes, n) || alloc(&w->codes_s, n) || alloc(&w->ids, n) || alloc(&w->ids_s, n) || alloc(&w->child, n) ||
       alloc(&w->range, n) || alloc(&w->parent, 2 * n) || alloc(&w->arrivals, n) || alloc(&w->ctr, 8) ||
       alloc(&w->qa, n) || alloc(&w->qb, n) || alloc(&w->cnt, n) || alloc(&w->off, n) ||
@@ -342,10 +474,11 @@ static bool bvh_work_reserve(BvhWork*& w, int n, hipStream_t s, std::string& err
     w = nullptr;
     return false;
   }
-  size_t sort_bytes = 0, scan_bytes = 0;
+  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0;
   hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, w->codes, w->codes_s, w->ids, w->ids_s, n, 0, 30, s);
   hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, w->cnt, w->off, n, s);
-  w->tmp_bytes = std::max(sort_bytes, scan_bytes);
+  hipcub::DeviceReduce::Sum(nullptr, sum_bytes, (float*)nullptr, (float*)nullptr, n, s);  // gpu_bvh_cost
+  w->tmp_bytes = std::max(std::max(sort_bytes, scan_bytes), sum_bytes);
   if (hipMalloc(&w->tmp, w->tmp_bytes) != hipSuccess) {
     err = "GPU BVH builder: scratch allocation failed";
     bvh_work_free(w);
@@ -370,11 +503,11 @@ bool bvh_builder_warm(BvhWork* w, hipStream_t s, std::string& err) {
 
 // The builder's small initial values in one launch (they were three pageable host-to-device copies, which
 // go through the runtime's staging path: the first rebuilds of a context took 6-15 ms instead of 0.8-2).
-// cb: the scene box accumulators (min: +bits, max: 0); qa[0]: the root item; ctr: node_ctr, max_stack, ncur,
-// nnext, levels.
+// cb: the scene box accumulators (min: +bits, max: 0; then the position check's flag); qa[0]: the root item;
+// ctr: node_ctr, max_stack, ncur, nnext, levels.
 __global__ void k_build_init(uint32_t* __restrict__ cb, CollapseItem* __restrict__ qa, uint32_t* __restrict__ ctr) {
   const int t = threadIdx.x;
-  if (t < 6) cb[t] = t < 3 ? 0xFFFFFFFFu : 0u;
+  if (t < 8) cb[t] = t < 3 ? 0xFFFFFFFFu : 0u;
   if (t < 5) ctr[t] = t == 0 || t == 2 ? 1u : 0u;
   if (t == 0) qa[0] = CollapseItem{0, 0, 0};
 }
@@ -465,6 +598,82 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
     return false;
   }
   phase("emit");
+  return true;
+}
+
+// Refits the four-wide tree nodes[0, num_nodes) (either builder's) over new positions, in place: every slot box
+// and tri[j] for every leaf-order j are rewritten, child / count / prim are not. num_nodes == 0 (the whole scene
+// is one leaf): tri only. Three launches whatever the depth, no allocation; the scratch is *work's nlo / nhi
+// (raw node boxes), parent and arrivals, which hold one entry per triangle (a tree has at most as many nodes).
+bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
+                   hipStream_t s, std::string& err) {
+  if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
+    err = "GPU BVH refit: no workspace for this tree";
+    return false;
+  }
+  BvhWork& w = *work;
+  const int B = 256;
+  hipLaunchKernelGGL(k_refit_tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, prim, n, tri);
+  if (num_nodes > 0) {
+    const int GN = (num_nodes + B - 1) / B;
+    hipLaunchKernelGGL(k_refit_links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals);
+    hipLaunchKernelGGL(k_refit_up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo,
+                       w.nhi);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+    err = "GPU BVH refit: kernel failure";
+    return false;
+  }
+  return true;
+}
+
+// SAH cost of the tree: 1 + (sum over non-empty slots of area(stored box) * (1 | leaf count)) / area(root), the
+// root being the union of node 0's slot boxes. One f32 term per node, summed by hipCUB (a tree reduction: its
+// error does not grow with the node count as an atomic accumulation's would), the division in f64 on the host.
+bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cost, hipStream_t s, std::string& err) {
+  if (!work || num_nodes < 1 || num_nodes > work->cap) { err = "GPU BVH cost: no workspace for this tree"; return false; }
+  BvhWork& w = *work;
+  const int B = 256;
+  float* part = reinterpret_cast<float*>(w.codes);
+  float* sums = reinterpret_cast<float*>(w.ctr + 5);  // sum, root area
+  hipLaunchKernelGGL(k_cost_terms, dim3((num_nodes + B - 1) / B), dim3(B), 0, s, nodes, num_nodes, part, sums + 1);
+  size_t tb = w.tmp_bytes;
+  hipcub::DeviceReduce::Sum(w.tmp, tb, part, sums, num_nodes, s);
+  hipMemcpyAsync(w.host + 5, w.ctr + 5, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+    err = "GPU BVH cost: kernel failure";
+    return false;
+  }
+  float sum, root;
+  memcpy(&sum, w.host + 5, sizeof(float));
+  memcpy(&root, w.host + 6, sizeof(float));
+  if (!(root > 0.0f)) { err = "GPU BVH cost: the root box has no area"; return false; }
+  *cost = (float)(1.0 + (double)sum / (double)root);
+  return true;
+}
+
+// Checks n triangles of device positions (any device pointer the caller owns) in one pass: *finite, and
+// box[0..2] = min, box[3..5] = max over all vertices. One kernel, one small copy back.
+bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, float box[6], hipStream_t s,
+                         std::string& err) {
+  if (!work || n < 1) { err = "GPU position check: no workspace"; return false; }
+  BvhWork& w = *work;
+  hipLaunchKernelGGL(k_build_init, dim3(1), dim3(64), 0, s, w.cb, w.qa, w.ctr);
+  const int B = 256;
+  const size_t nverts = (size_t)n * 3;
+  const int G = (int)std::min<size_t>((nverts + B - 1) / B, 2048);
+  hipLaunchKernelGGL(k_check_positions, dim3(G), dim3(B), 0, s, xyz, nverts, w.cb);
+  hipMemcpyAsync(w.host, w.cb, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+    err = "GPU position check: kernel failure (is the pointer device memory of ntris x 9 floats?)";
+    return false;
+  }
+  *finite = w.host[6] == 0;
+  for (int k = 0; k < 6; k++) {
+    const uint32_t u = w.host[k];
+    const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;  // unord
+    memcpy(&box[k], &b, sizeof(float));
+  }
   return true;
 }
 

@@ -30,6 +30,9 @@ GROUP_MAX_VIEW_RANKS = 16
 FR_OK, FR_E_INVALID, FR_E_HIP, FR_E_NOMEM, FR_E_IO, FR_E_STATE, FR_E_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 # scenes / masks
 SCENE_BOX, SCENE_BUNNY, SCENE_VOKSELIA = 0, 1, 2
+# fr_update_positions: what follows the new positions, and where they come from
+FR_BVH_REBUILD, FR_BVH_REFIT = 0, 1
+FR_MEM_HOST, FR_MEM_DEVICE = 0, 1
 MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 0, 1, 2, 3, 4
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
@@ -169,6 +172,9 @@ _SIGS = {
     "fr_restore": [C.c_void_p, C.c_void_p, C.c_size_t],
     "fr_rebuild_bvh": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_set_positions": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
+    "fr_refit_bvh": [C.c_void_p, C.POINTER(C.c_float)],
+    "fr_update_positions": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int],
+    "fr_bvh_sah_cost": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_get_stats": [C.c_void_p, C.POINTER(fr_stats)],
     "fr_reset_stats": [C.c_void_p],
     "fr_kernel_timing": [C.c_void_p, C.c_int],
@@ -570,12 +576,43 @@ class PathTracer:
         """Re-indexes the current triangles with the GPU builder; returns its wall time in ms."""
         return self._launch(_lib.fr_rebuild_bvh)
 
-    def set_positions(self, xyz: np.ndarray):
+    def refit_bvh(self) -> float:
+        """Keeps the tree's topology and recomputes its boxes and leaf triangles from the current positions;
+        returns its wall time in ms."""
+        return self._launch(_lib.fr_refit_bvh)
+
+    @staticmethod
+    def _update_kind(update) -> int:
+        """"rebuild" / "refit" (or an fr_update_positions `how` value, passed through)."""
+        if isinstance(update, str):
+            try:
+                return {"rebuild": FR_BVH_REBUILD, "refit": FR_BVH_REFIT}[update]
+            except KeyError:
+                raise ValueError(f"update must be 'rebuild' or 'refit', not {update!r}") from None
+        return int(update)
+
+    def set_positions(self, xyz: np.ndarray, update="rebuild"):
         """New world-space vertex positions (ntris x 3 x 3 float32, scene triangle order), then a GPU
-        rebuild of the BVH."""
+        rebuild of the BVH (update="rebuild") or a refit of the tree in use (update="refit")."""
         a = np.ascontiguousarray(xyz, dtype=np.float32)
         n = a.size // 9
-        self._check(_lib.fr_set_positions(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float)), n))
+        if update == "rebuild":
+            self._check(_lib.fr_set_positions(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float)), n))
+        else:
+            self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(a.ctypes.data), n, FR_MEM_HOST,
+                                                 self._update_kind(update)))
+
+    def set_positions_device(self, device_ptr, ntris, update="rebuild"):
+        """As set_positions from device memory (e.g. tensor.data_ptr() of ntris x 9 float32 on this
+        context's device): checked on the device, never copied to the host unless scene_arrays() asks."""
+        self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(device_ptr), int(ntris), FR_MEM_DEVICE,
+                                             self._update_kind(update)))
+
+    def bvh_sah_cost(self) -> float:
+        """SAH cost of the tree in use (fr_bvh_sah_cost): compare a refitted tree with itself when built."""
+        v = C.c_float()
+        self._check(_lib.fr_bvh_sah_cost(self._ctx, C.byref(v)))
+        return v.value
 
     def set_gaze(self, xpos, ypos, fullscreen=False):
         """cursorPosCallback (FR/gui.cpp:48-66): the cursor in window coordinates (y down);

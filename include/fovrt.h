@@ -386,6 +386,29 @@ const char* fr_group_last_error(void);  /* the failure of the calling thread's l
  * shading normals, texture coordinates and materials are kept. */
 int fr_rebuild_bvh(fr_ctx* ctx, float* ms);
 int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
+/* Moving geometry without giving up the tree. fr_refit_bvh keeps the topology of the tree in use (whichever
+ * builder made it: the host SAH tree too) and recomputes every slot box bottom-up and every leaf triangle
+ * from the current positions, in place; node count, depth and stack need do not change; *ms = its wall time.
+ * fr_update_positions replaces the positions from host (FR_MEM_HOST) or device memory (FR_MEM_DEVICE: a
+ * pointer the context's device can read, 9 floats per triangle) and then rebuilds (FR_BVH_REBUILD, the LBVH
+ * of fr_rebuild_bvh) or refits (FR_BVH_REFIT). fr_set_positions is the HOST / REBUILD case. Every check
+ * (triangle count, where, how, finite positions: FR_E_INVALID) runs before anything is written, device
+ * positions are checked on the device, and a rebuild that fails (FR_E_UNSUPPORTED) leaves positions, tree and
+ * scene box as they were. Device positions are not copied back: fr_scene_export fetches them when asked.
+ * fr_bvh_sah_cost reports the quality of the tree in use, lower is better:
+ *   1 + (sum over non-empty slots of area(slot box) * (1 for an inner slot | triangles of a leaf slot))
+ *       / area(union of the root's slot boxes)
+ * so a caller can compare a refitted tree with the same tree when it was built and rebuild when it has grown.
+ * Not covered: an update without host synchronisation (these calls wait for the context's pending work and
+ * for their own kernels); groups (each rank's context is updated by its caller); shading normals, which are
+ * kept as for fr_set_positions. */
+#define FR_BVH_REBUILD 0
+#define FR_BVH_REFIT   1
+#define FR_MEM_HOST    0
+#define FR_MEM_DEVICE  1
+int fr_refit_bvh(fr_ctx* ctx, float* ms);
+int fr_update_positions(fr_ctx* ctx, const void* xyz, size_t ntris, int where, int how);
+int fr_bvh_sah_cost(fr_ctx* ctx, float* cost);
 /* Buffer access (PathTracer::get_texture, FR/PathTracer.cpp:337-374; rtBufferMap). */
 int fr_get_buffer(fr_ctx* ctx, int id, fr_buffer_view* view);
 int fr_read_buffer(fr_ctx* ctx, int id, void* host, size_t bytes);

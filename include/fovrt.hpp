@@ -162,6 +162,20 @@ class PathTracer {
   void set_positions(const float* xyz, size_t ntris) {  // moved vertices + GPU rebuild (fr_set_positions)
     check(fr_set_positions(ctx(), xyz, ntris), ctx_, "set_positions");
   }
+  float refit_bvh() {  // same topology, new boxes and leaf triangles (fr_refit_bvh), wall ms
+    float ms = 0.0f;
+    check(fr_refit_bvh(ctx(), &ms), ctx_, "refit_bvh");
+    return ms;
+  }
+  // moved vertices from host or device memory (FR_MEM_*), then a rebuild or a refit (FR_BVH_*)
+  void update_positions(const void* xyz, size_t ntris, int where, int how) {
+    check(fr_update_positions(ctx(), xyz, ntris, where, how), ctx_, "update_positions");
+  }
+  float bvh_sah_cost() {  // SAH cost of the tree in use (fr_bvh_sah_cost), lower is better
+    float cost = 0.0f;
+    check(fr_bvh_sah_cost(ctx(), &cost), ctx_, "bvh_sah_cost");
+    return cost;
+  }
   // cursorPosCallback (FR/gui.cpp:48-66): the cursor in window coordinates (y down); adjust_scale 1.25
   // in a window, 1 in full screen (g_fullScreen)
   void set_gaze(double xpos, double ypos, bool fullscreen = false) {
