@@ -497,6 +497,15 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
+  {  // the weld and the recompute's scratch exist from the start: an update of the normals allocates nothing
+    build_normal_groups(s, c->groups);
+    std::string werr;
+    if (!normals_work_create(&c->nrm_work, c->groups.corner_vertex.data(), c->groups.vert_off.data(),
+                             c->groups.vert_corners.data(), nt, c->groups.num_verts, c->stream, werr)) {
+      c->err = werr;
+      return bail(FR_E_NOMEM);
+    }
+  }
   // The tree arrays hold one entry per triangle (room for any device-built tree), and the GPU builder's
   // spare arrays and scratch exist from the start: fr_rebuild_bvh allocates nothing (hipMalloc / hipFree
   // in a rebuild cost ~10-20 ms and synchronise the device).
@@ -674,6 +683,7 @@ int fr_destroy(fr_ctx* c) {
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
   fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
+  if (c->nrm_work) normals_work_free(c->nrm_work);
   for (auto p : c->d_tex) fr(p);
   fr(c->d_mats); fr(c->d_texs);
   for (auto p : c->img) fr(p);
@@ -1809,18 +1819,59 @@ int fr_bvh_sah_cost(fr_ctx* c, float* cost) {
 }
 
 static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
-// What fr_set_positions and fr_update_positions share. Everything that can reject the update runs before
-// anything of the scene is written: the new positions go to the spare device array, which becomes d_pos only
-// when the tree over it exists (a failed rebuild leaves d_pos, the tree, the box and the mirror as they were).
-static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how, const char* fn) {
+// A caller's host normals: finite on every triangle that has normals (the others are ignored).
+static bool host_normals_finite(const fr_ctx* c, const float* nrm) {
+  const HostScene& s = c->scene;
+  for (size_t t = 0; t < (size_t)s.num_tris(); t++) {
+    if (!(s.flags[t] & FR_SHADE_HAS_NORMALS)) continue;
+    for (size_t i = 9 * t; i < 9 * t + 9; i++)
+      if (!std::isfinite(nrm[i])) return false;
+  }
+  return true;
+}
+
+// Normals from the caller's array into d_shade (the caller has joined and synchronised the context stream and
+// checked the array). Host normals are staged in spare_pos, which is free between updates and of the right size.
+static int write_given_normals(fr_ctx* c, const void* nrm, int where, const std::string& name) {
+  const float* src = static_cast<const float*>(nrm);
+  if (where == FR_MEM_HOST) {
+    HIP_TRY(c, hipMemcpy(c->spare_pos, nrm, c->scene.pos.size() * sizeof(f3), hipMemcpyHostToDevice));
+    src = &c->spare_pos[0].x;
+  }
+  std::string err;
+  if (!gpu_scatter_normals(c->nrm_work, src, c->d_shade, c->stream, err)) return fail(c, FR_E_HIP, name + ": " + err);
+  c->nrm_mirror_stale = true;  // refreshed by the next fr_scene_export
+  return FR_OK;
+}
+
+static int recompute_normals(fr_ctx* c, const std::string& name) {
+  std::string err;
+  if (!gpu_recompute_normals(c->nrm_work, c->d_pos, c->d_shade, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  c->nrm_mirror_stale = true;
+  return FR_OK;
+}
+
+// What fr_set_positions, fr_update_positions and fr_update_geometry share. Everything that can reject the update
+// runs before anything of the scene is written: the new positions go to the spare device array, which becomes
+// d_pos only when the tree over it exists (a failed rebuild leaves d_pos, the tree, the box and the mirror as
+// they were). A caller's normals (FR_NORMALS_GIVEN) are checked with the positions, and the normals are written
+// last, when positions and tree are in place: nothing after that point rejects the update.
+static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how, const char* fn,
+                            const void* nrm = nullptr, int normals = FR_NORMALS_KEEP) {
   const std::string name = fn;
   if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
   if (where != FR_MEM_HOST && where != FR_MEM_DEVICE) return fail(c, FR_E_INVALID, name + ": bad memory kind");
   if (how != FR_BVH_REBUILD && how != FR_BVH_REFIT) return fail(c, FR_E_INVALID, name + ": bad update kind");
+  if (normals != FR_NORMALS_KEEP && normals != FR_NORMALS_GIVEN && normals != FR_NORMALS_RECOMPUTE)
+    return fail(c, FR_E_INVALID, name + ": bad normals kind");
+  if (normals == FR_NORMALS_GIVEN && !nrm) return fail(c, FR_E_INVALID, name + ": FR_NORMALS_GIVEN without normals");
   if (where == FR_MEM_HOST) {
     const float* h = static_cast<const float*>(xyz);
     for (size_t i = 0; i < ntris * 9; i++)
       if (!std::isfinite(h[i])) return fail(c, FR_E_INVALID, name + ": position not finite");
+    if (normals == FR_NORMALS_GIVEN && !host_normals_finite(c, static_cast<const float*>(nrm)))
+      return fail(c, FR_E_INVALID, name + ": normal not finite");
   }
   join_recon(c);
   hipSetDevice(c->cfg.device);
@@ -1836,6 +1887,11 @@ static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where,
     if (!finite) return fail(c, FR_E_INVALID, name + ": position not finite");
     lo = mk3(box[0], box[1], box[2]);
     hi = mk3(box[3], box[4], box[5]);
+    if (normals == FR_NORMALS_GIVEN) {
+      if (!gpu_check_normals(c->nrm_work, static_cast<const float*>(nrm), &finite, c->stream, err))
+        return fail(c, FR_E_HIP, name + ": " + err);
+      if (!finite) return fail(c, FR_E_INVALID, name + ": normal not finite");
+    }
   }
   const size_t bytes = ntris * 9 * sizeof(float);
   // (a device-to-device hipMemcpy returns before the copy ran, and the context stream is non-blocking: the
@@ -1866,6 +1922,10 @@ static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where,
   // reference's scene AABB does at load time (FR/PathTracer.cpp:601-602,663)
   c->scene.bbox_min = c->dsc.bbox_min = lo;
   c->scene.bbox_max = c->dsc.bbox_max = hi;
+  // the normals last, over the positions and the tree now in place (spare_pos holds the replaced positions
+  // and is free again)
+  if (normals == FR_NORMALS_GIVEN) return write_given_normals(c, nrm, where, name);
+  if (normals == FR_NORMALS_RECOMPUTE) return recompute_normals(c, name);
   return FR_OK;
 }
 
@@ -1877,6 +1937,60 @@ int fr_set_positions(fr_ctx* c, const float* xyz, size_t ntris) {
 int fr_update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how) {
   if (!c || !xyz) return FR_E_INVALID;
   return update_positions(c, xyz, ntris, where, how, "fr_update_positions");
+}
+
+int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int where, int how, int normals) {
+  if (!c) return FR_E_INVALID;
+  if (!xyz) return fail(c, FR_E_INVALID, "fr_update_geometry: positions are NULL");
+  return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
+}
+
+int fr_set_normals(fr_ctx* c, const void* nrm, size_t ntris, int where) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_normals";
+  if (!nrm) return fail(c, FR_E_INVALID, name + ": normals are NULL");
+  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
+  if (where != FR_MEM_HOST && where != FR_MEM_DEVICE) return fail(c, FR_E_INVALID, name + ": bad memory kind");
+  if (where == FR_MEM_HOST && !host_normals_finite(c, static_cast<const float*>(nrm)))
+    return fail(c, FR_E_INVALID, name + ": normal not finite");
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (where == FR_MEM_DEVICE) {
+    bool finite = false;
+    std::string err;
+    if (!gpu_check_normals(c->nrm_work, static_cast<const float*>(nrm), &finite, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    if (!finite) return fail(c, FR_E_INVALID, name + ": normal not finite");
+  }
+  return write_given_normals(c, nrm, where, name);
+}
+
+int fr_recompute_normals(fr_ctx* c, float* ms) {
+  if (!c) return FR_E_INVALID;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = recompute_normals(c, "fr_recompute_normals");
+  if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+static int copy_groups(const NormalGroups& g, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (corner_vertex) {
+    if (ncorners != g.corner_vertex.size()) return FR_E_INVALID;
+    memcpy(corner_vertex, g.corner_vertex.data(), ncorners * sizeof(int32_t));
+  }
+  if (nverts) *nverts = g.num_verts;
+  return FR_OK;
+}
+
+int fr_normal_groups(fr_ctx* c, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (!c) return FR_E_INVALID;
+  if (copy_groups(c->groups, corner_vertex, ncorners, nverts))
+    return fail(c, FR_E_INVALID, "fr_normal_groups: ncorners is not 3 per triangle");
+  return FR_OK;
 }
 
 #ifdef FR_STAMPS
@@ -2112,6 +2226,7 @@ int P_wgt(const fr_ctx* c) { return ::P_wgt(c); }
 struct fr_scene {
   HostScene scene;
   Bvh bvh;
+  NormalGroups groups;
   std::string err;
   std::vector<const float*> tex_ptrs;
   std::vector<int32_t> tex_dims, mat_pairs;
@@ -2150,6 +2265,17 @@ int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
     HIP_TRY(c, hipMemcpy(c->scene.pos.data(), c->d_pos, c->scene.pos.size() * sizeof(f3), hipMemcpyDeviceToHost));
     c->pos_mirror_stale = false;
   }
+  if (c->nrm_mirror_stale) {  // normals were last written on the device: they are d_shade's n0 / n1 / n2 .xyz
+    hipSetDevice(c->cfg.device);
+    std::vector<TriShade> shade(c->scene.flags.size());
+    HIP_TRY(c, hipMemcpy(shade.data(), c->d_shade, shade.size() * sizeof(TriShade), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < shade.size(); i++) {
+      c->scene.nrm[3 * i] = xyz(shade[i].n0);
+      c->scene.nrm[3 * i + 1] = xyz(shade[i].n1);
+      c->scene.nrm[3 * i + 2] = xyz(shade[i].n2);
+    }
+    c->nrm_mirror_stale = false;
+  }
   fill_arrays(c->scene, c->bvh, c->dsc.light_emission, c->mat_pairs, c->tex_dims, c->tex_ptrs, o);
   return FR_OK;
 }
@@ -2169,6 +2295,7 @@ int fr_scene_create(const fr_config* cfg_in, fr_scene** out) {
     return fail(nullptr, FR_E_IO, "scene: " + err);
   }
   build_bvh(sc->scene, sc->bvh);
+  build_normal_groups(sc->scene, sc->groups);
   *out = sc;
   return FR_OK;
 }
@@ -2177,6 +2304,11 @@ int fr_scene_get_arrays(fr_scene* sc, fr_scene_arrays* o) {
   if (!sc || !o) return FR_E_INVALID;
   fill_arrays(sc->scene, sc->bvh, sc->scene.light_emission, sc->mat_pairs, sc->tex_dims, sc->tex_ptrs, o);
   return FR_OK;
+}
+
+int fr_scene_normal_groups(fr_scene* sc, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (!sc) return FR_E_INVALID;
+  return copy_groups(sc->groups, corner_vertex, ncorners, nverts);
 }
 
 // Test hook (not part of include/fovrt.h): the host-built tree of an fr_scene (pointers into it, valid until

@@ -61,6 +61,14 @@ bool bvh_builder_warm(BvhWork*, hipStream_t, std::string&);
 bool gpu_refit_bvh(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, hipStream_t, std::string&);
 bool gpu_bvh_cost(BvhWork*, const BvhNode*, int, float*, hipStream_t, std::string&);
 bool gpu_check_positions(BvhWork*, const float*, int, bool*, float*, hipStream_t, std::string&);
+// shading normals over moving geometry (k_normals.hip)
+struct NormalsWork;
+bool normals_work_create(NormalsWork**, const int32_t*, const int32_t*, const int32_t*, int, int, hipStream_t,
+                         std::string&);
+void normals_work_free(NormalsWork*);
+bool gpu_recompute_normals(NormalsWork*, const f3*, TriShade*, hipStream_t, std::string&);
+bool gpu_check_normals(NormalsWork*, const float*, bool*, hipStream_t, std::string&);
+bool gpu_scatter_normals(NormalsWork*, const float*, TriShade*, hipStream_t, std::string&);
 #ifdef FR_STAMPS
 void launch_trace_queries(const DevScene&, const f4*, uint32_t, f4*, uint32_t*, hipStream_t, int);
 void diag_record_queries(f4*, uint32_t, hipStream_t);
@@ -184,6 +192,13 @@ struct fr_ctx {
   // back. fr_scene_export refreshes it; nothing else reads it.
   bool pos_mirror_stale = false;
   fr::BvhWork* bvh_work = nullptr;
+  // the smooth-vertex weld of the scene as fr_create built it (host), and on the device with the scratch of
+  // a normal recompute (k_normals.hip); fixed for the life of the context
+  fr::NormalGroups groups;
+  fr::NormalsWork* nrm_work = nullptr;
+  // scene.nrm (the host mirror of d_shade's normals) is behind: normals were written on the device.
+  // fr_scene_export refreshes it; nothing else reads it.
+  bool nrm_mirror_stale = false;
   bool tree_full_cap = false;  // d_nodes / d_tri / d_prim hold one entry per triangle (a device-built tree)
   TriShade* d_shade = nullptr;
   std::vector<void*> d_tex;

@@ -904,4 +904,45 @@ void build_bvh(const HostScene& s, Bvh& out) {
   b.run();
 }
 
+void build_normal_groups(const HostScene& s, NormalGroups& out) {
+  const int nt = s.num_tris();
+  const size_t nc = 3 * (size_t)nt;
+  struct Key { uint32_t w[6]; };
+  std::vector<Key> keys(nc);
+  // first[c]: the lowest corner with c's key (a vertex is named by it for now), found through an open-addressing
+  // table of corners, filled in ascending corner order
+  constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+  size_t cap = 16;
+  while (cap < 2 * nc) cap *= 2;
+  std::vector<uint32_t> table(cap, kEmpty), first(nc, 0);
+  size_t with_normals = 0;
+  for (size_t c = 0; c < nc; c++) {
+    if (!(s.flags[c / 3] & FR_SHADE_HAS_NORMALS)) continue;
+    with_normals++;
+    const float v[6] = {s.pos[c].x + 0.0f, s.pos[c].y + 0.0f, s.pos[c].z + 0.0f,
+                        s.nrm[c].x + 0.0f, s.nrm[c].y + 0.0f, s.nrm[c].z + 0.0f};
+    memcpy(keys[c].w, v, sizeof(v));
+    uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a over the six words, then a mix of the high bits down
+    for (uint32_t w : keys[c].w) h = (h ^ w) * 0x100000001b3ull;
+    size_t i = (size_t)(h ^ (h >> 29)) & (cap - 1);
+    while (table[i] != kEmpty && memcmp(keys[table[i]].w, keys[c].w, sizeof(Key)) != 0) i = (i + 1) & (cap - 1);
+    if (table[i] == kEmpty) table[i] = (uint32_t)c;
+    first[c] = table[i];
+  }
+  out.corner_vertex.assign(nc, -1);
+  out.vert_off.assign(1, 0);
+  out.num_verts = 0;
+  for (size_t c = 0; c < nc; c++) {  // ids in order of first corner; the run lengths into vert_off[id + 1]
+    if (!(s.flags[c / 3] & FR_SHADE_HAS_NORMALS)) continue;
+    if (first[c] == c) { out.corner_vertex[c] = out.num_verts++; out.vert_off.push_back(0); }
+    else out.corner_vertex[c] = out.corner_vertex[first[c]];
+    out.vert_off[(size_t)out.corner_vertex[c] + 1]++;
+  }
+  for (int v = 0; v < out.num_verts; v++) out.vert_off[(size_t)v + 1] += out.vert_off[v];
+  out.vert_corners.assign(with_normals, 0);
+  std::vector<int32_t> fill(out.vert_off.begin(), out.vert_off.end() - 1);
+  for (size_t c = 0; c < nc; c++)
+    if (out.corner_vertex[c] >= 0) out.vert_corners[(size_t)fill[out.corner_vertex[c]]++] = (int32_t)c;
+}
+
 }  // namespace fr

@@ -44,6 +44,18 @@ struct Bvh {
   int host_nodes = 0;             // node count of a host-built tree whose arrays were released after the upload
 };
 
+// The smooth-vertex weld of a scene (fixed for its life): corners 3 t + k of triangles with
+// FR_SHADE_HAS_NORMALS whose rest positions and rest normals are equal (all six floats by bits after adding
+// +0.0f, so -0 equals +0) are one vertex; vertices are numbered in order of their first corner; corners of
+// triangles without normals have vertex -1. A crease (equal positions, different normals) stays apart.
+struct NormalGroups {
+  std::vector<int32_t> corner_vertex;  // 3 per triangle
+  std::vector<int32_t> vert_off;       // CSR: num_verts + 1 offsets into vert_corners
+  std::vector<int32_t> vert_corners;   // the corners of each vertex, ascending
+  int num_verts = 0;
+};
+void build_normal_groups(const HostScene& s, NormalGroups& out);
+
 enum ScenePreset { PRESET_BOX = 0, PRESET_BUNNY = 1, PRESET_VOKSELIA = 2 };
 
 // Builds a preset. texture_mode 0: load the reference assets from asset_dir (error if missing);

@@ -33,6 +33,8 @@ SCENE_BOX, SCENE_BUNNY, SCENE_VOKSELIA = 0, 1, 2
 # fr_update_positions: what follows the new positions, and where they come from
 FR_BVH_REBUILD, FR_BVH_REFIT = 0, 1
 FR_MEM_HOST, FR_MEM_DEVICE = 0, 1
+# fr_update_geometry: what becomes of the shading normals
+FR_NORMALS_KEEP, FR_NORMALS_GIVEN, FR_NORMALS_RECOMPUTE = 0, 1, 2
 MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 0, 1, 2, 3, 4
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
@@ -175,6 +177,11 @@ _SIGS = {
     "fr_refit_bvh": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_update_positions": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int],
     "fr_bvh_sah_cost": [C.c_void_p, C.POINTER(C.c_float)],
+    "fr_update_geometry": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int],
+    "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
+    "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
+    "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
+    "fr_scene_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
     "fr_get_stats": [C.c_void_p, C.POINTER(fr_stats)],
     "fr_reset_stats": [C.c_void_p],
     "fr_kernel_timing": [C.c_void_p, C.c_int],
@@ -591,22 +598,77 @@ class PathTracer:
                 raise ValueError(f"update must be 'rebuild' or 'refit', not {update!r}") from None
         return int(update)
 
-    def set_positions(self, xyz: np.ndarray, update="rebuild"):
+    @staticmethod
+    def _normals_kind(normals) -> int:
+        """"keep" / "recompute" (or an fr_update_geometry `normals` value, passed through)."""
+        if isinstance(normals, str):
+            try:
+                return {"keep": FR_NORMALS_KEEP, "recompute": FR_NORMALS_RECOMPUTE}[normals]
+            except KeyError:
+                raise ValueError(f"normals must be 'keep', 'recompute' or the normals, not {normals!r}") from None
+        return int(normals)
+
+    def set_positions(self, xyz: np.ndarray, update="rebuild", normals="keep"):
         """New world-space vertex positions (ntris x 3 x 3 float32, scene triangle order), then a GPU
-        rebuild of the BVH (update="rebuild") or a refit of the tree in use (update="refit")."""
+        rebuild of the BVH (update="rebuild") or a refit of the tree in use (update="refit"). The shading
+        normals stay (normals="keep"), are recomputed from the new positions over the scene's smooth vertices
+        (normals="recompute", fr_update_geometry's rule) or are taken from an array shaped like xyz."""
         a = np.ascontiguousarray(xyz, dtype=np.float32)
         n = a.size // 9
-        if update == "rebuild":
-            self._check(_lib.fr_set_positions(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float)), n))
+        if isinstance(normals, str) and normals == "keep":
+            if update == "rebuild":
+                self._check(_lib.fr_set_positions(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float)), n))
+            else:
+                self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(a.ctypes.data), n, FR_MEM_HOST,
+                                                     self._update_kind(update)))
+        elif isinstance(normals, (str, int)):
+            self._check(_lib.fr_update_geometry(self._ctx, C.c_void_p(a.ctypes.data), None, n, FR_MEM_HOST,
+                                                self._update_kind(update), self._normals_kind(normals)))
         else:
-            self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(a.ctypes.data), n, FR_MEM_HOST,
-                                                 self._update_kind(update)))
+            nr = np.ascontiguousarray(normals, dtype=np.float32)
+            if nr.size != a.size:
+                raise ValueError(f"normals hold {nr.size} floats, positions {a.size}")
+            self._check(_lib.fr_update_geometry(self._ctx, C.c_void_p(a.ctypes.data), C.c_void_p(nr.ctypes.data), n,
+                                                FR_MEM_HOST, self._update_kind(update), FR_NORMALS_GIVEN))
 
-    def set_positions_device(self, device_ptr, ntris, update="rebuild"):
+    def set_positions_device(self, device_ptr, ntris, update="rebuild", normals="keep"):
         """As set_positions from device memory (e.g. tensor.data_ptr() of ntris x 9 float32 on this
-        context's device): checked on the device, never copied to the host unless scene_arrays() asks."""
-        self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(device_ptr), int(ntris), FR_MEM_DEVICE,
-                                             self._update_kind(update)))
+        context's device): checked on the device, never copied to the host unless scene_arrays() asks.
+        normals: "keep", "recompute", or a device pointer to ntris x 9 float32 normals."""
+        if isinstance(normals, str):
+            kind, nrm = self._normals_kind(normals), None
+        else:
+            kind, nrm = FR_NORMALS_GIVEN, C.c_void_p(int(normals))
+        if kind == FR_NORMALS_KEEP:
+            self._check(_lib.fr_update_positions(self._ctx, C.c_void_p(device_ptr), int(ntris), FR_MEM_DEVICE,
+                                                 self._update_kind(update)))
+        else:
+            self._check(_lib.fr_update_geometry(self._ctx, C.c_void_p(device_ptr), nrm, int(ntris), FR_MEM_DEVICE,
+                                                self._update_kind(update), kind))
+
+    def set_normals(self, nrm: np.ndarray):
+        """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have
+        normals; positions, tree, texture coordinates and flags stay."""
+        a = np.ascontiguousarray(nrm, dtype=np.float32)
+        self._check(_lib.fr_set_normals(self._ctx, C.c_void_p(a.ctypes.data), a.size // 9, FR_MEM_HOST))
+
+    def set_normals_device(self, device_ptr, ntris):
+        """As set_normals from device memory (ntris x 9 float32 on this context's device)."""
+        self._check(_lib.fr_set_normals(self._ctx, C.c_void_p(device_ptr), int(ntris), FR_MEM_DEVICE))
+
+    def recompute_normals(self) -> float:
+        """Recomputes the shading normals from the current positions (fr_update_geometry's rule); returns
+        the wall time in ms."""
+        return self._launch(_lib.fr_recompute_normals)
+
+    def normal_groups(self):
+        """(corner_vertex, nverts): the smooth vertex of every corner 3 t + k (int32, -1 for triangles without
+        normals) and the number of vertices; fixed for the life of the context."""
+        a = fr_scene_arrays()
+        self._check(_lib.fr_scene_export(self._ctx, C.byref(a)))
+        cv, nv = np.empty(3 * a.num_tris, np.int32), C.c_int()
+        self._check(_lib.fr_normal_groups(self._ctx, cv.ctypes.data_as(C.POINTER(C.c_int32)), cv.size, C.byref(nv)))
+        return cv, nv.value
 
     def bvh_sah_cost(self) -> float:
         """SAH cost of the tree in use (fr_bvh_sah_cost): compare a refitted tree with itself when built."""
@@ -716,6 +778,18 @@ class Scene:
         if rc:
             raise FovrtError(rc, "fr_scene_get_arrays")
         return _arrays_to_dict(a)
+
+    def normal_groups(self):
+        """(corner_vertex, nverts) as PathTracer.normal_groups, on the host."""
+        a = fr_scene_arrays()
+        rc = _lib.fr_scene_get_arrays(self._h, C.byref(a))
+        if rc:
+            raise FovrtError(rc, "fr_scene_get_arrays")
+        cv, nv = np.empty(3 * a.num_tris, np.int32), C.c_int()
+        rc = _lib.fr_scene_normal_groups(self._h, cv.ctypes.data_as(C.POINTER(C.c_int32)), cv.size, C.byref(nv))
+        if rc:
+            raise FovrtError(rc, "fr_scene_normal_groups")
+        return cv, nv.value
 
     def __del__(self):
         if getattr(self, "_h", None) is not None and _lib is not None:

@@ -400,8 +400,8 @@ int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
  *       / area(union of the root's slot boxes)
  * so a caller can compare a refitted tree with the same tree when it was built and rebuild when it has grown.
  * Not covered: an update without host synchronisation (these calls wait for the context's pending work and
- * for their own kernels); groups (each rank's context is updated by its caller); shading normals, which are
- * kept as for fr_set_positions. */
+ * for their own kernels); groups (each rank's context is updated by its caller). Shading normals are kept by
+ * these calls; fr_update_geometry below moves them with the positions. */
 #define FR_BVH_REBUILD 0
 #define FR_BVH_REFIT   1
 #define FR_MEM_HOST    0
@@ -409,6 +409,34 @@ int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
 int fr_refit_bvh(fr_ctx* ctx, float* ms);
 int fr_update_positions(fr_ctx* ctx, const void* xyz, size_t ntris, int where, int how);
 int fr_bvh_sah_cost(fr_ctx* ctx, float* cost);
+/* Shading normals that follow the geometry. The scene is a triangle soup (corner c = 3 t + k of triangle t), so
+ * its smooth vertices are derived once, from the scene as fr_create / fr_scene_create built it: two corners of
+ * triangles that have normals (flags & 0x100) are one vertex when their rest positions and rest normals are
+ * equal (all six floats by bits after adding +0.0f, so -0 equals +0). Vertices are numbered in order of their
+ * first corner; corners of triangles without normals have vertex -1; a crease (equal positions, different
+ * normals: a cube's faces) stays apart. The weld is fixed for the life of the scene: fr_normal_groups /
+ * fr_scene_normal_groups copy it out (corner_vertex: 3 per triangle, or NULL; *nverts: the vertex count).
+ * A recomputed normal has one right answer in bytes. fp32, unfused, no atomics, for a vertex v:
+ *   acc = (0, 0, 0); over the corners c of v in ascending order: acc += cross(p1 - p0, p2 - p0) of triangle c / 3
+ *   d = dot(acc, acc); if FLT_MIN <= d < inf every corner of v takes acc * (1.0f / sqrtf(d));
+ *   otherwise each corner of v takes its own triangle's cross, normalised the same way when its dot is in that
+ *   range; otherwise the corner keeps the normal it has.
+ * fr_update_geometry is fr_update_positions (which is its FR_NORMALS_KEEP case) plus the normals: every check on
+ * both arrays first, then positions, then the tree, then normals. FR_E_INVALID as for fr_update_positions, and
+ * for a bad `normals` value, FR_NORMALS_GIVEN with nrm NULL and a given normal that is not finite on a triangle
+ * that has normals (device arrays are checked on the device); a rejected update or a failed rebuild leaves
+ * positions, tree, scene box and normals as they were. Given normals of triangles without normals are ignored:
+ * neither checked nor written. Texture coordinates, flags and materials never change. fr_set_normals writes
+ * given normals alone (positions and tree untouched); fr_recompute_normals applies the rule to the current
+ * positions, *ms = its wall time. All of them wait for the context's pending work and for their own kernels,
+ * and allocate nothing. fr_scene_export returns the current normals (fetched from the device when asked). */
+#define FR_NORMALS_KEEP      0   /* fr_update_positions' behaviour */
+#define FR_NORMALS_GIVEN     1   /* nrm: 9 floats per triangle, scene order, same memory kind as xyz */
+#define FR_NORMALS_RECOMPUTE 2   /* the rule above, from the new positions */
+int fr_update_geometry(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntris, int where, int how, int normals);
+int fr_set_normals(fr_ctx* ctx, const void* nrm, size_t ntris, int where);
+int fr_recompute_normals(fr_ctx* ctx, float* ms);
+int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* nverts);
 /* Buffer access (PathTracer::get_texture, FR/PathTracer.cpp:337-374; rtBufferMap). */
 int fr_get_buffer(fr_ctx* ctx, int id, fr_buffer_view* view);
 int fr_read_buffer(fr_ctx* ctx, int id, void* host, size_t bytes);
@@ -477,6 +505,7 @@ int fr_scene_export(fr_ctx* ctx, fr_scene_arrays* out);
 typedef struct fr_scene fr_scene;
 int fr_scene_create(const fr_config* cfg, fr_scene** out);
 int fr_scene_get_arrays(fr_scene* scene, fr_scene_arrays* out);
+int fr_scene_normal_groups(fr_scene* scene, int32_t* corner_vertex, size_t ncorners, int* nverts);  /* fr_normal_groups */
 int fr_scene_destroy(fr_scene* scene);
 
 #ifdef __cplusplus

@@ -171,6 +171,27 @@ class PathTracer {
   void update_positions(const void* xyz, size_t ntris, int where, int how) {
     check(fr_update_positions(ctx(), xyz, ntris, where, how), ctx_, "update_positions");
   }
+  // update_positions plus the shading normals (FR_NORMALS_*): kept, given (nrm: 9 floats per triangle, the
+  // memory kind of xyz) or recomputed from the new positions over the scene's smooth vertices
+  void update_geometry(const void* xyz, const void* nrm, size_t ntris, int where, int how, int normals) {
+    check(fr_update_geometry(ctx(), xyz, nrm, ntris, where, how, normals), ctx_, "update_geometry");
+  }
+  void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
+    check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
+  }
+  float recompute_normals() {  // the normal rule over the current positions (fr_recompute_normals), wall ms
+    float ms = 0.0f;
+    check(fr_recompute_normals(ctx(), &ms), ctx_, "recompute_normals");
+    return ms;
+  }
+  // the smooth vertex of every corner 3 t + k (-1: the triangle has no normals); *nverts = their number
+  std::vector<int32_t> normal_groups(int* nverts = nullptr) {
+    fr_scene_arrays a;
+    check(fr_scene_export(ctx(), &a), ctx_, "normal_groups");
+    std::vector<int32_t> corner_vertex(3 * static_cast<size_t>(a.num_tris));
+    check(fr_normal_groups(ctx(), corner_vertex.data(), corner_vertex.size(), nverts), ctx_, "normal_groups");
+    return corner_vertex;
+  }
   float bvh_sah_cost() {  // SAH cost of the tree in use (fr_bvh_sah_cost), lower is better
     float cost = 0.0f;
     check(fr_bvh_sah_cost(ctx(), &cost), ctx_, "bvh_sah_cost");
