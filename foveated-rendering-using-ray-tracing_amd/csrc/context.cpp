@@ -458,6 +458,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   if (const char* v = getenv("FOVRT_TEX_PACKING")) c->tex_packing = atoi(v) != 0;  // A/B knob: 0 = RGBA32F textures
   if (const char* v = getenv("FOVRT_JFA_LAZY_OUTPUTS")) c->lazy_jfa_outputs = atoi(v) != 0;  // A/B knob
   if (const char* v = getenv("FOVRT_EARLY_SETUP")) c->early_setup = atoi(v) != 0;            // A/B knob
+  if (const char* v = getenv("FOVRT_EXTRA_LAZY")) c->extra_lazy = atoi(v) != 0;  // A/B knob: 0 = every sampling writes EXTRA
   if (const char* v = getenv("FOVRT_SIB_STRIP")) c->sib_strip = atoi(v) != 0;      // A/B knob: 0 = k_sibson_wide for the big discs
   {  // FOVRT_SLOTS: frame slots of the pipelined loop (2 or 3; A/B knob)
     const char* v = getenv("FOVRT_SLOTS");
@@ -815,9 +816,22 @@ static int enqueue_sampling(fr_ctx* c, hipStream_t fs) {
   const bool lp_refresh = lp && (c->lp_mode != c->U.mask_mode || c->lp_gaze.x != c->U.gaze.x ||
                                  c->lp_gaze.y != c->U.gaze.y);
   if (lp_refresh) { c->lp_mode = c->U.mask_mode; c->lp_gaze = c->U.gaze; }
+  // EXTRA on demand (extra_owed, materialize_extra_now): the launch stores no heat map and, unless the saliency mask
+  // reads them, evaluates no saliency features; what k_extra needs of it is recorded. A tile-local front and tile
+  // sharding keep the eager form (their G-buffer inputs do not cover the screen).
+  const bool lazy = c->extra_lazy && c->cfg.write_extra && !c->U.front_need && c->U.shard_count <= 1;
   launch_sampling(c->U, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
                   c->img[P_nrm(c)], c->img[P_DIFFUSE], c->img[P_EXTRA], c->mask, c->gclass, c->words, c->counts,
-                  c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh, c->U.shard_count > 1 ? c->bcount : nullptr, fs);
+                  lazy ? 0 : c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh,
+                  c->U.shard_count > 1 ? c->bcount : nullptr, fs);
+  if (c->cfg.write_extra) c->extra_owed = lazy;  // (write_extra = 0: EXTRA is never written, nothing is ever owed)
+  if (lazy) {
+    c->extra_U = c->U;
+    c->extra_sc = c->dsc;
+    c->extra_depth = c->depth_cur;
+    c->extra_nrm = P_nrm(c);
+    c->extra_wgt = P_wgt(c);
+  }
   if (c->U.shard_count > 1) {
     // every rank's active count of this frame (fr_shard_counts, the group's transfer sizes), to pinned
     // host memory with its own event: reading it waits for this frame's front stages only
@@ -919,10 +933,28 @@ static void materialize_jfa_now(fr_ctx* c) {
   materialize_jfa(c, c->stream);
 }
 
+// EXTRA owed by the last sampling (enqueue_sampling), written from an ABI call: on the context stream, after the
+// pending reconstruction and front stages. Called before anything reads EXTRA and before anything outside a frame
+// overwrites what k_extra reads (extra_reads). Inside a frame the next sampling replaces the debt instead: no caller
+// can see EXTRA between a frame's G-buffer and its sampling.
+static void materialize_extra_now(fr_ctx* c) {
+  if (!c->extra_owed) return;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  launch_extra(c->extra_U, c->extra_sc, c->img[c->extra_depth], c->img[c->extra_wgt], c->img[c->extra_nrm],
+               c->img[P_DIFFUSE], c->img[P_EXTRA], c->stream);
+  c->extra_owed = false;
+}
+// does the owed heat map read this physical buffer?
+static bool extra_reads(const fr_ctx* c, int phys) {
+  return c->extra_owed && (phys == P_DIFFUSE || phys == c->extra_depth || phys == c->extra_nrm || phys == c->extra_wgt);
+}
+
 static int resolve(fr_ctx* c, int id, int* phys) {
   // JFA_COORD read by a caller or a pass outside the frame chain, or JFA_COLOR about to be written: JFA_COORD is
   // written first when owed
   if (id == FR_BUF_JFA_COORD || id == FR_BUF_JFA_COLOR) materialize_jfa_now(c);
+  if (id == FR_BUF_EXTRA) materialize_extra_now(c);  // the same for a read of EXTRA
   switch (id) {
     case FR_BUF_POSITION: *phys = P_pos(c); return FR_OK;
     case FR_BUF_NORMAL: *phys = P_nrm(c); return FR_OK;
@@ -1010,7 +1042,11 @@ static int timed(fr_ctx* c, const std::function<int()>& f, float* ms) {
   return FR_OK;
 }
 
-int fr_geometry_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_geometry(c, c->stream); }, ms); }
+int fr_geometry_launch(fr_ctx* c, float* ms) {
+  if (!c) return FR_E_INVALID;
+  materialize_extra_now(c);  // the stage call overwrites DIFFUSE and DEPTH, and the caller may read EXTRA before the next sampling
+  return timed(c, [&] { return enqueue_geometry(c, c->stream); }, ms);
+}
 int fr_sampling_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_sampling(c, c->stream); }, ms); }
 int fr_optimize_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_optimize(c, c->stream); }, ms); }
 int fr_shading_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_shading(c); }, ms); }
@@ -1385,6 +1421,7 @@ int fr_set_shard_plan(fr_ctx* c, int rank, int count, int tile, const uint8_t* o
       if (owner[t] >= count) return fail(c, FR_E_INVALID, "fr_set_shard_plan: owner out of range");
       map[t] = (uint32_t)owner[t] << 24 | next[owner[t]]++;
     }
+  materialize_extra_now(c);  // a sharded context's unpack calls write the images an owed EXTRA reads
   join_recon(c);
   hipSetDevice(c->cfg.device);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1591,8 +1628,16 @@ int fr_gaze_target(fr_ctx* c, float xyz[3]) {
 }
 
 int fr_get_buffer(fr_ctx* c, int id, fr_buffer_view* v) {
-  const bool owed = c && c->jfa_coord_owed && (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD);
+  bool owed = c && c->jfa_coord_owed && (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD);
+  // a view of EXTRA: from now on every sampling writes it (the caller reads through the pointer without a call).
+  // A view of something the owed heat map reads: the caller may write through it, so EXTRA is written first.
+  int p;
+  if (c && c->extra_owed && (id == FR_BUF_EXTRA || (resolve(c, id, &p) == FR_OK && extra_reads(c, p)))) {
+    materialize_extra_now(c);
+    owed = true;
+  }
   const int rc = buffer_view(c, id, v);
+  if (rc == FR_OK && id == FR_BUF_EXTRA) c->extra_lazy = false;
   // a view handed out after its image was written on demand: that write is complete when the call returns (the
   // caller may read through the pointer on any stream)
   if (rc == FR_OK && owed) HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1638,6 +1683,12 @@ int fr_read_buffer(fr_ctx* c, int id, void* host, size_t bytes) {
 
 int fr_write_buffer(fr_ctx* c, int id, const void* host, size_t bytes) {
   fr_buffer_view v;
+  if (c && c->extra_owed) {
+    // a whole EXTRA from the caller replaces the owed heat map; a write of something the heat map reads comes after it
+    int p;
+    if (id == FR_BUF_EXTRA && host && bytes == (size_t)c->W * c->H * sizeof(f4)) c->extra_owed = false;
+    else if (id != FR_BUF_EXTRA && resolve(c, id, &p) == FR_OK && extra_reads(c, p)) materialize_extra_now(c);
+  }
   int rc = buffer_view(c, id, &v);
   if (rc) return rc;
   if (!host || bytes > v.bytes) return fail(c, FR_E_INVALID, "write_buffer: size");
@@ -1743,6 +1794,7 @@ int fr_restore(fr_ctx* c, const void* host, size_t bytes) {
   if (h.width != c->W || h.height != c->H || h.pp_S != c->pp_S || h.spp != c->U.spp || h.scene != c->cfg.scene ||
       h.payload_bytes != need - sizeof(SnapHeader))
     return fail(c, FR_E_INVALID, "restore: snapshot of another configuration (size, spp or scene differ)");
+  materialize_extra_now(c);  // the depth pair is overwritten below: an owed EXTRA is written from the old one first
   join_recon(c);
   hipSetDevice(c->cfg.device);
   const char* in = static_cast<const char*>(host);

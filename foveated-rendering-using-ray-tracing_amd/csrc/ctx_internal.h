@@ -29,6 +29,7 @@ void launch_carry_history(const FrameUniforms&, const uint8_t*, const f4*, const
 void launch_sampling(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, f4*, const f4*,
                      const f4*, f4*, uint8_t*, const uint8_t*, unsigned long long*, uint32_t*, int, uint8_t*, uint32_t*,
                      bool, uint32_t*, hipStream_t);
+void launch_extra(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, const f4*, f4*, hipStream_t);
 size_t logpolar_inv_words(int W, int H);
 void launch_owner_counts(const FrameUniforms&, const uint32_t*, uint32_t*, hipStream_t);
 void launch_mask_words(const uint8_t*, const uint8_t*, int, int, unsigned long long*, uint32_t*, hipStream_t);
@@ -258,6 +259,16 @@ struct fr_ctx {
   // materialize_jfa writes it (k_jfa_coord, from jfa_final and JFA_COLOR) before anything reads it or writes JFA_COLOR.
   bool jfa_coord_owed = false;
   bool lazy_jfa_outputs = true;  // FOVRT_JFA_LAZY_OUTPUTS=0: every JumpFlooding writes JFA_COORD
+  // k_sampling leaves the EXTRA heat map unwritten (nothing in a frame reads it): while extra_owed, materialize_extra_now
+  // writes it (k_extra) from what the owing launch saw, before anything reads EXTRA or overwrites one of those inputs
+  // outside a frame: the launch's uniforms and scene (gaze, screen, bbox: copies, so later setters do not reach them),
+  // DIFFUSE, and the physical buffers that were its DEPTH (the ping-pong swaps in enqueue_shading), NORMAL and WEIGHT
+  // (its slot's; the sampling leaves WEIGHT.xy as they were). The next sampling replaces the debt.
+  bool extra_owed = false;
+  bool extra_lazy = true;  // FOVRT_EXTRA_LAZY=0: every sampling writes EXTRA; also after fr_get_buffer(EXTRA) gave a view
+  FrameUniforms extra_U;
+  DevScene extra_sc;
+  int extra_depth = P_DEPTH_A, extra_nrm = P_NORMAL, extra_wgt = P_WEIGHT;
   int pp_S = 0;
   DevStats* stats = nullptr;
   FrameUniforms U;

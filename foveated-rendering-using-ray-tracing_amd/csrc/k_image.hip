@@ -99,43 +99,18 @@ FR_DEV void publish_ballots(bool on, int cls, unsigned long long* __restrict__ w
   if (threadIdx.x < 4) counts[threadIdx.x * nb + b] = cnt[threadIdx.x];
 }
 
-template <bool LOCAL>  // LOCAL: a tile-local front (fr_set_front_local); the whole-screen instance carries none of it
-__global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, const f4* __restrict__ position,
-                                                  const f4* __restrict__ depth, const f4* __restrict__ depth_cache,
-                                                  f4* __restrict__ weight, const f4* __restrict__ normal,
-                                                  const f4* __restrict__ diffuse, f4* __restrict__ extra,
-                                                  uint8_t* __restrict__ mask, const uint8_t* __restrict__ gclass,
-                                                  unsigned long long* __restrict__ words, uint32_t* __restrict__ counts,
-                                                  int write_extra, const uint8_t* __restrict__ lp_cache,
-                                                  uint32_t* __restrict__ bcount) {
+// The saliency features are functions of the 4x4 cell origin (samplingStep.cu:186-219): the 16
+// cells of a 16x16 block are evaluated once each and shared via LDS (the same expressions as
+// per pixel, so every pixel sees the same values). The 4 x 16 Sobel sums (diffuse gx, gy, normal
+// gx, gy; gradient(), shared_helper_funcs.h) are one per lane of wave 0, with all nine taps of a lane requested at once; wave 1
+// evaluates the per-cell rest. (One lane evaluating a whole cell serialised 36 tap loads.)
+// Called by all 256 threads of the block (two barriers); cellf / cellg are the block's LDS.
+FR_DEV void saliency_cells(const FrameUniforms& U, const DevScene& sc, const f4* __restrict__ diffuse,
+                           const f4* __restrict__ normal, const f4* __restrict__ depth, float (&cellf)[16][8],
+                           float (&cellg)[4][16]) {
   const int W = U.width, H = U.height;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int x = blockIdx.x * 16 + (lane & 15);
-  const int y = blockIdx.y * 16 + wv * 4 + (lane >> 4);
   const f2 screenf = U.screen;
-  if (LOCAL && !shard_owns(U, blockIdx.x * 16, blockIdx.y * 16)) {
-    // tile-local front: another rank's block (its G-buffer may not exist here) is inactive; its ballot
-    // words, class counts, unfolded count and mask bytes are zero
-    const size_t nb = (size_t)gridDim.x * gridDim.y, b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (threadIdx.x < 16) words[b * 16 + threadIdx.x] = 0ull;
-    else if (threadIdx.x < 20) counts[(threadIdx.x - 16) * nb + b] = 0u;
-    else if (threadIdx.x == 20 && bcount) bcount[b] = 0u;
-    if (x < W && y < H) mask[(size_t)y * W + x] = 0;
-    return;
-  }
-  // The saliency features are functions of the 4x4 cell origin (samplingStep.cu:186-219): the 16
-  // cells of this 16x16 block are evaluated once each and shared via LDS (the same expressions as
-  // per pixel, so every pixel sees the same values). The 4 x 16 Sobel sums (diffuse gx, gy, normal
-  // gx, gy; gradient(), shared_helper_funcs.h) are one per lane of wave 0, with all nine taps of a lane requested at once; wave 1
-  // evaluates the per-cell rest. (One lane evaluating a whole cell serialised 36 tap loads.)
-  // Only the saliency mask and the `extra` output read the features: with a log-polar, uniform or
-  // full mask (the bench's mode) the cell phase, its two barriers and its 36 B of tap loads per
-  // pixel are skipped (block-uniform branch).
-  const bool saliency_used = U.mask_mode == MASK_SALIENCY || write_extra;
-  __shared__ float cellf[16][8];
-  __shared__ float cellg[4][16];
-  if (!saliency_used) {
-  } else if (threadIdx.x < 64) {
+  if (threadIdx.x < 64) {
     const int cell = threadIdx.x & 15, g = threadIdx.x >> 4;
     const uint32_t sx = blockIdx.x * 16 + 4 * (cell & 3), sy = blockIdx.y * 16 + 4 * (cell >> 2);
     if ((int)sx < W && (int)sy < H) {
@@ -182,16 +157,70 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
       f[5] = normal[(size_t)sy * W + sx].w;                                                // s_shadow
     }
   }
-  if (saliency_used) {
-    __syncthreads();
-    if (threadIdx.x < 16) {
-      const float gx = cellg[0][threadIdx.x], gy = cellg[1][threadIdx.x];
-      const float ngx = cellg[2][threadIdx.x], ngy = cellg[3][threadIdx.x];
-      cellf[threadIdx.x][3] = cuda_atanf(gy / gx);  // s_orientation: CUDA's atanf (samplingStep.ptx:748-784)
-      cellf[threadIdx.x][6] = len2c(ngx, ngy);      // s_normal_grad (:1117-1119)
-    }
-    __syncthreads();
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const float gx = cellg[0][threadIdx.x], gy = cellg[1][threadIdx.x];
+    const float ngx = cellg[2][threadIdx.x], ngy = cellg[3][threadIdx.x];
+    cellf[threadIdx.x][3] = cuda_atanf(gy / gx);  // s_orientation: CUDA's atanf (samplingStep.ptx:748-784)
+    cellf[threadIdx.x][6] = len2c(ngx, ngy);      // s_normal_grad (:1117-1119)
   }
+  __syncthreads();
+}
+
+// A pixel's saliency from its cell's features and its reprojected position (WEIGHT.xy).
+FR_DEV float pixel_saliency(const float (&cellf)[16][8], int x, int y, f2 query_uv) {
+  const float* f = cellf[((y & 15) >> 2) * 4 + ((x & 15) >> 2)];
+  const f3 rgbyl = mk3(f[0], f[1], f[2]);
+  const float s_orientation = f[3], s_depth = f[4], s_shadow = f[5], s_normal_grad = f[6];
+  float velocity = len2c((float)x - query_uv.x, (float)y - query_uv.y) * 0.5f;  // samplingStep.ptx:1120-1128
+  if (query_uv.x < 0.0f && query_uv.y < 0.0f) velocity = 0.0f;
+  const float m = -0.4f, Am = 20.0f;
+  float va = (velocity / Am) * (velocity / Am);
+  float s_velocity = __builtin_fmaf(fr_exp(-va / (m * m)), 1.0f / (m * sqrtf(2.0f * kPi)), 1.0f);  // :1147
+  float saliency = (__builtin_fmaf(rgbyl.x + rgbyl.y, 0.5f, rgbyl.z) + s_orientation) / 3.0f;      // :1150-1153
+  saliency = fmaxf(saliency, s_normal_grad);
+  saliency *= s_depth;
+  saliency = fmaxf(saliency, s_velocity) * s_shadow;
+  return saliency;
+}
+
+// The `extra` heat map of a saliency, with CUDA's cosf / sinf (samplingStep.ptx:1288-1600).
+FR_DEV f4 heat_map(float saliency) {
+  return mk4(cuda_cosf(saliency * kPi_2 - kPi_2), cuda_sinf(saliency * kPi) * 1.5f, cuda_cosf(saliency * kPi_2), 1.0f);
+}
+
+template <bool LOCAL>  // LOCAL: a tile-local front (fr_set_front_local); the whole-screen instance carries none of it
+__global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, const f4* __restrict__ position,
+                                                  const f4* __restrict__ depth, const f4* __restrict__ depth_cache,
+                                                  f4* __restrict__ weight, const f4* __restrict__ normal,
+                                                  const f4* __restrict__ diffuse, f4* __restrict__ extra,
+                                                  uint8_t* __restrict__ mask, const uint8_t* __restrict__ gclass,
+                                                  unsigned long long* __restrict__ words, uint32_t* __restrict__ counts,
+                                                  int write_extra, const uint8_t* __restrict__ lp_cache,
+                                                  uint32_t* __restrict__ bcount) {
+  const int W = U.width, H = U.height;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int x = blockIdx.x * 16 + (lane & 15);
+  const int y = blockIdx.y * 16 + wv * 4 + (lane >> 4);
+  const f2 screenf = U.screen;
+  if (LOCAL && !shard_owns(U, blockIdx.x * 16, blockIdx.y * 16)) {
+    // tile-local front: another rank's block (its G-buffer may not exist here) is inactive; its ballot
+    // words, class counts, unfolded count and mask bytes are zero
+    const size_t nb = (size_t)gridDim.x * gridDim.y, b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (threadIdx.x < 16) words[b * 16 + threadIdx.x] = 0ull;
+    else if (threadIdx.x < 20) counts[(threadIdx.x - 16) * nb + b] = 0u;
+    else if (threadIdx.x == 20 && bcount) bcount[b] = 0u;
+    if (x < W && y < H) mask[(size_t)y * W + x] = 0;
+    return;
+  }
+  // Only the saliency mask and an `extra` stored here read the saliency features. write_extra is 0 when the
+  // context leaves the heat map to k_extra (written when something reads EXTRA) or never writes it: with a
+  // log-polar, uniform or full mask the cell phase, its two barriers and its 36 B of tap loads per pixel are
+  // then skipped (block-uniform branch).
+  const bool saliency_used = U.mask_mode == MASK_SALIENCY || write_extra;
+  __shared__ float cellf[16][8];
+  __shared__ float cellg[4][16];
+  if (saliency_used) saliency_cells(U, sc, diffuse, normal, depth, cellf, cellg);
   bool usingRay = false, unfolded = false;
   int cls = 3;
   if (x < W && y < H) {
@@ -209,21 +238,7 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
         isValid = fabsf(diff) < sc.scene_epsilon ? 1.0f : 0.0f;
       }
     }
-    float saliency = 0.0f;
-    if (saliency_used) {
-      const float* f = cellf[((y & 15) >> 2) * 4 + ((x & 15) >> 2)];
-      const f3 rgbyl = mk3(f[0], f[1], f[2]);
-      const float s_orientation = f[3], s_depth = f[4], s_shadow = f[5], s_normal_grad = f[6];
-      float velocity = len2c((float)x - query_uv.x, (float)y - query_uv.y) * 0.5f;  // samplingStep.ptx:1120-1128
-      if (query_uv.x < 0.0f && query_uv.y < 0.0f) velocity = 0.0f;
-      const float m = -0.4f, Am = 20.0f;
-      float va = (velocity / Am) * (velocity / Am);
-      float s_velocity = __builtin_fmaf(fr_exp(-va / (m * m)), 1.0f / (m * sqrtf(2.0f * kPi)), 1.0f);  // :1147
-      saliency = (__builtin_fmaf(rgbyl.x + rgbyl.y, 0.5f, rgbyl.z) + s_orientation) / 3.0f;          // :1150-1153
-      saliency = fmaxf(saliency, s_normal_grad);
-      saliency *= s_depth;
-      saliency = fmaxf(saliency, s_velocity) * s_shadow;
-    }
+    const float saliency = saliency_used ? pixel_saliency(cellf, x, y, query_uv) : 0.0f;
 
     switch (U.mask_mode) {
       case MASK_SALIENCY:
@@ -238,9 +253,7 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
     if (bcount) unfolded = usingRay;
     usingRay = usingRay && shard_owns(U, x, y);  // tile sharding: this rank traces its own tiles only
     weight[p] = mk4(query_uv.x, query_uv.y, isValid, 0.0f);
-    if (write_extra)
-      extra[p] = mk4(cuda_cosf(saliency * kPi_2 - kPi_2), cuda_sinf(saliency * kPi) * 1.5f, cuda_cosf(saliency * kPi_2),
-                     1.0f);  // heatmap with CUDA's cosf / sinf (samplingStep.ptx:1288-1600)
+    if (write_extra) extra[p] = heat_map(saliency);
     mask[p] = usingRay ? 1 : 0;
   }
   publish_ballots(usingRay, cls, words, counts);
@@ -255,6 +268,31 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
     __syncthreads();
     if (threadIdx.x == 0) bcount[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = nb;
   }
+}
+
+// The heat map a k_sampling launch left unwritten (context.cpp, materialize_extra_now): the same cell phase and
+// per-pixel expressions over that launch's inputs (its uniforms, DIFFUSE, NORMAL, DEPTH and WEIGHT.xy, which
+// the sampling does not change), so EXTRA is what that launch would have stored, bit for bit.
+__global__ __launch_bounds__(256) void k_extra(FrameUniforms U, DevScene sc, const f4* __restrict__ depth,
+                                               const f4* __restrict__ weight, const f4* __restrict__ normal,
+                                               const f4* __restrict__ diffuse, f4* __restrict__ extra) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int x = blockIdx.x * 16 + (lane & 15);
+  const int y = blockIdx.y * 16 + wv * 4 + (lane >> 4);
+  __shared__ float cellf[16][8];
+  __shared__ float cellg[4][16];
+  saliency_cells(U, sc, diffuse, normal, depth, cellf, cellg);
+  if (x < U.width && y < U.height) {
+    const size_t p = (size_t)y * U.width + x;
+    const f4 wgt = weight[p];
+    extra[p] = heat_map(pixel_saliency(cellf, x, y, mk2(wgt.x, wgt.y)));
+  }
+}
+
+void launch_extra(const FrameUniforms& U, const DevScene& sc, const f4* depth, const f4* weight, const f4* normal,
+                  const f4* diffuse, f4* extra, hipStream_t stream) {
+  dim3 grid((U.width + 15) / 16, (U.height + 15) / 16);
+  hipLaunchKernelGGL(k_extra, grid, dim3(256), 0, stream, U, sc, depth, weight, normal, diffuse, extra);
 }
 
 // Per-owner sums of the unfolded block counts (one block; owners < FR_MAX_SHARD_RANKS).

@@ -11,9 +11,9 @@
 //   envmap_miss               FR/cuda/gradientbg.cu:57-66
 //   mesh_intersect_refine     FR/cuda/triangle_mesh.cu:57-105 (+ intersection_refinement.h)
 //
-// MI355X design: no RT cores, so traversal is a wave64 software loop over a 2-wide BVH whose nodes
-// carry both child boxes (one 64-B line per visit) with a per-lane stack in LDS; triangles are
-// pre-differenced (three 16-B loads). OptiX's recursive rtTrace is replaced by an explicit,
+// MI355X design: no RT cores, so traversal is a wave64 software loop over a 4-wide BVH whose 128-B nodes
+// carry the boxes of all four children (eight 16-B loads, two 64-B lines per visit) with a per-lane stack
+// in LDS; triangles are pre-differenced (three 16-B loads). OptiX's recursive rtTrace is replaced by an explicit,
 // output-equivalent work list: children whose results the parent never reads are not traced
 // (diffuse/mirror parents read only child.reflectance, so grand-children and
 // refraction sub-trees below them are dead work in the reference). Closest-hit ties resolve to the
@@ -1241,7 +1241,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
   };
   const uint32_t lane = threadIdx.x & 63;
   const float tmin = sc.scene_epsilon;
-  const bool exit_early = SHADE_EXIT_T > 0 && (SHADE_EXIT_REFR == 0 || (!fx && nrefr * SHADE_EXIT_REFR >= total));
+  const bool exit_early = SHADE_EXIT_T > 0 && (SHADE_EXIT_REFR == 0 || (!fx && (uint64_t)nrefr * SHADE_EXIT_REFR >= total));
   // wave-uniform queue state
   uint32_t shard = blockIdx.x & (SHADE_SHARDS - 1);
   uint32_t shards_left = SHADE_SHARDS;
