@@ -377,6 +377,33 @@ static int pack_texture(const HostTexture& t, std::vector<uint32_t>& out) {
   return FR_TEX_RGBE;
 }
 
+// The FOVRT_* environment knobs of a context, read once per fr_create; the kernels' launchers take them as arguments.
+// (Read where they act instead: the host BVH builder's in scene.cpp, FOVRT_BVH_PHASES in k_bvh.hip, FOVRT_DIAG_DUMP
+// in fr_diag_trace_queries, and once per process FOVRT_LAT_OVERLAP in frame_half and FOVRT_GROUP_VRING in group.cpp.)
+static void read_env_knobs(fr_ctx* c) {
+  if (const char* v = getenv("FOVRT_SHADE_CHUNK_REFR")) c->chunk_refr = (uint32_t)std::max(0, atoi(v));
+  if (const char* v = getenv("FOVRT_SHADE_XCD_BANDS")) c->xcd_bands = atoi(v) != 0;
+  if (const char* v = getenv("FOVRT_SHADE_HANDOFF")) c->handoff = (uint32_t)std::min(std::max(atoi(v), 0), 2);
+  if (const char* v = getenv("FOVRT_TEX_PACKING")) c->tex_packing = atoi(v) != 0;  // A/B knob: 0 = RGBA32F textures
+  if (const char* v = getenv("FOVRT_JFA_LAZY_OUTPUTS")) c->lazy_jfa_outputs = atoi(v) != 0;  // A/B knob
+  if (const char* v = getenv("FOVRT_EARLY_SETUP")) c->early_setup = atoi(v) != 0;            // A/B knob
+  if (const char* v = getenv("FOVRT_EXTRA_LAZY")) c->extra_lazy = atoi(v) != 0;  // A/B knob: 0 = every sampling writes EXTRA
+  if (const char* v = getenv("FOVRT_SIB_STRIP")) c->sib_strip = atoi(v) != 0;      // A/B knob: 0 = k_sibson_wide for the big discs
+  {  // FOVRT_SLOTS: frame slots of the pipelined loop (2 or 3; A/B knob)
+    const char* v = getenv("FOVRT_SLOTS");
+    if (v) c->nslots = std::max(2, std::min(fr_ctx::MAX_SLOTS, atoi(v)));
+  }
+  {  // FOVRT_SHADE_BLOCKS_PER_CU: tuning knob (fewer leaves room for concurrent kernels)
+    const char* v = getenv("FOVRT_SHADE_BLOCKS_PER_CU");
+    const int full = fr::shade_max_blocks_per_cu();
+    c->shade_blocks_per_cu = v ? std::max(1, std::min(full, atoi(v))) : full;
+  }
+  if (const char* v = getenv("FOVRT_JFA_XCD")) c->jfa_xcd = atoi(v);
+  if (const char* v = getenv("FOVRT_SIB_STRIP_MID")) c->sib_strip_mid = atoi(v);
+  if (const char* v = getenv("FOVRT_ATROUS_ROWS2")) c->atrous_rows2 = atoi(v) != 0;
+  if (const char* v = getenv("FOVRT_ATROUS_XCD")) c->atrous_xcd = atoi(v) != 0;
+}
+
 int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   if (!out) return fail(nullptr, FR_E_INVALID, "out is NULL");
   *out = nullptr;
@@ -404,46 +431,11 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   c->W = cfg.width; c->H = cfg.height;
   auto bail = [&](int code) { g_create_error = c->err; fr_destroy(c); return code; };
   if (hipSetDevice(cfg.device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(FR_E_HIP); }
-  // Stream priorities (FOVRT_STREAM_PRIORITY, A/B knob): 0 (default) all streams at the default
-  // priority; 1 trace half (context stream, carry, front stages) high, reconstruction low; 2 the
-  // reconstruction high, the trace half low; 3 only the front stages high; 4 JumpFlooding -> Sibson high,
-  // pull-push -> A-Trous and the front stages low.
-  static const int prio_mode = [] {
-    const char* v = getenv("FOVRT_STREAM_PRIORITY");
-    return v ? atoi(v) : 0;
-  }();
-  int lo = 0, hi = 0;
-  if (prio_mode) hipDeviceGetStreamPriorityRange(&lo, &hi);
-  const int p_trace = prio_mode == 1 ? hi : prio_mode == 2 ? lo : 0;
-  const int p_recon = prio_mode == 1 ? lo : prio_mode == 2 ? hi : 0;
-  const int p_front = prio_mode == 1 || prio_mode == 3 ? hi : prio_mode == 2 || prio_mode == 4 ? lo : 0;
-  const int p_jfa = prio_mode == 4 ? hi : p_recon, p_pp = prio_mode == 4 ? lo : p_recon;
-  // CU masks (FOVRT_RECON_CUS = R, A/B knob, 0 = off): the two reconstruction streams run on R CUs spread evenly
-  // over the device's CU mask (every XCD); FOVRT_CU_DISJOINT=1 also keeps the trace streams off those CUs.
-  static const int recon_cus = [] { const char* v = getenv("FOVRT_RECON_CUS"); return v ? atoi(v) : 0; }();
-  static const int cu_disjoint = [] { const char* v = getenv("FOVRT_CU_DISJOINT"); return v ? atoi(v) : 0; }();
-  int ncu = 0;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg.device);
-  const bool masked = recon_cus > 0 && recon_cus < ncu;
-  std::vector<uint32_t> m_recon((size_t)(ncu + 31) / 32, 0u), m_trace((size_t)(ncu + 31) / 32, 0u);
-  if (masked) {
-    for (int i = 0; i < recon_cus; i++) {
-      const int b = (int)((int64_t)i * ncu / recon_cus);
-      m_recon[(size_t)b / 32] |= 1u << (b % 32);
+  for (hipStream_t* st : {&c->stream, &c->stream2, &c->stream3, &c->stream4, &c->stream5}) {
+    if (hipStreamCreateWithPriority(st, hipStreamNonBlocking, 0) != hipSuccess) {
+      c->err = "stream create failed";
+      return bail(FR_E_HIP);
     }
-    for (int b = 0; b < ncu; b++)
-      if (!cu_disjoint || !(m_recon[(size_t)b / 32] & (1u << (b % 32)))) m_trace[(size_t)b / 32] |= 1u << (b % 32);
-  }
-  auto mk = [&](hipStream_t* st, int prio, bool recon) {
-    if (!masked) return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio);
-    std::vector<uint32_t>& m = recon ? m_recon : m_trace;
-    return hipExtStreamCreateWithCUMask(st, (uint32_t)m.size(), m.data());
-  };
-  if (mk(&c->stream, p_trace, false) != hipSuccess || mk(&c->stream2, p_pp, true) != hipSuccess ||
-      mk(&c->stream3, p_jfa, true) != hipSuccess || mk(&c->stream4, p_trace, false) != hipSuccess ||
-      mk(&c->stream5, p_front, false) != hipSuccess) {
-    c->err = "stream create failed";
-    return bail(FR_E_HIP);
   }
   for (auto& e : c->ev) hipEventCreate(&e);
   hipEventCreateWithFlags(&c->ev_front, hipEventDisableTiming);
@@ -452,18 +444,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   for (auto& e : c->ev_jfa) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& row : c->lat_ev) for (auto& e : row) hipEventCreate(&e);
   for (auto& e : c->ev_counts) hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  if (const char* v = getenv("FOVRT_SHADE_CHUNK_REFR")) c->chunk_refr = (uint32_t)std::max(0, atoi(v));
-  if (const char* v = getenv("FOVRT_SHADE_XCD_BANDS")) c->xcd_bands = atoi(v) != 0;
-  if (const char* v = getenv("FOVRT_SHADE_HANDOFF")) c->handoff = (uint32_t)std::min(std::max(atoi(v), 0), 2);
-  if (const char* v = getenv("FOVRT_TEX_PACKING")) c->tex_packing = atoi(v) != 0;  // A/B knob: 0 = RGBA32F textures
-  if (const char* v = getenv("FOVRT_JFA_LAZY_OUTPUTS")) c->lazy_jfa_outputs = atoi(v) != 0;  // A/B knob
-  if (const char* v = getenv("FOVRT_EARLY_SETUP")) c->early_setup = atoi(v) != 0;            // A/B knob
-  if (const char* v = getenv("FOVRT_EXTRA_LAZY")) c->extra_lazy = atoi(v) != 0;  // A/B knob: 0 = every sampling writes EXTRA
-  if (const char* v = getenv("FOVRT_SIB_STRIP")) c->sib_strip = atoi(v) != 0;      // A/B knob: 0 = k_sibson_wide for the big discs
-  {  // FOVRT_SLOTS: frame slots of the pipelined loop (2 or 3; A/B knob)
-    const char* v = getenv("FOVRT_SLOTS");
-    if (v) c->nslots = std::max(2, std::min(fr_ctx::MAX_SLOTS, atoi(v)));
-  }
+  read_env_knobs(c);
 
   std::string err;
   if (!build_preset_scene(cfg.scene, c->asset_dir, cfg.texture_mode, cfg.light_power, cfg.detail, c->scene, err,
@@ -619,12 +600,12 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
       dalloc(&c->tiles, 1024) != hipSuccess || dalloc(&c->jfa_a, N) != hipSuccess || dalloc(&c->jfa_b, N) != hipSuccess ||
       dalloc(&c->pull, atlas) != hipSuccess || dalloc(&c->push, atlas) != hipSuccess ||
       dalloc(&c->snap, pp_snap_count(c->pp_S)) != hipSuccess || dalloc(&c->stats, 1) != hipSuccess ||
-      dalloc(&c->shade_ctr, shade_counter_words()) != hipSuccess || dalloc(&c->samples, std::max(N * cfg.spp, 2 * shade_fx_slots((uint32_t)N, cfg.spp, c->handoff))) != hipSuccess ||
-      dalloc(&c->sample_help, std::max<size_t>(4 * shade_fx_slots((uint32_t)N, cfg.spp, c->handoff), 1)) != hipSuccess ||
+      dalloc(&c->shade_ctr, shade_counter_words()) != hipSuccess || dalloc(&c->samples, std::max(N * cfg.spp, 2 * shade_fx_slots((uint32_t)N, cfg.spp, c->handoff, c->shade_blocks_per_cu))) != hipSuccess ||
+      dalloc(&c->sample_help, std::max<size_t>(4 * shade_fx_slots((uint32_t)N, cfg.spp, c->handoff, c->shade_blocks_per_cu), 1)) != hipSuccess ||
       dalloc(&c->aux_p[0], N) != hipSuccess || dalloc(&c->aux_seed_p[0], N) != hipSuccess ||
       dalloc(&c->aux_p[1], N) != hipSuccess || dalloc(&c->aux_seed_p[1], N) != hipSuccess ||
       dalloc(&c->hvalid, N / 64 + 1) != hipSuccess ||
-      hipMalloc((void**)&c->item_store, shade_item_store_f4() * sizeof(f4)) != hipSuccess ||
+      hipMalloc((void**)&c->item_store, shade_item_store_f4(c->shade_blocks_per_cu) * sizeof(f4)) != hipSuccess ||
       (cfg.sibson_mode == 0 && (dalloc(&c->sib_prefix, (size_t)(c->W + 1) * c->H) != hipSuccess ||
                                 dalloc(&c->sib_blocks, (size_t)sibson_prefix_blocks(c->W) * c->H) != hipSuccess ||
                                 hipMalloc((void**)&c->sib_wide, ((size_t)c->W * c->H + 2) * sizeof(uint32_t)) != hipSuccess ||
@@ -898,13 +879,13 @@ static int enqueue_shading(fr_ctx* c) {
   if (kt) hipEventRecord(kt[1], c->stream);
   launch_shade_paths(c->dsc, c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache],
                      c->shade_ctr, c->samples, c->sample_help, c->stats, c->aux, c->aux_seed, c->chunk_refr,
-                     c->xcd_bands, c->handoff, c->item_store, c->stream);
+                     c->xcd_bands, c->handoff, c->shade_blocks_per_cu, c->item_store, c->stream);
   if (c->time_kernels) hipEventRecord(c->ev[10], c->stream);
   if (kt) hipEventRecord(kt[2], c->stream);
   hipStreamWaitEvent(c->stream, c->ev[12], 0);
   launch_shade_resolve(c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache], c->samples,
                        c->sample_help, c->img[c->hist_cur], c->img[P_shd(c)], c->shade_ctr, c->handoff,
-                       c->U.shard_count > 1 ? c->shade_radiance : nullptr, c->stream);
+                       c->shade_blocks_per_cu, c->U.shard_count > 1 ? c->shade_radiance : nullptr, c->stream);
   if (kt) hipEventRecord(kt[3], c->stream);
   // this slot's WEIGHT / mask / active list are free for the front stages of frame + nslots after this
   hipEventRecord(c->ev_trace[c->slot], c->stream);
@@ -987,7 +968,7 @@ static int enqueue_jfa(fr_ctx* c, int in_buffer, hipStream_t stream = nullptr) {
   const bool lazy = run_form && c->lazy_jfa_outputs;
   c->jfa_final = launch_jfa(c->img[p], c->jfa_a, c->jfa_b, c->img[P_JFA_COORD], c->img[P_JFA_COLOR], c->ftab, c->W,
                             c->H, run_form ? c->sib_prefix : nullptr, run_form ? c->sib_blocks : nullptr, !lazy,
-                            stream ? stream : c->stream);
+                            c->jfa_xcd, stream ? stream : c->stream);
   c->jfa_coord_owed = lazy;
   c->sib_prefix_fresh = run_form;
   return check_launch(c);
@@ -998,7 +979,8 @@ static int enqueue_sibson(fr_ctx* c, hipStream_t stream = nullptr) {
     launch_sibson(c->img[P_JFA_COORD], c->img[P_JFA_COLOR], c->img[P_SIBSON], c->W, c->H, stream ? stream : c->stream);
   } else {  // run form (default): exact tap sets, rounding-level differences
     launch_sibson_runs(c->img[P_JFA_COORD], c->jfa_final, c->img[P_JFA_COLOR], c->sib_prefix, c->sib_blocks, c->sib_rowp, c->sib_wide,
-                       c->sib_strips, c->img[P_SIBSON], c->W, c->H, c->sib_prefix_fresh, c->sib_strip, c->jfa_coord_owed,
+                       c->sib_strips, c->img[P_SIBSON], c->W, c->H, c->sib_prefix_fresh, c->sib_strip, c->sib_strip_mid,
+                       c->jfa_coord_owed,
                        stream ? stream : c->stream);
   }
   return check_launch(c);
@@ -1017,12 +999,12 @@ static int enqueue_atrous(fr_ctx* c, int count, int pos, int nrm, int col, hipSt
   if (pc == P_ATROUS_A || pc == P_ATROUS_B) return fail(c, FR_E_INVALID, "atrous: colour input aliases the output");
   float c_phi = 1.f, n_phi = 1.f, p_phi = 1.f;
   int sw = 1;
-  launch_atrous(c->img[pp], c->img[pn], c->img[pc], c->img[P_ATROUS_A], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, stream);
+  launch_atrous(c->img[pp], c->img[pn], c->img[pc], c->img[P_ATROUS_A], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, c->atrous_rows2, c->atrous_xcd, stream);
   bool usingA = true;
   for (int k = 1; k < count; k++) {  // FR/ATrous.cpp:90-113
     c_phi *= 1.0f; n_phi *= 0.5f; p_phi *= 1.0f; sw *= 2;
-    if (usingA) launch_atrous(c->img[pp], c->img[pn], c->img[P_ATROUS_A], c->img[P_ATROUS_B], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, stream);
-    else launch_atrous(c->img[pp], c->img[pn], c->img[P_ATROUS_B], c->img[P_ATROUS_A], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, stream);
+    if (usingA) launch_atrous(c->img[pp], c->img[pn], c->img[P_ATROUS_A], c->img[P_ATROUS_B], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, c->atrous_rows2, c->atrous_xcd, stream);
+    else launch_atrous(c->img[pp], c->img[pn], c->img[P_ATROUS_B], c->img[P_ATROUS_A], c->W, c->H, c_phi, n_phi, p_phi, (float)sw, c->atrous_rows2, c->atrous_xcd, stream);
     usingA = !usingA;
   }
   c->atrous_out = usingA ? P_ATROUS_A : P_ATROUS_B;
@@ -1330,10 +1312,10 @@ int fr_set_sample_sum(fr_ctx* c, int mode) {
   HIP_TRY(c, hipDeviceSynchronize());
   // the fixed-point form keeps 32-B sample records and a 32-B help record per sample
   const size_t N = (size_t)c->W * c->H;
-  const size_t need_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode));
-  const size_t need_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode), 1);
-  const size_t have_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff));
-  const size_t have_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff), 1);
+  const size_t need_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode, c->shade_blocks_per_cu));
+  const size_t need_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode, c->shade_blocks_per_cu), 1);
+  const size_t have_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff, c->shade_blocks_per_cu));
+  const size_t have_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff, c->shade_blocks_per_cu), 1);
   if (need_s > have_s) {
     hipFree(c->samples); c->samples = nullptr;
     if (dalloc(&c->samples, need_s) != hipSuccess) return fail(c, FR_E_NOMEM, "fr_set_sample_sum: allocation failed");

@@ -16,14 +16,15 @@ namespace fr {
 void launch_gbuffer(const DevScene&, const FrameUniforms&, f4*, f4*, f4*, f4*, f4*, uint8_t*, DevStats*, hipStream_t);
 void launch_shade_paths(const DevScene&, const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*,
                         const f4*, uint32_t*, f4*, unsigned long long*, DevStats*, f4*, uint32_t*, uint32_t, uint32_t,
-                        uint32_t, f4*, hipStream_t);
-size_t shade_item_store_f4();
+                        uint32_t, int, f4*, hipStream_t);
+int shade_max_blocks_per_cu();
+size_t shade_item_store_f4(int per_cu);
 void launch_sample_setup(const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*, const f4*,
                          const unsigned long long*, f4*, uint32_t*, hipStream_t);
 void launch_shade_resolve(const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*, const f4*,
-                          const f4*, unsigned long long*, f4*, f4*, uint32_t*, uint32_t, f4*, hipStream_t);
+                          const f4*, unsigned long long*, f4*, f4*, uint32_t*, uint32_t, int, f4*, hipStream_t);
 size_t shade_counter_words();
-size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff);
+size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff, int per_cu);
 void launch_carry_history(const FrameUniforms&, const uint8_t*, const f4*, const f4*, f4*, f4*, unsigned long long*,
                           hipStream_t);
 void launch_sampling(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, f4*, const f4*,
@@ -46,11 +47,11 @@ void launch_vring_pack(const f4*, int, int, int, const int32_t*, int, uint32_t*,
 void launch_vring_unpack(const uint32_t*, int, int, int, const int32_t*, int, f4*, hipStream_t);
 void launch_shard_unpack_active(const FrameUniforms&, const f4*, const uint32_t*, uint32_t, uint32_t, const f4*, const f4*, f4*,
                                 f4*, hipStream_t);
-const u2* launch_jfa(const f4*, u2*, u2*, f4*, f4*, const float*, int, int, f4*, f4*, bool, hipStream_t);
+const u2* launch_jfa(const f4*, u2*, u2*, f4*, f4*, const float*, int, int, f4*, f4*, bool, int, hipStream_t);
 void launch_jfa_coord(const u2*, const f4*, f4*, int, int, hipStream_t);
 void launch_sibson(const f4*, const f4*, f4*, int, int, hipStream_t);
 void launch_sibson_runs(const f4*, const u2*, const f4*, f4*, f4*, f4*, uint32_t*, uint32_t*, f4*, int, int, bool, bool,
-                        bool, hipStream_t);
+                        int, bool, hipStream_t);
 int sibson_prefix_blocks(int W);
 size_t sibson_strip_words(int W, int H);
 size_t sibson_rowp_texels(int W, int H);
@@ -77,7 +78,7 @@ uint32_t diag_recorded_queries(hipStream_t);
 void diag_sample_trace(uint32_t*, uint32_t, uint32_t*, uint32_t, hipStream_t);
 #endif
 void launch_pullpush(const f4*, f4*, f4*, f4*, f4*, int, int, hipStream_t);
-void launch_atrous(const f4*, const f4*, const f4*, f4*, int, int, float, float, float, float, hipStream_t);
+void launch_atrous(const f4*, const f4*, const f4*, f4*, int, int, float, float, float, float, bool, int, hipStream_t);
 int pp_size(int W, int H);
 size_t pp_snap_count(int S);
 }  // namespace fr
@@ -246,6 +247,13 @@ struct fr_ctx {
   uint32_t chunk_refr = 0;  // fixed refraction-class chunk of the megakernel (FOVRT_SHADE_CHUNK_REFR), 0 adaptive
   uint32_t xcd_bands = 1;   // megakernel queue: per-XCD class bands (FOVRT_SHADE_XCD_BANDS=0: interleaved chunks)
   uint32_t handoff = 1;     // megakernel tail handoff (FOVRT_SHADE_HANDOFF): 0 never, 1 small launches, 2 always
+  int shade_blocks_per_cu = 0;  // resident megakernel blocks per CU (FOVRT_SHADE_BLOCKS_PER_CU; default and most:
+                                // shade_max_blocks_per_cu; fewer leave room for concurrent kernels)
+  int jfa_xcd = 1;             // JFA steps in XCD-contiguous runs of the block order (FOVRT_JFA_XCD=0: round robin)
+  int sib_strip_mid = 0;       // FOVRT_SIB_STRIP_MID=1: the mid-size wide discs go to k_sibson_strip too (helps
+                               // 45-90 degree gazes, costs the centred one)
+  bool atrous_rows2 = true;    // the stepWidth-1 A-Trous pass by k_atrous_rows2 (FOVRT_ATROUS_ROWS2=0: k_atrous)
+  int atrous_xcd = 1;          // k_atrous_rows2's blocks in XCD-contiguous runs (FOVRT_ATROUS_XCD=0: round robin)
   float* ftab = nullptr;  // texel-centre coordinates ((x + 0.5) / W, x < W; then (y + 0.5) / H)
   f4 *pull = nullptr, *push = nullptr, *snap = nullptr;
   f4 *sib_prefix = nullptr, *sib_blocks = nullptr;  // Sibson run form: per-row block prefix sums + block totals

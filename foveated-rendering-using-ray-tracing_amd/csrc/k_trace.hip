@@ -234,18 +234,13 @@ struct TravState {
   int tlo, thi;  // triangles of the last visited node still to test (one pair per step)
 };
 
-// trav_begin without resetting the any-hit product: a closest-hit query never changes ts.atten, so a chained
-// query (k_shade_paths, SHADE_CHAIN) keeps the answer of the shadow query before it there.
-FR_DEV void trav_restart(TravState& ts, f3 d, float tmax) {
+FR_DEV void trav_begin(TravState& ts, f3 d, float tmax) {
+  ts.atten = 1.0;
   ts.best.t = tmax; ts.best.leaf = -1; ts.best.prim = -1; ts.best.beta = 0; ts.best.gamma = 0;
   ts.inv = safe_inv(d);
   ts.node = 0;
   ts.sp = 0;
   ts.tlo = ts.thi = 0;
-}
-FR_DEV void trav_begin(TravState& ts, f3 d, float tmax) {
-  ts.atten = 1.0;
-  trav_restart(ts, d, tmax);
 }
 
 // Leaf-step form: a step visits a node only when the previous node's triangles are all tested, and
@@ -319,40 +314,6 @@ FR_DEV bool trav_step(const DevScene& sc, Stack st, TravState& ts, f3 o, f3 d, f
     }
     ts.tlo = j + 2;
   }
-  if (ts.tlo >= ts.thi && ts.node < 0) {
-    if (ts.best.prim == -2) ts.best.prim = sc.tri_prim[ts.best.leaf];
-    return true;
-  }
-  return false;
-}
-// Latency form of a step (k_shade_paths<true>, the small launches: a tile-sharded tracer's, or a frame below 64
-// pixel-samples per lane, whose end is set by the chain of dependent steps of the longest refraction trees, not by
-// throughput). trav_step fetches a node, then, from the leaf range the visit found, a triangle pair: two memory
-// round trips per step. Here the pending pair (the last of the previous visit's range) and the next node are
-// fetched together, one round trip per step: the pair is tested first, then the node visited with the best hit
-// known after it, exactly the t trav_step's visit would cull with (it visits only once a range is done). The node's
-// own leaves are tested in the next steps. Visits, tests and results are trav_step's; the order of a node's
-// triangle tests relative to the next visit's loads is all that changes.
-FR_DEV bool trav_step_lat(const DevScene& sc, Stack st, TravState& ts, f3 o, f3 d, float tmin, float tmax, bool any_hit) {
-  const bool pair = ts.tlo < ts.thi;
-  const bool visit = ts.node >= 0 && ts.thi - ts.tlo <= 2;
-  NodeSlabs N;
-  if (visit) N = load_node(sc, ts.node, ts.inv);
-  if (pair) {
-    const int j = ts.tlo;
-    const bool two = j + 1 < ts.thi;
-    const TriGeo g0 = sc.tri_geo[j];
-    const TriGeo g1 = sc.tri_geo[two ? j + 1 : j];
-    bool done = false;
-    test_tri(sc, j, g0, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done);
-    if (done) return true;
-    if (two) {
-      test_tri(sc, j + 1, g1, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done);
-      if (done) return true;
-    }
-    ts.tlo = j + 2;
-  }
-  if (visit) visit_loaded(N, st, ts, o, tmin);
   if (ts.tlo >= ts.thi && ts.node < 0) {
     if (ts.best.prim == -2) ts.best.prim = sc.tri_prim[ts.best.leaf];
     return true;
@@ -465,15 +426,11 @@ struct Item {
   int depth;
   float importance;
 };
-// The refraction work items waiting on a lane (its explicit recursion stack). ITEM_GLOBAL (default): in
+// The refraction work items waiting on a lane (its explicit recursion stack), in
 // a per-context device buffer, item k of every lane of the launch contiguous (k-major), 64 B per item,
-// so a push or a pop moves one half cache line with three 16-B accesses. The alternative is a private
-// array: the compiler puts it in scratch, where dword j of item k of the 64 lanes of a wave share one
-// 256-B row, so one lane's push or pop touched 11 different cache lines (1,072 B of scratch per lane).
-#ifndef ITEM_GLOBAL
-#define ITEM_GLOBAL 1
-#endif
-#if ITEM_GLOBAL
+// so a push or a pop moves one half cache line with three 16-B accesses. (Measured and not kept: a private
+// array. The compiler puts it in scratch, where dword j of item k of the 64 lanes of a wave share one
+// 256-B row, so one lane's push or pop touched 11 different cache lines (1,072 B of scratch per lane).)
 struct ItemStack {
   f4* base;         // item 0 of this lane
   uint32_t stride;  // f4 between consecutive items of one lane (4 x the launch's lanes)
@@ -489,13 +446,6 @@ struct ItemStack {
     return Item{mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), mk3(b.z, b.w, c.x), __float_as_int(c.y), c.z};
   }
 };
-#else
-struct ItemStack {
-  Item* base;
-  FR_DEV void put(int k, const Item& x) const { base[k] = x; }
-  FR_DEV Item get(int k) const { return base[k]; }
-};
-#endif
 
 struct ItemState {  // what of the current work item stays live after its closest hit
   f3 w;
@@ -997,13 +947,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_gbuffer(DevScene sc, FrameUnifo
 // ---------------------------------------------------------------------------------------------
 #define SHADE_SHARDS 8
 #define SHADE_SHARD_STRIDE 32  // uint32 words between shard counters (128 B)
-#define SHADE_REFR_CTR 16      // the shard's refraction-slot counter: word 16 of its line (SHADE_REFR_EXACT)
-// SHADE_REFR_EXACT (off): the refraction class of a large launch claimed slot by slot. It removes the late
-// starts the sample trace showed, but the pipelined 4K frame got no faster: 237.2 against 242.8 fps over five
-// interleaved runs each (and two modes, 229-247 fps, instead of one).
-#ifndef SHADE_REFR_EXACT
-#define SHADE_REFR_EXACT 0
-#endif
+#define SHADE_REFR_CTR 16      // word 16 of a shard's line: k_shade_resolve zeroes it with the chunk counter; nothing claims from it
+// (Measured and not kept: the refraction class of a large launch claimed slot by slot from that counter. It removed the
+// late starts the sample trace showed, but the pipelined 4K frame got no faster: 237.2 against 242.8 fps over five
+// interleaved runs each, and two modes, 229-247 fps, instead of one.)
 
 #ifndef SHADE_CHUNK
 #define SHADE_CHUNK 64
@@ -1148,16 +1095,6 @@ FR_DEV uint32_t rtime() { return (uint32_t)__builtin_amdgcn_s_memrealtime(); }
 #ifndef SHADE_WAVES
 #define SHADE_WAVES 3  // waves per SIMD the register allocation must allow (3: 168 VGPRs; measured best of 2-5)
 #endif
-#ifndef SHADE_CHAIN
-// A diffuse or reflection surface's light-sample (shadow) query and its bounce / mirror query are independent:
-// the bounce's ray (front hit point, cdir) is set when the surface is shaded, before the shadow query runs
-// (diffuse.cu:109-139, reflection.cu:108-130 trace them one after the other). With SHADE_CHAIN a lane whose shadow
-// query ends inside the traversal loop starts the bounce query there at once, keeping the shadow's answer in
-// ts.atten (a closest-hit query never touches it); the shading pass then runs the light-sample step and the
-// bounce's hit step back to back. The steps and their order are unchanged (same results, bit for bit); the lane
-// no longer idles until the wave's slowest query ends before it can start the bounce.
-#define SHADE_CHAIN 0
-#endif
 #ifndef SHADE_EXIT_T
 // Early exit from the traversal loop: once at most SHADE_EXIT_T lanes still traverse (after SHADE_EXIT_S passes) and
 // some lane is answered, the answered lanes shade and refill while the rest keep their traversal state for the next
@@ -1175,11 +1112,7 @@ FR_DEV uint32_t rtime() { return (uint32_t)__builtin_amdgcn_s_memrealtime(); }
 #ifndef SHADE_EXIT_REFR
 #define SHADE_EXIT_REFR 20
 #endif
-#ifndef SHADE_LAT_WAVES
-#define SHADE_LAT_WAVES 2  // k_shade_paths<true>: a latency-form step holds a node and a triangle pair at once
-#endif
-template <bool LAT>
-__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT ? SHADE_LAT_WAVES : SHADE_WAVES, LAT ? SHADE_LAT_WAVES : SHADE_WAVES))) void k_shade_paths(DevScene sc, FrameUniforms U,
+__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(SHADE_WAVES, SHADE_WAVES))) void k_shade_paths(DevScene sc, FrameUniforms U,
                                                              const uint32_t* __restrict__ active,
                                                              const uint32_t* __restrict__ ray_count,
                                                              const f4* __restrict__ weight,
@@ -1198,12 +1131,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
   if (threadIdx.x < 32) reinterpret_cast<float*>(&lds_root)[threadIdx.x] = reinterpret_cast<const float*>(sc.nodes)[threadIdx.x];
   counters_begin(lds_cnt);
   Counters cnt{lds_cnt};
-#if ITEM_GLOBAL
   const ItemStack items{item_store + (size_t)(blockIdx.x * TRACE_BLOCK + threadIdx.x) * 4, gridDim.x * TRACE_BLOCK * 4u};
-#else
-  Item item_arr[ITEM_STACK];
-  const ItemStack items{item_arr};
-#endif
   const uint32_t spp_shift = __builtin_ctz((uint32_t)U.spp);
   const uint32_t total = ray_count[0] * (uint32_t)U.spp;
   // The refraction class (the head of the class-major list: the long sample trees through the glass)
@@ -1223,7 +1151,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
                               : total < 8 * lanes
                                   ? min(max(nrefr / (lanes / 64), 8u), (uint32_t)SHADE_CHUNK) & ~((uint32_t)U.spp - 1u)
                                   : SHADE_CHUNK;
-  const bool refr_exact = chunk_refr >= SHADE_CHUNK;  // slot-exact refraction claims (SHADE_REFR_EXACT)
   const uint32_t nsmall = (nrefr + chunk_refr - 1) / chunk_refr;
   const uint32_t nchunks = nsmall + (total - nrefr + SHADE_CHUNK - 1) / SHADE_CHUNK;
   // xcd_bands (the default): class c's slots [cb[c], cb[c + 1]); shard (XCD) s takes the s-th eighth of
@@ -1246,12 +1173,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
   uint32_t shard = blockIdx.x & (SHADE_SHARDS - 1);
   uint32_t shards_left = SHADE_SHARDS;
   uint32_t q_next = 0, q_end = 0;
-#if SHADE_REFR_EXACT
-  bool refr_done = false;  // this shard's refraction slots are all claimed
-#endif
   // per-lane state: IDLE (no sample) -> TRAV (query in flight) -> READY (query answered, to shade)
   int ls = L_IDLE;
-  bool chained = false;  // the lane's query is the bounce of a chained pair (SHADE_CHAIN); ts.atten holds the shadow's
   uint32_t slot = 0;
   PathState ps;
   TravState ts;
@@ -1274,36 +1197,11 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
         // class (the longest paths) on one XCD (measured 173 vs 183 fps)
         if (xcd_bands) {
         bool found = false;
-#if SHADE_REFR_EXACT
-        // The refraction class is claimed slot by slot, as many slots as the wave has idle lanes, so a wave
-        // never holds unstarted refraction samples behind lanes busy with long trees (with 8- or 64-slot
-        // chunks such samples started up to 2 ms late and set the end of the launch).
-        // Only in a launch of 8 or more samples per lane (refr_exact; chunk_refr = 64): a smaller launch keeps
-        // its 8-slot chunks, which spread the class over more waves, so the tail handoff finds idle lanes
-        // beside the long trees (slot-exact claims there made a 4-GPU tracer's launch 10-20 % slower).
-        if (refr_exact && !refr_done) {
-          const uint32_t b0 = part(0, shard), n0 = part(0, shard + 1) - b0;
-          const uint32_t k = (uint32_t)__popcll(idle);
-          uint32_t off = 0;
-          if (lane == 0) off = atomicAdd(&chunk_ctr[shard * SHADE_SHARD_STRIDE + SHADE_REFR_CTR], k);
-          off = __builtin_amdgcn_readfirstlane(off);
-          if (off < n0) {
-            q_next = b0 + off;
-            q_end = b0 + min(off + k, n0);
-            continue;
-          }
-          refr_done = true;
-        }
-        const int c_first = refr_exact ? 1 : 0;
-#else
-        const int c_first = 0;
-#endif
         uint32_t j = 0;
         if (lane == 0) j = atomicAdd(&chunk_ctr[shard * SHADE_SHARD_STRIDE], 1u);
         j = __builtin_amdgcn_readfirstlane(j);
 #pragma unroll
         for (int c = 0; c < 4; c++) {  // constant bounds: unrolled, cb[] stays in registers
-          if (c < c_first) continue;
           const uint32_t b = part(c, shard), e = part(c, shard + 1);
           const uint32_t ch = c == 0 ? chunk_refr : SHADE_CHUNK;
           const uint32_t n = (e - b + ch - 1) / ch;
@@ -1317,9 +1215,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
         if (!found) {
           shard = (shard + 1) & (SHADE_SHARDS - 1);
           shards_left--;
-#if SHADE_REFR_EXACT
-          refr_done = false;
-#endif
         }
         } else {
         uint32_t j = 0;
@@ -1419,45 +1314,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LAT
       for (int u = 0; u < TRAV_UNROLL; u++)
         if (ls == L_TRAV) {
           DIAG(d_steps++);
-          if (LAT ? trav_step_lat(sc, st, ts, ps.qo, ps.qd, tmin, ps.qtmax, ps.qany)
-                  : trav_step(sc, st, ts, ps.qo, ps.qd, tmin, ps.qtmax, ps.qany)) {
-#if SHADE_CHAIN
-            if (ps.phase == PH_PARENT_SHADOW && ps.want_child && !chained) {
-              // the shadow query of a surface with a bounce / mirror child ended: start the child's query now
-              // (its origin is the shadow ray's, qo = front; path_shade sets the same ray when it shades)
-              chained = true;
-              ps.qd = ps.cdir; ps.qtmax = INFINITY; ps.qany = false;
-              trav_restart(ts, ps.qd, ps.qtmax);
-              RECORD_QUERY(ps);
-              DIAG(d_q++);
-            } else
-#endif
-            {
-              ls = L_READY;
-            }
-          }
+          if (trav_step(sc, st, ts, ps.qo, ps.qd, tmin, ps.qtmax, ps.qany)) ls = L_READY;
         }
     }
     STAMP_ADD(trav_cycles, t_tr);
     STAMP(t_step);
     if (ls == L_READY) {
-#if SHADE_CHAIN == 1
-      // a chained pair shades twice: the light-sample step with the shadow's answer (ts.atten; it sets up the
-      // bounce query the lane already traced), then the bounce's hit step (ts.best)
-      bool fin = false;
-#pragma unroll 1
-      for (int r = chained ? 2 : 1; r > 0; r--) fin = path_shade(sc, U, ps, items, cnt, ts.best, (float)ts.atten, fx);
-      chained = false;
-#else
-      // a chained pair: this pass runs the light-sample step with the shadow's answer (ts.atten); it sets up the
-      // bounce query, which the lane has already traced (ts.best): the lane stays READY and the next pass, which
-      // runs before any traversal, shades the bounce's hit
-      const bool ch = chained;
-      chained = false;
       const bool fin = path_shade(sc, U, ps, items, cnt, ts.best, (float)ts.atten, fx);
-      if (ch) {
-      } else
-#endif
       if (fin) {
         ps.total.flush(samples, help, slot, fx);
         ls = L_IDLE;
@@ -1764,65 +1627,55 @@ void launch_gbuffer(const DevScene& sc, const FrameUniforms& U, f4* position, f4
 }
 
 // Grid of k_shade_paths: persistent, as many resident blocks as the register budget allows (SHADE_WAVES
-// waves per SIMD, 4 SIMDs per CU, TRACE_BLOCK / 64 waves per block, 256 CUs).
-static int shade_blocks(const FrameUniforms& U, uint32_t max_active) {
+// waves per SIMD, 4 SIMDs per CU, TRACE_BLOCK / 64 waves per block, 256 CUs). per_cu: the context's blocks per CU
+// (fr_ctx::shade_blocks_per_cu, at most shade_max_blocks_per_cu).
+int shade_max_blocks_per_cu() { return 4 * SHADE_WAVES / (TRACE_BLOCK / 64); }
+static int shade_blocks(const FrameUniforms& U, uint32_t max_active, int per_cu) {
   size_t slots = (size_t)max_active * U.spp;
-  static const int per_cu = [] {  // FOVRT_SHADE_BLOCKS_PER_CU: tuning knob (fewer leaves room for concurrent kernels)
-    const char* v = getenv("FOVRT_SHADE_BLOCKS_PER_CU");
-    const int full = 4 * SHADE_WAVES / (TRACE_BLOCK / 64);  // resident blocks per CU at SHADE_WAVES waves/SIMD
-    return v ? std::max(1, std::min(full, atoi(v))) : full;
-  }();
   return (int)std::min<size_t>((slots + TRACE_BLOCK - 1) / TRACE_BLOCK, (size_t)256 * per_cu);
 }
 
 // Does a W x H frame at spp (max_active = W H) use the fixed-point sums and the tail handoff (SampleSum)?
 // handoff: 0 never, 1 below SHADE_FX_FRAME pixel-samples per lane of the grid, 2 always.
-static bool shade_fx_frame(int spp, uint32_t max_active, uint32_t handoff) {
+static bool shade_fx_frame(int spp, uint32_t max_active, uint32_t handoff, int per_cu) {
   if (handoff == 0) return false;
   if (handoff >= 2) return true;
   FrameUniforms U{};
   U.spp = spp;
-  const uint64_t lanes = (uint64_t)shade_blocks(U, max_active) * TRACE_BLOCK;
+  const uint64_t lanes = (uint64_t)shade_blocks(U, max_active, per_cu) * TRACE_BLOCK;
   return (uint64_t)max_active * (uint64_t)spp < (uint64_t)SHADE_FX_FRAME * lanes;
 }
 
 // Sample slots that can use the fixed-point form (32-B records in samples, 32-B help records).
-size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff) {
-  return shade_fx_frame(spp, max_active, handoff) ? (size_t)max_active * spp : 0;
+size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff, int per_cu) {
+  return shade_fx_frame(spp, max_active, handoff, per_cu) ? (size_t)max_active * spp : 0;
 }
 
 // The kernels' threshold: launches of fewer samples use the fixed-point form (all or none).
-static uint32_t shade_fx_below(const FrameUniforms& U, uint32_t max_active, uint32_t handoff) {
-  return shade_fx_frame(U.spp, max_active, handoff) ? 0xFFFFFFFFu : 0u;
+static uint32_t shade_fx_below(const FrameUniforms& U, uint32_t max_active, uint32_t handoff, int per_cu) {
+  return shade_fx_frame(U.spp, max_active, handoff, per_cu) ? 0xFFFFFFFFu : 0u;
 }
 
 void launch_shade_paths(const DevScene& sc, const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count,
                         uint32_t max_active, const f4* weight, const f4* history_cache, uint32_t* chunk_ctr,
                         f4* samples, unsigned long long* help, DevStats* stats, f4* aux, uint32_t* aux_seed,
-                        uint32_t chunk_refr, uint32_t xcd_bands, uint32_t handoff, f4* item_store, hipStream_t stream) {
+                        uint32_t chunk_refr, uint32_t xcd_bands, uint32_t handoff, int per_cu, f4* item_store,
+                        hipStream_t stream) {
   if (max_active == 0) return;
-  int blocks = shade_blocks(U, max_active);
+  const int blocks = shade_blocks(U, max_active, per_cu);
   // chunk_refr: a fixed refraction-class chunk (fr_ctx, FOVRT_SHADE_CHUNK_REFR), 0 = adaptive
   const uint32_t cr = chunk_refr ? std::min(std::max(chunk_refr & ~((uint32_t)U.spp - 1u), (uint32_t)U.spp), (uint32_t)SHADE_CHUNK) : 0u;
-  const uint32_t fxb = shade_fx_below(U, max_active, handoff);
-  // The latency form (trav_step_lat, SHADE_LAT_WAVES waves per SIMD) for the small launches of the fixed-point form
-  // (FOVRT_SHADE_LAT=1; 2: every launch; 0, the default: never). Bit-identical, but measured slower (round 6): 1080p
-  // C2 400 against 424 fps, megakernel 2.14 against 1.77 ms serialised; the group model's tracers 1.52 against 1.63
-  // ms at G = 8, but the view's speedup 2.73 against 2.95 (profiles/r06_latform/): the lost third wave per SIMD
-  // costs more than the halved round trips per step save.
-  static const int lat_mode = [] { const char* v = getenv("FOVRT_SHADE_LAT"); return v ? atoi(v) : 0; }();
-  const bool lat = lat_mode == 2 || (lat_mode == 1 && fxb != 0);
-  if (lat) blocks = std::min(blocks, 256 * 4 * SHADE_LAT_WAVES / (TRACE_BLOCK / 64));
-  hipLaunchKernelGGL(lat ? k_shade_paths<true> : k_shade_paths<false>, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc,
+  const uint32_t fxb = shade_fx_below(U, max_active, handoff, per_cu);
+  hipLaunchKernelGGL(k_shade_paths, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc,
                      U, active, ray_count, weight, history_cache, chunk_ctr, samples, stats, aux, aux_seed, cr,
                      xcd_bands, help, fxb, item_store);
 }
 
-// The megakernel's item stacks (ITEM_GLOBAL): the largest grid's lanes x ITEM_STACK items of 64 B.
-size_t shade_item_store_f4() {
+// The megakernel's item stacks (ItemStack): the largest grid's lanes x ITEM_STACK items of 64 B.
+size_t shade_item_store_f4(int per_cu) {
   FrameUniforms U{};
   U.spp = 1;
-  return (size_t)shade_blocks(U, 0xFFFFFFFFu) * TRACE_BLOCK * ITEM_STACK * 4;
+  return (size_t)shade_blocks(U, 0xFFFFFFFFu, per_cu) * TRACE_BLOCK * ITEM_STACK * 4;
 }
 
 void launch_sample_setup(const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count, uint32_t max_active,
@@ -1836,12 +1689,12 @@ void launch_sample_setup(const FrameUniforms& U, const uint32_t* active, const u
 void launch_shade_resolve(const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count,
                           uint32_t max_active, const f4* weight, const f4* history_cache, const f4* samples,
                           unsigned long long* help, f4* history_buffer, f4* shading, uint32_t* chunk_ctr,
-                          uint32_t handoff, f4* radiance, hipStream_t stream) {
+                          uint32_t handoff, int per_cu, f4* radiance, hipStream_t stream) {
   if (max_active == 0) return;
   int rblocks = (int)std::min<size_t>((max_active + 255) / 256, 4096);
   hipLaunchKernelGGL(k_shade_resolve, dim3(rblocks), dim3(256), 0, stream, U, active, ray_count, weight,
                      history_cache, samples, history_buffer, shading, chunk_ctr, help,
-                     shade_fx_below(U, max_active, handoff), radiance);
+                     shade_fx_below(U, max_active, handoff, per_cu), radiance);
 }
 
 size_t shade_counter_words() { return SHADE_SHARDS * SHADE_SHARD_STRIDE; }

@@ -36,7 +36,7 @@ wall = time.perf_counter() - t0
 lat, itv = t.frame_clock_read()
 t.frame_clock(False)
 order = np.argsort(lat)[::-1][:8]
-print(f"{mode} FOVRT_LAT_SIB_MAX={os.environ.get('FOVRT_LAT_SIB_MAX', '1')}: fps {n / wall:.1f} latency p50 "
+print(f"{mode}: fps {n / wall:.1f} latency p50 "
       f"{np.percentile(lat, 50):.2f} p99 {np.percentile(lat, 99):.2f} max {lat.max():.2f} ms; slowest (deg, ms): "
       + " ".join(f"{int(i)}:{lat[i]:.1f}" for i in order), flush=True)
 t.destroy()

@@ -128,7 +128,7 @@ def test_oracle_matches_golden(oracle, name):
 
 
 def _sqrt_le_bound(d):
-    """numpy mirror of k_image.hip sqrt_le_bound: the largest float32 x with sqrtf(x) <= d."""
+    """numpy mirror of fr_math.h sqrt_le_bound: the largest float32 x with sqrtf(x) <= d."""
     f32 = np.float32
     c = f32(d) * f32(d)
     while c > 0 and np.sqrt(c) > d:
@@ -141,7 +141,7 @@ def _sqrt_le_bound(d):
 
 
 def test_sqrt_free_disc_test_is_exact():
-    """Sibson's disc test 'sqrtf(r2) > d' is replaced by 'r2 > sqrt_le_bound(d)' (k_image.hip):
+    """Sibson's disc test 'sqrtf(r2) > d' is replaced by 'r2 > sqrt_le_bound(d)' (k_sibson.hip):
     equivalent for every float32 r2 >= 0 because sqrtf is correctly rounded and monotone. Checked
     here on the ulps around d*d and on random values."""
     rs = np.random.RandomState(3)

@@ -1,4 +1,4 @@
-"""k_sibson_rowp's whole-row prefix sums (csrc/k_image.hip), restated in numpy float32, against float64 sums.
+"""k_sibson_rowp's whole-row prefix sums (csrc/k_sibson.hip), restated in numpy float32, against float64 sums.
 
 k_sibson_strip sums a row's run as G[e] - G[s] with G = P + the row's block totals before it (k_jfa_final_prefix:
 P is the 64-column block-local exclusive prefix, T the block totals, both fp32 warp scans). Those sums carry an

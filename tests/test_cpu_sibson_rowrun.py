@@ -1,4 +1,4 @@
-"""The closed-form row run of k_sibson_runs (csrc/k_image.hip, sib_rows_setup / sib_row_run), restated in numpy
+"""The closed-form row run of k_sibson_runs (csrc/k_sibson.hip, sib_rows_setup / sib_row_run), restated in numpy
 float32 and checked against a brute-force walk of the reference's taps (sibsonFS.glsl:26-45: w from min_box.x in
 steps of 1/W, tap inside when dx^2 + dy^2 <= the bound of d) on the CPU.
 

@@ -1,4 +1,4 @@
-"""The exactness argument of k_sibson_wide's tap tables (csrc/k_image.hip, sib_axis_build), restated in numpy
+"""The exactness argument of k_sibson_wide's tap tables (csrc/k_sibson.hip, sib_axis_build), restated in numpy
 float32 and checked on the CPU: the reference's positions v_{k+1} = fl(v_k + 1/W) from min_box while v < max_box
 (sibsonFS.glsl:30-31) equal the segment table's v_s + (k - k_s) delta for every tap, over random boxes that
 cross binade edges, zero and the image border. The GPU tests check the kernel itself against the oracle."""
