@@ -663,7 +663,7 @@ int fr_destroy(fr_ctx* c) {
   if (c->stream5) hipStreamSynchronize(c->stream5);
   auto fr = [](void* p) { if (p) hipFree(p); };
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
-  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos);
+  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   if (c->nrm_work) normals_work_free(c->nrm_work);
   for (auto p : c->d_tex) fr(p);
@@ -785,8 +785,14 @@ static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
     const uint32_t gw = (uint32_t)std::min(8, c->W - (t8 % tx8) * 8), gh = (uint32_t)std::min(8, c->H - (t8 / tx8) * 8);
     c->U.front_pixels = c->front_need_px + (c->front_need_h[t8] ? 0u : gw * gh);
   }
+  // motion reprojection: the first G-buffer after a position update reprojects from the positions the previous
+  // one traced, and leaves the sampling launch of this frame a distance in WEIGHT.z
+  const bool motion = c->motion_on && c->moved;
   launch_gbuffer(c->dsc, c->U, c->img[P_pos(c)], c->img[P_nrm(c)], c->img[c->depth_cur], c->img[P_DIFFUSE],
-                 c->img[P_wgt(c)], c->gclass, c->stats, fs);
+                 c->img[P_wgt(c)], c->gclass, c->stats, motion ? c->d_pos : nullptr, motion ? c->prev_pos : nullptr,
+                 fs);
+  c->motion_frame = motion;
+  c->moved = false;
   c->compacted = false;
   return check_launch(c);
 }
@@ -804,7 +810,8 @@ static int enqueue_sampling(fr_ctx* c, hipStream_t fs) {
   launch_sampling(c->U, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
                   c->img[P_nrm(c)], c->img[P_DIFFUSE], c->img[P_EXTRA], c->mask, c->gclass, c->words, c->counts,
                   lazy ? 0 : c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh,
-                  c->U.shard_count > 1 ? c->bcount : nullptr, fs);
+                  c->U.shard_count > 1 ? c->bcount : nullptr, c->motion_frame, fs);
+  c->motion_frame = false;  // WEIGHT.z is the validity from here on: a repeated sampling launch runs the plain test
   if (c->cfg.write_extra) c->extra_owed = lazy;  // (write_extra = 0: EXTRA is never written, nothing is ever owed)
   if (lazy) {
     c->extra_U = c->U;
@@ -1800,6 +1807,7 @@ int fr_restore(fr_ctx* c, const void* host, size_t bytes) {
   c->lp_mode = -1;
   c->sib_prefix_fresh = false;
   c->hvalid_fresh = false;
+  c->moved = false;  // a snapshot carries no previous positions: the next G-buffer reprojects as over still geometry
   return FR_OK;
 }
 
@@ -1942,6 +1950,13 @@ static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where,
     if (const int rc = gpu_refit(c, c->spare_pos)) return fail(c, rc, name + ": " + c->err);
     std::swap(c->d_pos, c->spare_pos);
   }
+  // motion reprojection: spare_pos now holds the outgoing positions. If the last G-buffer traced them they become
+  // prev_pos (with the swap above a three-pointer rotation, no copy); after an earlier update since that G-buffer
+  // prev_pos already holds what it traced and stays.
+  if (c->motion_on && !c->moved) {
+    std::swap(c->spare_pos, c->prev_pos);
+    c->moved = true;
+  }
   if (where == FR_MEM_HOST) {
     memcpy(c->scene.pos.data(), xyz, bytes);
     c->pos_mirror_stale = false;
@@ -1977,6 +1992,23 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
   if (!c) return FR_E_INVALID;
   if (!xyz) return fail(c, FR_E_INVALID, "fr_update_geometry: positions are NULL");
   return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
+}
+
+int fr_set_motion_reprojection(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  if (on != 0 && on != 1) return fail(c, FR_E_INVALID, "fr_set_motion_reprojection: on is 0 or 1");
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (on && !c->prev_pos && dalloc(&c->prev_pos, c->scene.pos.size()) != hipSuccess) {
+    (void)hipGetLastError();
+    if (c->prev_pos) hipFree(c->prev_pos);
+    c->prev_pos = nullptr;
+    return fail(c, FR_E_NOMEM, "fr_set_motion_reprojection: device allocation (previous positions) failed");
+  }
+  c->motion_on = on != 0;
+  if (!on) c->moved = false;  // a pending motion is dropped: the next G-buffer is the plain one
+  return FR_OK;
 }
 
 int fr_set_normals(fr_ctx* c, const void* nrm, size_t ntris, int where) {

@@ -13,7 +13,10 @@
 #define FR_MAX_SHARD_RANKS 64  // ranks per view (an owner is one byte of the tile map)
 
 namespace fr {
-void launch_gbuffer(const DevScene&, const FrameUniforms&, f4*, f4*, f4*, f4*, f4*, uint8_t*, DevStats*, hipStream_t);
+// (the two f3 arrays: the positions this launch traces and the ones the previous launch traced, for the motion
+// form; NULL for the plain one)
+void launch_gbuffer(const DevScene&, const FrameUniforms&, f4*, f4*, f4*, f4*, f4*, uint8_t*, DevStats*, const f3*,
+                    const f3*, hipStream_t);
 void launch_shade_paths(const DevScene&, const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*,
                         const f4*, uint32_t*, f4*, unsigned long long*, DevStats*, f4*, uint32_t*, uint32_t, uint32_t,
                         uint32_t, int, f4*, hipStream_t);
@@ -29,7 +32,7 @@ void launch_carry_history(const FrameUniforms&, const uint8_t*, const f4*, const
                           hipStream_t);
 void launch_sampling(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, f4*, const f4*,
                      const f4*, f4*, uint8_t*, const uint8_t*, unsigned long long*, uint32_t*, int, uint8_t*, uint32_t*,
-                     bool, uint32_t*, hipStream_t);
+                     bool, uint32_t*, bool, hipStream_t);
 void launch_extra(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, const f4*, f4*, hipStream_t);
 size_t logpolar_inv_words(int W, int H);
 void launch_owner_counts(const FrameUniforms&, const uint32_t*, uint32_t*, hipStream_t);
@@ -190,6 +193,14 @@ struct fr_ctx {
   // fr_update_positions writes new positions here and swaps with d_pos once the update succeeded: the old
   // positions survive a failed rebuild on the device, without the host mirror
   f3* spare_pos = nullptr;
+  // Motion reprojection (fr_set_motion_reprojection). prev_pos: the positions the most recent G-buffer launch traced
+  // (allocated at the first on = 1; undefined while !moved, when d_pos are those positions). moved: d_pos changed
+  // since that launch; the next G-buffer runs its motion form over (d_pos, prev_pos) and clears it. An update with
+  // moved clear rotates d_pos -> prev_pos -> spare_pos -> d_pos instead of swapping d_pos and spare_pos, so spare_pos
+  // stays free between updates and nothing is copied. motion_frame: the last G-buffer ran the motion form and left
+  // a distance in WEIGHT.z for the sampling launch that follows it (which clears it).
+  f3* prev_pos = nullptr;
+  bool motion_on = false, moved = false, motion_frame = false;
   // scene.pos (the host mirror of d_pos) is behind: positions came from device memory and were not copied
   // back. fr_scene_export refreshes it; nothing else reads it.
   bool pos_mirror_stale = false;

@@ -183,7 +183,10 @@ FR_DEV f4 heat_map(float saliency) {
   return mk4(cuda_cosf(saliency * kPi_2 - kPi_2), cuda_sinf(saliency * kPi) * 1.5f, cuda_cosf(saliency * kPi_2), 1.0f);
 }
 
-template <bool LOCAL>  // LOCAL: a tile-local front (fr_set_front_local); the whole-screen instance carries none of it
+// LOCAL: a tile-local front (fr_set_front_local); the whole-screen instance carries none of it.
+// MOTION: this frame's G-buffer ran its motion form (fr_set_motion_reprojection): WEIGHT.z holds the distance of the
+// reprojected point, where it was a frame ago, from the previous eye, and the history depth is tested against that.
+template <bool LOCAL, bool MOTION>
 __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, const f4* __restrict__ position,
                                                   const f4* __restrict__ depth, const f4* __restrict__ depth_cache,
                                                   f4* __restrict__ weight, const f4* __restrict__ normal,
@@ -228,7 +231,7 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
       if ((0 <= query_uv.x && query_uv.x < screenf.x - 0.5f) && (0 <= query_uv.y && query_uv.y < screenf.y - 0.5f)) {
         uint32_t qx = f2u_sat(fr_round(query_uv.x)), qy = f2u_sat(fr_round(query_uv.y));
         f4 prev_depth = depth_cache[(size_t)qy * W + qx];
-        float diff = prev_depth.x - lengthc(xyz(pos) - U.prev_eye);  // samplingStep.ptx:258-273
+        float diff = prev_depth.x - (MOTION ? wgt.z : lengthc(xyz(pos) - U.prev_eye));  // samplingStep.ptx:258-273
         isValid = fabsf(diff) < sc.scene_epsilon ? 1.0f : 0.0f;
       }
     }
@@ -377,7 +380,8 @@ __global__ __launch_bounds__(256) void k_logpolar_mask(FrameUniforms U, float lp
 void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* position, const f4* depth,
                      const f4* depth_cache, f4* weight, const f4* normal, const f4* diffuse, f4* extra, uint8_t* mask,
                      const uint8_t* gclass, unsigned long long* words, uint32_t* counts, int write_extra,
-                     uint8_t* lp_cache, uint32_t* lp_inv, bool lp_refresh, uint32_t* bcount, hipStream_t stream) {
+                     uint8_t* lp_cache, uint32_t* lp_inv, bool lp_refresh, uint32_t* bcount, bool motion,
+                     hipStream_t stream) {
   if (lp_refresh) {
     const size_t N = (size_t)U.width * U.height;
     const float lpL = log_polar_L(U.gaze, U.screen * 0.25f);
@@ -389,8 +393,10 @@ void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* posit
                        stream, U, lpL, nu, inv, lp_cache);
   }
   dim3 grid((U.width + 15) / 16, (U.height + 15) / 16);
-  hipLaunchKernelGGL(U.front_need ? k_sampling<true> : k_sampling<false>, grid, dim3(256), 0, stream, U, sc, position, depth, depth_cache, weight, normal,
-                     diffuse, extra, mask, gclass, words, counts, write_extra, lp_cache, bcount);
+  auto k = U.front_need ? (motion ? k_sampling<true, true> : k_sampling<true, false>)
+                        : (motion ? k_sampling<false, true> : k_sampling<false, false>);
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, U, sc, position, depth, depth_cache, weight, normal, diffuse, extra,
+                     mask, gclass, words, counts, write_extra, lp_cache, bcount);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -846,14 +846,27 @@ FR_DEV void gbuffer_count(DevStats* stats, const FrameUniforms& U) {
     atomicAdd(&stats->gbuffer_primary, U.front_need ? (unsigned long long)U.front_pixels : (unsigned long long)U.width * U.height);
 }
 
+// The point (w, beta, gamma) of triangle k over the positions P (3 per triangle, scene order): fma(w, p0, fma(b, p1,
+// g p2)), the form surface() gives the texture coordinates.
+FR_DEV f3 tri_blend(const f3* __restrict__ P, int k, float w, float b, float g) {
+  const f3* p = P + 3 * (size_t)k;
+  return fma3(w, p[0], fma3(b, p[1], g * p[2]));
+}
+
 // The G-buffer outputs of one pixel's primary hit (g_diffuse.cu:67-144, g_miss gradientbg.cu:45-51).
+// MOTION (fr_set_motion_reprojection, the first G-buffer after a position update): the reprojection starts from where
+// the hit point was when the previous G-buffer traced its triangle (prev_pos: those positions; cur_pos: the ones this
+// launch traces), and WEIGHT.z carries that point's distance from the previous eye for this frame's k_sampling. A
+// triangle that did not move has delta = 0 exactly and gets the plain form's reprojection bits.
+template <bool MOTION>
 FR_DEV void gbuffer_store(const DevScene& sc, const FrameUniforms& U, bool on, int x, int y, f3 o, f3 d, const Hit& h,
                           f4* __restrict__ position, f4* __restrict__ normal, f4* __restrict__ depth,
-                          f4* __restrict__ diffuse, f4* __restrict__ weight, uint8_t* __restrict__ gclass) {
+                          f4* __restrict__ diffuse, f4* __restrict__ weight, uint8_t* __restrict__ gclass,
+                          const f3* __restrict__ cur_pos, const f3* __restrict__ prev_pos) {
   const int W = U.width;
   if (on) {
     f3 origin = mk3(0.0f), nrm = mk3(0.0f), result = mk3(0.0f);
-    float radiance = 0.0f, dv = 0.0f;
+    float radiance = 0.0f, dv = 0.0f, prev_dist = 0.0f;
     f2 reproj = mk2(-1.0f, -1.0f);
     int cls = 3;  // primary-hit class for the class-major active list: 0 refr, 1 refl, 2 diffuse, 3 miss
     if (h.leaf >= 0) {
@@ -868,7 +881,14 @@ FR_DEV void gbuffer_store(const DevScene& sc, const FrameUniforms& U, bool on, i
       nrm = s.ng;
       dv = lengthc(hp - U.eye);
       // compute_reprojection as g_diffuse.ptx:659-689: contracted rows, rcp(w) * row, fma(ndc, W, W) * 0.5
-      f4 p_cs = mul(U.prev_vp, mk4(hp, 1.0f));
+      f3 hp_prev = hp;
+      if (MOTION) {
+        const float w = 1.0f - h.beta - h.gamma;
+        const f3 delta = tri_blend(prev_pos, h.prim, w, h.beta, h.gamma) - tri_blend(cur_pos, h.prim, w, h.beta, h.gamma);
+        if (!(delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f)) hp_prev = hp + delta;
+        prev_dist = lengthc(hp_prev - U.prev_eye);
+      }
+      f4 p_cs = mul(U.prev_vp, mk4(hp_prev, 1.0f));
       const float iw = 1.0f / p_cs.w;
       reproj = mk2(__builtin_fmaf(p_cs.x * iw, U.screen.x, U.screen.x) * 0.5f,
                    __builtin_fmaf(p_cs.y * iw, U.screen.y, U.screen.y) * 0.5f);
@@ -886,7 +906,7 @@ FR_DEV void gbuffer_store(const DevScene& sc, const FrameUniforms& U, bool on, i
                       __builtin_fmaf(nrm.z, 0.5f, 0.5f), radiance);
     depth[idx] = mk4(dv, dv, dv, 1.0f);
     diffuse[idx] = mk4(result, 1.0f);
-    weight[idx] = mk4(reproj.x, reproj.y, 0.0f, 1.0f);
+    weight[idx] = mk4(reproj.x, reproj.y, MOTION ? prev_dist : 0.0f, 1.0f);
     gclass[idx] = (uint8_t)cls;
   }
 }
@@ -895,11 +915,15 @@ FR_DEV void gbuffer_store(const DevScene& sc, const FrameUniforms& U, bool on, i
 // Entry 0: G-buffer. One lane per pixel, 8x8-pixel tiles per wave (coherent primary rays).
 // ---------------------------------------------------------------------------------------------
 // LOCAL: a tile-local front (U.front_need set; fr_set_front_local); the whole-screen instance carries none of it.
-template <bool LOCAL>
+// MOTION: gbuffer_store's motion form (cur_pos / prev_pos: 18 more scattered dword loads on the hit lanes, no LDS); the
+// plain instances read neither pointer.
+template <bool LOCAL, bool MOTION>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_gbuffer(DevScene sc, FrameUniforms U, f4* __restrict__ position,
                                                          f4* __restrict__ normal, f4* __restrict__ depth,
                                                          f4* __restrict__ diffuse, f4* __restrict__ weight,
-                                                         uint8_t* __restrict__ gclass, DevStats* stats) {
+                                                         uint8_t* __restrict__ gclass, DevStats* stats,
+                                                         const f3* __restrict__ cur_pos,
+                                                         const f3* __restrict__ prev_pos) {
   __shared__ int32_t lds_stack[BVH_STACK * TRACE_BLOCK];
   Stack st{&lds_stack[threadIdx.x]};
   const int W = U.width, H = U.height;
@@ -927,7 +951,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_gbuffer(DevScene sc, FrameUnifo
   while (__ballot(tracing)) {
     if (tracing && trav_step(sc, st, ts, o, d, sc.scene_epsilon, INFINITY, false)) tracing = false;
   }
-  gbuffer_store(sc, U, on, x, y, o, d, ts.best, position, normal, depth, diffuse, weight, gclass);
+  gbuffer_store<MOTION>(sc, U, on, x, y, o, d, ts.best, position, normal, depth, diffuse, weight, gclass, cur_pos,
+                        prev_pos);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1618,12 +1643,17 @@ uint32_t diag_recorded_queries(hipStream_t stream) {
 // Host launchers
 // ---------------------------------------------------------------------------------------------
 void launch_gbuffer(const DevScene& sc, const FrameUniforms& U, f4* position, f4* normal, f4* depth, f4* diffuse,
-                    f4* weight, uint8_t* gclass, DevStats* stats, hipStream_t stream) {
+                    f4* weight, uint8_t* gclass, DevStats* stats, const f3* cur_pos, const f3* prev_pos,
+                    hipStream_t stream) {
   int tiles = ((U.width + 7) / 8) * ((U.height + 7) / 8);
   int threads = tiles * 64;
   int blocks = (threads + TRACE_BLOCK - 1) / TRACE_BLOCK;
-  hipLaunchKernelGGL(U.front_need ? k_gbuffer<true> : k_gbuffer<false>, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc, U, position, normal, depth, diffuse,
-                     weight, gclass, stats);
+  // the motion form when the caller gives both position arrays (context.cpp, enqueue_geometry)
+  const bool motion = cur_pos && prev_pos;
+  auto k = U.front_need ? (motion ? k_gbuffer<true, true> : k_gbuffer<true, false>)
+                        : (motion ? k_gbuffer<false, true> : k_gbuffer<false, false>);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc, U, position, normal, depth, diffuse, weight,
+                     gclass, stats, cur_pos, prev_pos);
 }
 
 // Grid of k_shade_paths: persistent, as many resident blocks as the register budget allows (SHADE_WAVES

@@ -181,6 +181,7 @@ _SIGS = {
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
+    "fr_set_motion_reprojection": [C.c_void_p, C.c_int],
     "fr_scene_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
     "fr_get_stats": [C.c_void_p, C.POINTER(fr_stats)],
     "fr_reset_stats": [C.c_void_p],
@@ -669,6 +670,12 @@ class PathTracer:
         cv, nv = np.empty(3 * a.num_tris, np.int32), C.c_int()
         self._check(_lib.fr_normal_groups(self._ctx, cv.ctypes.data_as(C.POINTER(C.c_int32)), cv.size, C.byref(nv)))
         return cv, nv.value
+
+    def set_motion_reprojection(self, on=True):
+        """fr_set_motion_reprojection: the first G-buffer after a position update reprojects each hit point from
+        where its triangle was when the previous G-buffer traced it, and that frame's sampling tests the history
+        depth against that point (off by default; one more device position array at the first on)."""
+        self._check(_lib.fr_set_motion_reprojection(self._ctx, int(bool(on))))
 
     def bvh_sah_cost(self) -> float:
         """SAH cost of the tree in use (fr_bvh_sah_cost): compare a refitted tree with itself when built."""

@@ -437,6 +437,29 @@ int fr_update_geometry(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntr
 int fr_set_normals(fr_ctx* ctx, const void* nrm, size_t ntris, int where);
 int fr_recompute_normals(fr_ctx* ctx, float* ms);
 int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* nverts);
+/* History that follows moving geometry (off by default). The G-buffer reprojects a hit point with the previous
+ * camera, and the sampling stage accepts the history there only when the depth stored a frame ago equals the
+ * point's distance from the previous eye: both assume the point stood still. With motion reprojection on, the
+ * first G-buffer after a position update (fr_set_positions, fr_update_positions, fr_update_geometry) moves each
+ * hit point back to where the same point of its triangle (same barycentrics) was when the previous G-buffer
+ * traced it. fp32, every fma written out; for a hit (prim k, beta b, gamma g) over positions P (3 per triangle):
+ *   w = 1.0f - b - g;  blend(P).c = fma(w, P[3k].c, fma(b, P[3k+1].c, g * P[3k+2].c))        c = x, y, z
+ *   delta = blend(prev) - blend(cur);  hp_prev = delta == (0, 0, 0) ? hp : hp + delta         hp = POSITION
+ *   WEIGHT = (reprojection of hp_prev, length(hp_prev - prev_eye), 1)
+ * and that frame's sampling stage tests DEPTH_CACHE against WEIGHT.z instead of length(POSITION - prev_eye); it
+ * still leaves WEIGHT = (qu, qv, valid, 0). A triangle whose nine floats did not change gets the bits it gets
+ * today, as does every frame with no update since the last G-buffer and every frame with the feature off. prev
+ * is the positions the most recent G-buffer traced: of several updates before one G-buffer the first one's
+ * outgoing positions are kept. A rejected update or a failed rebuild changes nothing; fr_refit_bvh,
+ * fr_rebuild_bvh, fr_set_normals and fr_recompute_normals neither. The first on = 1 allocates one more device
+ * position array (36 B per triangle; FR_E_NOMEM); nothing is allocated per frame or per update (the arrays
+ * rotate, no copy). on = 0 drops a pending motion (the positions then in place count as the ones the last G-buffer
+ * traced), and so does fr_restore (a snapshot does not carry the previous positions: the frame after a restore
+ * reprojects as over still geometry). FR_E_INVALID for a NULL
+ * context or on outside {0, 1}. The call waits for the context's pending work. Not covered: a changed triangle
+ * count, a sampling launch repeated for one G-buffer (the repeat runs the plain test), groups (each rank's
+ * context is switched and updated by its caller). */
+int fr_set_motion_reprojection(fr_ctx* ctx, int on);
 /* Buffer access (PathTracer::get_texture, FR/PathTracer.cpp:337-374; rtBufferMap). */
 int fr_get_buffer(fr_ctx* ctx, int id, fr_buffer_view* view);
 int fr_read_buffer(fr_ctx* ctx, int id, void* host, size_t bytes);

@@ -184,6 +184,10 @@ class PathTracer {
     check(fr_recompute_normals(ctx(), &ms), ctx_, "recompute_normals");
     return ms;
   }
+  // history follows moving geometry: the G-buffer after a position update reprojects from the previous positions
+  void set_motion_reprojection(bool on) {
+    check(fr_set_motion_reprojection(ctx(), on ? 1 : 0), ctx_, "set_motion_reprojection");
+  }
   // the smooth vertex of every corner 3 t + k (-1: the triangle has no normals); *nverts = their number
   std::vector<int32_t> normal_groups(int* nverts = nullptr) {
     fr_scene_arrays a;
