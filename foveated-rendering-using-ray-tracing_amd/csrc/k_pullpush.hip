@@ -264,8 +264,12 @@ void launch_pullpush(const f4* in, f4* pull, f4* push, f4* snap, f4* out, int W,
   a.W = W; a.H = H; a.S = pp_size(W, H); a.AW = a.S + a.S / 2;
   a.e = 0;
   while ((1 << a.e) < a.S) a.e++;
-  if (a.e == 0) {  // 1x1 screen: pull/push degenerate to a copy
-    hipMemcpyAsync(out, in, sizeof(f4), hipMemcpyDeviceToDevice, stream);
+  if (a.e <= 1) {
+    // S = 1 and S = 2: the reference's push loop never writes the full-resolution region. It moves
+    // writeOffset to (0, 0) after step--, when the NEXT dispatch is the last one; at e = 1 the only
+    // dispatch still writes at (S, 1), and at e = 0 there is none (PullPushInterpolation.cpp:163-198).
+    // pullpushFinal then copies out what the cleared atlas holds: zeros, for any input.
+    hipMemsetAsync(out, 0, (size_t)W * H * sizeof(f4), stream);
     return;
   }
   for (int sl = a.e; sl > 0;) {

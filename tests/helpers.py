@@ -147,7 +147,8 @@ class PullPushNp:
     reads of the atlas being written see it as it was when the dispatch began (the resolution of the
     reference's in-dispatch races that oracle and GPU share). Input zero-padded to
     S x S, S = 2^ceil(log2(max(W, H))) (the reference requires W = H = 2^e). Atlases 1.5S x S
-    RGBA32F persist across calls (the push atlas carries texels across frames)."""
+    RGBA32F persist across calls (the push atlas carries texels across frames). At S <= 2 the host
+    loop never writes the region render returns (zeros: tests/test_cpu_recon_cases.py)."""
 
     def __init__(self, W, H):
         S = 1
@@ -199,10 +200,10 @@ class PullPushNp:
                 f32(1 / 16)]
         wox, woy = S, 1
         for count, step in zip(range(1, e + 1), range(e - 1, -1, -1)):
-            if step == 0:
-                wox, woy = 0, 0
             n = 1 << count
             gy, gx = np.mgrid[woy:woy + n, wox:wox + n]
+            inside = (gx < self.AW) & (gy < S)  # the dispatch runs over the atlas
+            gy, gx = gy[inside], gx[inside]
 
             def tdiv2(v):  # GLSL ivec2 /= 2: truncation toward zero
                 return np.sign(v) * (np.abs(v) // 2)
@@ -229,6 +230,12 @@ class PullPushNp:
                 acc = (acc + (filt[i] * self._load(snap, qx + ox, qy + oy)).astype(np.float32)).astype(np.float32)
             self.push[gy, gx] = np.where((nxt[..., 3] > 0)[..., None], nxt, acc)
             woy += 1 << count
+            # PullPushInterpolation.cpp:191-197: the write offset moves to (0, 0) after step-- when the
+            # NEXT dispatch is the last one (step == 0). At S = 2 the only dispatch already has step 0
+            # and still writes at (S, 1): the full-resolution region is never written (render's output
+            # stays what the atlas held, zeros).
+            if step - 1 == 0:
+                wox, woy = 0, 0
         return self.push[:H, :W].copy()  # pullpushFinal.glsl:14-19
 
 
