@@ -444,6 +444,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   for (auto& e : c->ev_jfa) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& row : c->lat_ev) for (auto& e : row) hipEventCreate(&e);
   for (auto& e : c->ev_counts) hipEventCreateWithFlags(&e, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->ev_geo_read, hipEventDisableTiming);
   read_env_knobs(c);
 
   std::string err;
@@ -476,6 +477,12 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     return hipMemcpy(*dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
   };
   if (!up(&c->d_shade, shade) || !up(&c->d_pos, s.pos) || dalloc(&c->spare_pos, s.pos.size()) != hipSuccess) {
+    c->err = "device allocation (scene) failed";
+    return bail(FR_E_NOMEM);
+  }
+  // the record of enqueued updates (fr_update_geometry_enqueue allocates nothing)
+  if (dalloc(&c->geo, 1) != hipSuccess || hipMemset(c->geo, 0, sizeof(fr::GeoUpdateState)) != hipSuccess ||
+      hipHostMalloc((void**)&c->h_geo, sizeof(fr::GeoUpdateState)) != hipSuccess) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
@@ -672,6 +679,9 @@ int fr_destroy(fr_ctx* c) {
   for (int k = 0; k < fr_ctx::MAX_SLOTS; k++) { fr(c->mask_p[k]); fr(c->ray_count_p[k]); fr(c->active_p[k]); fr(c->owner_counts_p[k]); }
   fr(c->bcount); fr(c->shard_map); fr(c->front_need); fr(c->shade_radiance);
   if (c->h_counts) hipHostFree(c->h_counts);
+  fr(c->geo);
+  if (c->h_geo) hipHostFree(c->h_geo);
+  if (c->ev_geo_read) hipEventDestroy(c->ev_geo_read);
   for (auto e : c->ev_counts) if (e) hipEventDestroy(e);
   fr(c->gclass); fr(c->lp_cache); fr(c->lp_inv); fr(c->words); fr(c->counts); fr(c->offsets); fr(c->tiles); fr(c->shade_ctr); fr(c->samples); fr(c->sample_help); fr(c->aux_p[0]); fr(c->aux_p[1]); fr(c->aux_seed_p[0]); fr(c->aux_seed_p[1]); fr(c->hvalid); fr(c->item_store); fr(c->jfa_a); fr(c->jfa_b); fr(c->ftab);
   fr(c->pull); fr(c->push); fr(c->snap); fr(c->stats); fr(c->sib_prefix); fr(c->sib_blocks); fr(c->sib_wide); fr(c->sib_strips); fr(c->sib_rowp);
@@ -810,12 +820,13 @@ static int enqueue_sampling(fr_ctx* c, hipStream_t fs) {
   launch_sampling(c->U, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
                   c->img[P_nrm(c)], c->img[P_DIFFUSE], c->img[P_EXTRA], c->mask, c->gclass, c->words, c->counts,
                   lazy ? 0 : c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh,
-                  c->U.shard_count > 1 ? c->bcount : nullptr, c->motion_frame, fs);
+                  c->U.shard_count > 1 ? c->bcount : nullptr, c->motion_frame, c->dev_box, fs);
   c->motion_frame = false;  // WEIGHT.z is the validity from here on: a repeated sampling launch runs the plain test
   if (c->cfg.write_extra) c->extra_owed = lazy;  // (write_extra = 0: EXTRA is never written, nothing is ever owed)
   if (lazy) {
     c->extra_U = c->U;
     c->extra_sc = c->dsc;
+    c->extra_box = c->dev_box;
     c->extra_depth = c->depth_cur;
     c->extra_nrm = P_nrm(c);
     c->extra_wgt = P_wgt(c);
@@ -930,7 +941,7 @@ static void materialize_extra_now(fr_ctx* c) {
   join_recon(c);
   hipSetDevice(c->cfg.device);
   launch_extra(c->extra_U, c->extra_sc, c->img[c->extra_depth], c->img[c->extra_wgt], c->img[c->extra_nrm],
-               c->img[P_DIFFUSE], c->img[P_EXTRA], c->stream);
+               c->img[P_DIFFUSE], c->img[P_EXTRA], c->extra_box, c->stream);
   c->extra_owed = false;
 }
 // does the owed heat map read this physical buffer?
@@ -1971,6 +1982,18 @@ static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where,
   // reference's scene AABB does at load time (FR/PathTracer.cpp:601-602,663)
   c->scene.bbox_min = c->dsc.bbox_min = lo;
   c->scene.bbox_max = c->dsc.bbox_max = hi;
+  if (c->dev_box) {
+    // the context has enqueued updates: the saliency stage reads the box from device memory, kept current here
+    // (an owed EXTRA keeps the one its sampling launch saw)
+    const float box[6] = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z};
+    if (c->extra_owed && c->extra_box == c->geo->box) {
+      HIP_TRY(c, hipMemcpyAsync(c->geo->xbox, c->geo->box, sizeof(box), hipMemcpyDeviceToDevice, c->stream));
+      c->extra_box = c->geo->xbox;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->geo->box, box, sizeof(box), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->box_mirror_stale = false;
+  }
   // the normals last, over the positions and the tree now in place (spare_pos holds the replaced positions
   // and is free again)
   if (normals == FR_NORMALS_GIVEN) return write_given_normals(c, nrm, where, name);
@@ -1992,6 +2015,108 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
   if (!c) return FR_E_INVALID;
   if (!xyz) return fail(c, FR_E_INVALID, "fr_update_geometry: positions are NULL");
   return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
+}
+
+// fr_update_geometry (device memory, refit) in stream order: every launch below goes on the context stream and
+// nothing here waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no synchronisation, no copy to
+// the host, no allocation). What the host learnt from the device in update_positions stays there: the verdict of
+// the two checks is a device word that k_take_over publishes and every later kernel of the update reads, and the
+// scene box goes from the check's result into geo->box, where the saliency stage reads it from now on.
+// The three position arrays rotate here, at enqueue time and whatever the verdict, exactly as in update_positions;
+// their contents follow in stream order (k_take_over fills the array that becomes d_pos with the caller's
+// positions, or with the current ones when the update is rejected). That is safe because every reader and writer
+// of the three arrays, the tree and the normals is ordered on the context stream: the front stages of a pipelined
+// frame run on stream5, but entry 3 of that frame waits for them on the context stream (ev_front) before this
+// update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
+// The reconstruction streams read none of it, so they are not joined.
+int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_update_geometry_enqueue";
+  if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
+  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
+  if (normals != FR_NORMALS_KEEP && normals != FR_NORMALS_GIVEN && normals != FR_NORMALS_RECOMPUTE)
+    return fail(c, FR_E_INVALID, name + ": bad normals kind");
+  if (normals == FR_NORMALS_GIVEN && !nrm) return fail(c, FR_E_INVALID, name + ": FR_NORMALS_GIVEN without normals");
+  if (c->group_refs > 0 || c->U.shard_count > 1)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_update_geometry)");
+  if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
+  hipSetDevice(c->cfg.device);
+  c->stream_dirty = true;  // the next pipelined frame's front stages (stream5) start after this update
+  // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
+  if (c->front_pending) { hipStreamWaitEvent(c->stream, c->ev_front, 0); c->front_pending = false; }
+  if (ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ready_event), 0));
+  const int nt = (int)ntris;
+  std::string err;
+  if (!gpu_check_positions_enqueue(c->bvh_work, static_cast<const float*>(xyz), nt, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  const bool given = normals == FR_NORMALS_GIVEN;
+  if (given && !gpu_check_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), &c->geo->bad_nrm, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  // the box: seeded from the host's at the first enqueue; an owed EXTRA keeps the one its sampling launch saw
+  int flags = 0;
+  if (!c->dev_box) flags |= 1;
+  if (c->extra_owed && c->extra_box == c->geo->box) {
+    flags |= 2;
+    c->extra_box = c->geo->xbox;
+  }
+  if (!gpu_take_over_positions(c->bvh_work, static_cast<const f3*>(xyz), c->d_pos, nt, c->spare_pos,
+                               given ? &c->geo->bad_nrm : nullptr, c->geo, flags, c->scene.bbox_min, c->scene.bbox_max,
+                               c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  c->dev_box = c->geo->box;
+  c->box_mirror_stale = true;
+  if (!given) HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // xyz has been read
+  const uint32_t* reject = &c->geo->reject;
+  const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  if (!gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  std::swap(c->d_pos, c->spare_pos);
+  if (c->motion_on && !c->moved) {  // as update_positions: the outgoing positions are what the last G-buffer traced
+    std::swap(c->spare_pos, c->prev_pos);
+    c->moved = true;
+  }
+  c->pos_mirror_stale = true;
+  if (given) {
+    if (!gpu_scatter_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), c->d_shade, reject, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // nrm has been read as well
+    c->nrm_mirror_stale = true;
+  } else if (normals == FR_NORMALS_RECOMPUTE) {
+    if (!gpu_recompute_normals_enqueue(c->nrm_work, c->d_pos, c->d_shade, reject, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    c->nrm_mirror_stale = true;
+  }
+  c->geo_read_pending = true;
+  return FR_OK;
+}
+
+int fr_geometry_consumed(fr_ctx* c, void* stream) {
+  if (!c) return FR_E_INVALID;
+  if (!c->geo_read_pending) return FR_OK;
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamWaitEvent(static_cast<hipStream_t>(stream), c->ev_geo_read, 0));
+  return FR_OK;
+}
+
+int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) {
+  if (!c) return FR_E_INVALID;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(c->h_geo, c->geo, sizeof(fr::GeoUpdateState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const fr::GeoUpdateState& g = *c->h_geo;
+  if (applied) *applied = g.applied;
+  if (rejected) *rejected = g.rejected;
+  if (g.rejected > c->geo_rejected_seen[0]) {
+    const bool pos = g.rejected_pos > c->geo_rejected_seen[1], nr = g.rejected_nrm > c->geo_rejected_seen[2];
+    c->err = std::string("fr_update_geometry_enqueue: ") +
+             (pos && nr ? "position not finite, normal not finite" : pos ? "position not finite" : "normal not finite") +
+             " (update rejected on the device, scene unchanged)";
+  }
+  c->geo_rejected_seen[0] = g.rejected;
+  c->geo_rejected_seen[1] = g.rejected_pos;
+  c->geo_rejected_seen[2] = g.rejected_nrm;
+  return FR_OK;
 }
 
 int fr_set_motion_reprojection(fr_ctx* c, int on) {
@@ -2326,10 +2451,23 @@ extern "C" {
 
 int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
   if (!c || !o) return FR_E_INVALID;
+  if (c->geo_read_pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
+    // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
+    hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
   if (c->pos_mirror_stale) {  // positions last came from device memory (fr_update_positions): fetch them now
     hipSetDevice(c->cfg.device);
     HIP_TRY(c, hipMemcpy(c->scene.pos.data(), c->d_pos, c->scene.pos.size() * sizeof(f3), hipMemcpyDeviceToHost));
     c->pos_mirror_stale = false;
+  }
+  if (c->box_mirror_stale) {  // an enqueued update left the scene box on the device (fr_update_geometry_enqueue)
+    hipSetDevice(c->cfg.device);
+    float box[6];
+    HIP_TRY(c, hipMemcpy(box, c->geo->box, sizeof(box), hipMemcpyDeviceToHost));
+    c->scene.bbox_min = c->dsc.bbox_min = mk3(box[0], box[1], box[2]);
+    c->scene.bbox_max = c->dsc.bbox_max = mk3(box[3], box[4], box[5]);
+    c->box_mirror_stale = false;
   }
   if (c->nrm_mirror_stale) {  // normals were last written on the device: they are d_shade's n0 / n1 / n2 .xyz
     hipSetDevice(c->cfg.device);

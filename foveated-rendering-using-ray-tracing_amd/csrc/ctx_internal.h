@@ -32,8 +32,9 @@ void launch_carry_history(const FrameUniforms&, const uint8_t*, const f4*, const
                           hipStream_t);
 void launch_sampling(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, f4*, const f4*,
                      const f4*, f4*, uint8_t*, const uint8_t*, unsigned long long*, uint32_t*, int, uint8_t*, uint32_t*,
-                     bool, uint32_t*, bool, hipStream_t);
-void launch_extra(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, const f4*, f4*, hipStream_t);
+                     bool, uint32_t*, bool, const float*, hipStream_t);
+void launch_extra(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, const f4*, f4*, const float*,
+                  hipStream_t);
 size_t logpolar_inv_words(int W, int H);
 void launch_owner_counts(const FrameUniforms&, const uint32_t*, uint32_t*, hipStream_t);
 void launch_mask_words(const uint8_t*, const uint8_t*, int, int, unsigned long long*, uint32_t*, hipStream_t);
@@ -64,6 +65,11 @@ void bvh_work_free(BvhWork*);
 bool bvh_work_prepare(BvhWork**, int, hipStream_t, std::string&);
 bool bvh_builder_warm(BvhWork*, hipStream_t, std::string&);
 bool gpu_refit_bvh(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, hipStream_t, std::string&);
+bool gpu_refit_bvh_enqueue(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, const uint32_t*, hipStream_t,
+                           std::string&);
+bool gpu_check_positions_enqueue(BvhWork*, const float*, int, hipStream_t, std::string&);
+bool gpu_take_over_positions(BvhWork*, const f3*, const f3*, int, f3*, const uint32_t*, GeoUpdateState*, int, f3, f3,
+                             hipStream_t, std::string&);
 bool gpu_bvh_cost(BvhWork*, const BvhNode*, int, float*, hipStream_t, std::string&);
 bool gpu_check_positions(BvhWork*, const float*, int, bool*, float*, hipStream_t, std::string&);
 // shading normals over moving geometry (k_normals.hip)
@@ -74,6 +80,10 @@ void normals_work_free(NormalsWork*);
 bool gpu_recompute_normals(NormalsWork*, const f3*, TriShade*, hipStream_t, std::string&);
 bool gpu_check_normals(NormalsWork*, const float*, bool*, hipStream_t, std::string&);
 bool gpu_scatter_normals(NormalsWork*, const float*, TriShade*, hipStream_t, std::string&);
+// their enqueue halves (no wait; the uint32_t*: the device verdict word of an enqueued update, or NULL)
+bool gpu_recompute_normals_enqueue(NormalsWork*, const f3*, TriShade*, const uint32_t*, hipStream_t, std::string&);
+bool gpu_check_normals_enqueue(NormalsWork*, const float*, uint32_t*, hipStream_t, std::string&);
+bool gpu_scatter_normals_enqueue(NormalsWork*, const float*, TriShade*, const uint32_t*, hipStream_t, std::string&);
 #ifdef FR_STAMPS
 void launch_trace_queries(const DevScene&, const f4*, uint32_t, f4*, uint32_t*, hipStream_t, int);
 void diag_record_queries(f4*, uint32_t, hipStream_t);
@@ -126,7 +136,8 @@ struct fr_ctx {
   // earlier work on `stream`, although they overwrite shared buffers (gclass, DIFFUSE, EXTRA, depth,
   // ballots, counts, lp_cache). So every ABI call that enqueues on `stream` outside a pipelined frame
   // goes through join_recon, which sets stream_dirty, and the next pipelined frame's front stages then
-  // wait for `stream` once (frame_half).
+  // wait for `stream` once (frame_half). fr_update_geometry_enqueue sets stream_dirty itself without joining the
+  // reconstruction: its kernels touch positions, tree and normals, which only the trace half reads.
   bool stream_dirty = true;
   // Frame pipelining: frame N's reconstruction (stream3 + stream2) runs while later frames trace.
   // The buffers the reconstruction reads (POSITION, NORMAL, SHADING) rotate over `nslots` frame
@@ -204,6 +215,21 @@ struct fr_ctx {
   // scene.pos (the host mirror of d_pos) is behind: positions came from device memory and were not copied
   // back. fr_scene_export refreshes it; nothing else reads it.
   bool pos_mirror_stale = false;
+  // Enqueued updates (fr_update_geometry_enqueue). geo: their record on the device (verdict, counters, the scene
+  // box), made by fr_create; h_geo: its pinned copy for fr_geometry_update_status. Once a context has enqueued an
+  // update the box lives in geo->box (dev_box points there, the saliency stage reads it; extra_box: the box an owed
+  // EXTRA's sampling launch saw, geo->box or geo->xbox) and scene.bbox_min / bbox_max may be behind
+  // (box_mirror_stale; fr_scene_export fetches it). ev_geo_read: recorded on the context
+  // stream after the last kernel that reads the caller's arrays of the last enqueued update (fr_geometry_consumed).
+  // geo_rejected_seen: the rejected counts fr_geometry_update_status last reported (total, positions, normals).
+  fr::GeoUpdateState* geo = nullptr;
+  fr::GeoUpdateState* h_geo = nullptr;
+  const float *dev_box = nullptr, *extra_box = nullptr;
+  hipEvent_t ev_geo_read = nullptr;
+  bool geo_read_pending = false;
+  bool box_mirror_stale = false;
+  unsigned long long geo_rejected_seen[3] = {};
+  int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
   // the smooth-vertex weld of the scene as fr_create built it (host), and on the device with the scratch of
   // a normal recompute (k_normals.hip); fixed for the life of the context

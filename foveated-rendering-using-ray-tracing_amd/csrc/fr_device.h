@@ -93,6 +93,17 @@ struct DevScene {
   float scene_epsilon;      // 1e-3 (FR/PathTracer.cpp:474)
 };
 
+// Device-side record of enqueued geometry updates (fr_update_geometry_enqueue), one per context.
+struct GeoUpdateState {
+  unsigned long long applied, rejected;          // updates since fr_create, by verdict
+  unsigned long long rejected_pos, rejected_nrm; // rejected ones by the array that was not finite (both may count)
+  uint32_t reject;   // verdict of the update in flight, written by k_take_over and read by every gated kernel
+                     // after it: 0 apply; bit 0 a position, bit 1 a given normal was not finite
+  uint32_t bad_nrm;  // k_check_normals' flag for that update
+  float box[6];      // the scene box (min, max) of the positions in place
+  float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
+};
+
 // Per-frame uniforms (FR/PathTracer.cpp:85-116, 774-820).
 struct FrameUniforms {
   mat4 inv_vp;              // "mvp" on the device: inverse(P*V), row-major

@@ -457,6 +457,7 @@ int fr_group_destroy(fr_group* g) {
       fr_synchronize(L.c);
       L.c->recon_gate = nullptr;
       L.c->recon_chains = 3;
+      L.c->group_refs--;
       fr_set_shard_plan(L.c, 0, 1, 128, nullptr, 0);  // the whole screen again
     }
     free_rank(L);
@@ -523,6 +524,7 @@ int fr_group_create(fr_ctx* const* ctxs, int n, void* rccl_comm, const fr_group_
     L.chains = chains_of(g, L.vrank);
     L.tiles = G > 1 ? g->tiles_per_vrank[L.vrank] : (int)ntiles;
     fr_ctx* c = L.c;
+    c->group_refs++;  // (fr_group_destroy, which also undoes a failed create, takes it back)
     hipSetDevice(c->cfg.device);
     if (G > 1) {
       if (int rc = fr_set_shard_plan(c, L.vrank, G, T, g->owner.data(), ntiles))

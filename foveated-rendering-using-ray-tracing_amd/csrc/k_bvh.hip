@@ -18,7 +18,9 @@
 //
 // Also here, for geometry that moves without regrouping: the refit of an existing four-wide tree of either
 // builder (gpu_refit_bvh: same topology, new boxes and leaf triangles), the tree's SAH cost (gpu_bvh_cost) and
-// the check of positions handed over in device memory (gpu_check_positions).
+// the check of positions handed over in device memory (gpu_check_positions). Each has an enqueue half that
+// launches and returns; an update enqueued in stream order (fr_update_geometry_enqueue) uses those alone, with
+// the refit's gated kernels and the take-over of the positions by verdict (gpu_take_over_positions).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -308,14 +310,22 @@ __global__ void k_emit_leaves(BvhNode* __restrict__ nodes, int nn, const uint32_
 // Refit: new boxes and leaf triangles for an existing four-wide tree (either builder's); child, count,
 // prim and the node order stay.
 // ---------------------------------------------------------------------------------------------
-__global__ void k_refit_tris(const f3* __restrict__ pos, const int32_t* __restrict__ prim, int n, TriGeo* __restrict__ tri) {
+// GATED (all three kernels): the form of an enqueued update (fr_update_geometry_enqueue), whose verdict is in
+// device memory. *reject (GeoUpdateState::reject, one uniform load per kernel) != 0: the update was rejected on the
+// device and the kernel writes nothing. The plain instances never read the pointer.
+template <bool GATED>
+__global__ void k_refit_tris(const f3* __restrict__ pos, const int32_t* __restrict__ prim, int n, TriGeo* __restrict__ tri,
+                             const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < n) store_tri_geo(pos, prim[j], &tri[j]);
 }
 
 // Parent links (node, not slot) from the nodes themselves, and the arrival counters back to zero.
+template <bool GATED>
 __global__ void k_refit_links(const BvhNode* __restrict__ nodes, int nn, int* __restrict__ parent,
-                              uint32_t* __restrict__ arrivals) {
+                              uint32_t* __restrict__ arrivals, const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   arrivals[i] = 0u;
@@ -335,8 +345,11 @@ FR_DEV void store_agent(f4* p, f3 v) {
 // thread that finishes a node arrives at its parent, and the last of the parent's inner children to arrive
 // (which then sees every child's raw box) goes on with the parent. nlo / nhi hold the raw (uninflated) box of
 // each node; a slot stores inflate(raw). Nobody waits: a walk that is not the last arrival ends.
+template <bool GATED>
 __global__ void k_refit_up(BvhNode* nodes, int nn, const f3* __restrict__ pos, const int32_t* __restrict__ prim,
-                           const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi) {
+                           const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi,
+                           const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   int node = i;
@@ -424,6 +437,40 @@ __global__ void k_check_positions(const float* __restrict__ xyz, size_t nverts, 
     for (int k = 0; k < 3; k++) atomicMin(&cb[k], ord(r[k]));
     for (int k = 3; k < 6; k++) atomicMax(&cb[k], ord(r[k]));
     if (any_bad) atomicOr(&cb[6], 1u);
+  }
+}
+
+// The take-over of an enqueued update (fr_update_geometry_enqueue), after both checks: one lane per vertex (12 B,
+// consecutive lanes consecutive vertices). dst (the context's spare array, which the host makes the current one
+// whatever the verdict) gets the caller's positions when the update is accepted and the current ones otherwise.
+// The verdict is cb[6] (k_check_positions) and *bad_nrm (k_check_normals; NULL: no normals were given), two
+// uniform loads. Lane 0 of block 0 publishes it for the gated kernels that follow (st->reject), counts it, and on
+// an accepted update writes the scene box from the check's result (k_check_positions' order-mapped min / max, so
+// the bytes a synchronous update reads back). flags bit 0: first enqueue of the context, the device box is seeded
+// with the host's (seed_lo / seed_hi) first; bit 1: an owed EXTRA heat map reads the box in place, which is kept
+// for it in st->xbox before the new one lands.
+__global__ void k_take_over(const f3* __restrict__ xyz, const f3* __restrict__ cur, size_t nverts, f3* __restrict__ dst,
+                            const uint32_t* __restrict__ cb, const uint32_t* __restrict__ bad_nrm,
+                            GeoUpdateState* __restrict__ st, int flags, f3 seed_lo, f3 seed_hi) {
+  const uint32_t rej = (cb[6] ? 1u : 0u) | (bad_nrm && *bad_nrm ? 2u : 0u);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nverts) dst[i] = rej ? cur[i] : xyz[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (flags & 1) {
+      st->box[0] = seed_lo.x; st->box[1] = seed_lo.y; st->box[2] = seed_lo.z;
+      st->box[3] = seed_hi.x; st->box[4] = seed_hi.y; st->box[5] = seed_hi.z;
+    }
+    if (flags & 2)
+      for (int k = 0; k < 6; k++) st->xbox[k] = st->box[k];
+    st->reject = rej;
+    if (rej) {
+      st->rejected++;
+      if (rej & 1u) st->rejected_pos++;
+      if (rej & 2u) st->rejected_nrm++;
+    } else {
+      st->applied++;
+      for (int k = 0; k < 6; k++) st->box[k] = unord(cb[k]);
+    }
   }
 }
 
@@ -605,21 +652,36 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
 // and tri[j] for every leaf-order j are rewritten, child / count / prim are not. num_nodes == 0 (the whole scene
 // is one leaf): tri only. Three launches whatever the depth, no allocation; the scratch is *work's nlo / nhi
 // (raw node boxes), parent and arrivals, which hold one entry per triangle (a tree has at most as many nodes).
-bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
-                   hipStream_t s, std::string& err) {
+// gpu_refit_bvh_enqueue launches them and returns (reject: NULL, or the device verdict word of an enqueued update,
+// which selects the gated kernels); gpu_refit_bvh also waits for them.
+bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
+                           const int32_t* prim, const uint32_t* reject, hipStream_t s, std::string& err) {
   if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
     err = "GPU BVH refit: no workspace for this tree";
     return false;
   }
   BvhWork& w = *work;
   const int B = 256;
-  hipLaunchKernelGGL(k_refit_tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, prim, n, tri);
+  auto tris = reject ? k_refit_tris<true> : k_refit_tris<false>;
+  auto links = reject ? k_refit_links<true> : k_refit_links<false>;
+  auto up = reject ? k_refit_up<true> : k_refit_up<false>;
+  hipLaunchKernelGGL(tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, prim, n, tri, reject);
   if (num_nodes > 0) {
     const int GN = (num_nodes + B - 1) / B;
-    hipLaunchKernelGGL(k_refit_links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals);
-    hipLaunchKernelGGL(k_refit_up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo,
-                       w.nhi);
+    hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals, reject);
+    hipLaunchKernelGGL(up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo, w.nhi,
+                       reject);
   }
+  if (hipGetLastError() != hipSuccess) {
+    err = "GPU BVH refit: launch failure";
+    return false;
+  }
+  return true;
+}
+
+bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
+                   hipStream_t s, std::string& err) {
+  if (!gpu_refit_bvh_enqueue(work, pos, n, nodes, num_nodes, tri, prim, nullptr, s, err)) return false;
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: kernel failure";
     return false;
@@ -654,8 +716,9 @@ bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cos
 
 // Checks n triangles of device positions (any device pointer the caller owns) in one pass: *finite, and
 // box[0..2] = min, box[3..5] = max over all vertices. One kernel, one small copy back.
-bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, float box[6], hipStream_t s,
-                         std::string& err) {
+// gpu_check_positions_enqueue launches the check and leaves its result on the device (the workspace's cb words,
+// which k_take_over reads); gpu_check_positions also copies it back and waits.
+bool gpu_check_positions_enqueue(BvhWork* work, const float* xyz, int n, hipStream_t s, std::string& err) {
   if (!work || n < 1) { err = "GPU position check: no workspace"; return false; }
   BvhWork& w = *work;
   hipLaunchKernelGGL(k_build_init, dim3(1), dim3(64), 0, s, w.cb, w.qa, w.ctr);
@@ -663,6 +726,27 @@ bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, f
   const size_t nverts = (size_t)n * 3;
   const int G = (int)std::min<size_t>((nverts + B - 1) / B, 2048);
   hipLaunchKernelGGL(k_check_positions, dim3(G), dim3(B), 0, s, xyz, nverts, w.cb);
+  if (hipGetLastError() != hipSuccess) { err = "GPU position check: launch failure"; return false; }
+  return true;
+}
+
+// The take-over of an enqueued update (k_take_over), after gpu_check_positions_enqueue and, with given normals,
+// the normals check into st->bad_nrm (bad_nrm then, else NULL). No wait.
+bool gpu_take_over_positions(BvhWork* work, const f3* xyz, const f3* cur, int n, f3* dst, const uint32_t* bad_nrm,
+                             GeoUpdateState* st, int flags, f3 seed_lo, f3 seed_hi, hipStream_t s, std::string& err) {
+  if (!work || n < 1) { err = "GPU position take-over: no workspace"; return false; }
+  const int B = 256;
+  const size_t nverts = (size_t)n * 3;
+  hipLaunchKernelGGL(k_take_over, dim3((unsigned)((nverts + B - 1) / B)), dim3(B), 0, s, xyz, cur, nverts, dst,
+                     work->cb, bad_nrm, st, flags, seed_lo, seed_hi);
+  if (hipGetLastError() != hipSuccess) { err = "GPU position take-over: launch failure"; return false; }
+  return true;
+}
+
+bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, float box[6], hipStream_t s,
+                         std::string& err) {
+  if (!gpu_check_positions_enqueue(work, xyz, n, s, err)) return false;
+  BvhWork& w = *work;
   hipMemcpyAsync(w.host, w.cb, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU position check: kernel failure (is the pointer device memory of ntris x 9 floats?)";

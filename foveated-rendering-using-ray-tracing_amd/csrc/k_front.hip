@@ -99,9 +99,13 @@ FR_DEV void publish_ballots(bool on, int cls, unsigned long long* __restrict__ w
 // gx, gy; gradient(), shared_helper_funcs.h) are one per lane of wave 0, with all nine taps of a lane requested at once; wave 1
 // evaluates the per-cell rest. (One lane evaluating a whole cell serialised 36 tap loads.)
 // Called by all 256 threads of the block (two barriers); cellf / cellg are the block's LDS.
-FR_DEV void saliency_cells(const FrameUniforms& U, const DevScene& sc, const f4* __restrict__ diffuse,
-                           const f4* __restrict__ normal, const f4* __restrict__ depth, float (&cellf)[16][8],
-                           float (&cellg)[4][16]) {
+// DEVBOX: the scene box comes from device memory (dev_box: min, max; GeoUpdateState::box or ::xbox), where an
+// enqueued geometry update (fr_update_geometry_enqueue) leaves it and the host no longer knows it; else from
+// sc.bbox_min / bbox_max as the host passed them (dev_box is not read). Same bytes either way.
+template <bool DEVBOX>
+FR_DEV void saliency_cells(const FrameUniforms& U, const DevScene& sc, const float* __restrict__ dev_box,
+                           const f4* __restrict__ diffuse, const f4* __restrict__ normal,
+                           const f4* __restrict__ depth, float (&cellf)[16][8], float (&cellg)[4][16]) {
   const int W = U.width, H = U.height;
   const f2 screenf = U.screen;
   if (threadIdx.x < 64) {
@@ -138,7 +142,9 @@ FR_DEV void saliency_cells(const FrameUniforms& U, const DevScene& sc, const f4*
       // reference's; the clamp to the last row / column is ours (a cursor on the window's top edge
       // gives gaze.y = H, off-window cursors give any value; the reference reads out of bounds)
       const uint32_t gzx = min(f2u_sat(U.gaze.x), (uint32_t)W - 1), gzy = min(f2u_sat(U.gaze.y), (uint32_t)H - 1);
-      float theta = lengthc(sc.bbox_max - sc.bbox_min) * 0.005f;  // samplingStep.ptx:785-795
+      const f3 bmin = DEVBOX ? mk3(dev_box[0], dev_box[1], dev_box[2]) : sc.bbox_min;
+      const f3 bmax = DEVBOX ? mk3(dev_box[3], dev_box[4], dev_box[5]) : sc.bbox_max;
+      float theta = lengthc(bmax - bmin) * 0.005f;  // samplingStep.ptx:785-795
       float focal = depth[(size_t)gzy * W + gzx].x;
       float dep = depth[(size_t)sy * W + sx].x - focal;
       float dep2 = dep * dep;
@@ -186,7 +192,8 @@ FR_DEV f4 heat_map(float saliency) {
 // LOCAL: a tile-local front (fr_set_front_local); the whole-screen instance carries none of it.
 // MOTION: this frame's G-buffer ran its motion form (fr_set_motion_reprojection): WEIGHT.z holds the distance of the
 // reprojected point, where it was a frame ago, from the previous eye, and the history depth is tested against that.
-template <bool LOCAL, bool MOTION>
+// DEVBOX: saliency_cells' (a context that has enqueued a geometry update).
+template <bool LOCAL, bool MOTION, bool DEVBOX>
 __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, const f4* __restrict__ position,
                                                   const f4* __restrict__ depth, const f4* __restrict__ depth_cache,
                                                   f4* __restrict__ weight, const f4* __restrict__ normal,
@@ -194,7 +201,8 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
                                                   uint8_t* __restrict__ mask, const uint8_t* __restrict__ gclass,
                                                   unsigned long long* __restrict__ words, uint32_t* __restrict__ counts,
                                                   int write_extra, const uint8_t* __restrict__ lp_cache,
-                                                  uint32_t* __restrict__ bcount) {
+                                                  uint32_t* __restrict__ bcount,
+                                                  const float* __restrict__ dev_box) {
   const int W = U.width, H = U.height;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int x = blockIdx.x * 16 + (lane & 15);
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
   const bool saliency_used = U.mask_mode == MASK_SALIENCY || write_extra;
   __shared__ float cellf[16][8];
   __shared__ float cellg[4][16];
-  if (saliency_used) saliency_cells(U, sc, diffuse, normal, depth, cellf, cellg);
+  if (saliency_used) saliency_cells<DEVBOX>(U, sc, dev_box, diffuse, normal, depth, cellf, cellg);
   bool usingRay = false, unfolded = false;
   int cls = 3;
   if (x < W && y < H) {
@@ -270,15 +278,17 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
 // The heat map a k_sampling launch left unwritten (context.cpp, materialize_extra_now): the same cell phase and
 // per-pixel expressions over that launch's inputs (its uniforms, DIFFUSE, NORMAL, DEPTH and WEIGHT.xy, which
 // the sampling does not change), so EXTRA is what that launch would have stored, bit for bit.
+template <bool DEVBOX>
 __global__ __launch_bounds__(256) void k_extra(FrameUniforms U, DevScene sc, const f4* __restrict__ depth,
                                                const f4* __restrict__ weight, const f4* __restrict__ normal,
-                                               const f4* __restrict__ diffuse, f4* __restrict__ extra) {
+                                               const f4* __restrict__ diffuse, f4* __restrict__ extra,
+                                               const float* __restrict__ dev_box) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int x = blockIdx.x * 16 + (lane & 15);
   const int y = blockIdx.y * 16 + wv * 4 + (lane >> 4);
   __shared__ float cellf[16][8];
   __shared__ float cellg[4][16];
-  saliency_cells(U, sc, diffuse, normal, depth, cellf, cellg);
+  saliency_cells<DEVBOX>(U, sc, dev_box, diffuse, normal, depth, cellf, cellg);
   if (x < U.width && y < U.height) {
     const size_t p = (size_t)y * U.width + x;
     const f4 wgt = weight[p];
@@ -287,9 +297,10 @@ __global__ __launch_bounds__(256) void k_extra(FrameUniforms U, DevScene sc, con
 }
 
 void launch_extra(const FrameUniforms& U, const DevScene& sc, const f4* depth, const f4* weight, const f4* normal,
-                  const f4* diffuse, f4* extra, hipStream_t stream) {
+                  const f4* diffuse, f4* extra, const float* dev_box, hipStream_t stream) {
   dim3 grid((U.width + 15) / 16, (U.height + 15) / 16);
-  hipLaunchKernelGGL(k_extra, grid, dim3(256), 0, stream, U, sc, depth, weight, normal, diffuse, extra);
+  auto k = dev_box ? k_extra<true> : k_extra<false>;
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, U, sc, depth, weight, normal, diffuse, extra, dev_box);
 }
 
 // Per-owner sums of the unfolded block counts (one block; owners < FR_MAX_SHARD_RANKS).
@@ -381,7 +392,7 @@ void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* posit
                      const f4* depth_cache, f4* weight, const f4* normal, const f4* diffuse, f4* extra, uint8_t* mask,
                      const uint8_t* gclass, unsigned long long* words, uint32_t* counts, int write_extra,
                      uint8_t* lp_cache, uint32_t* lp_inv, bool lp_refresh, uint32_t* bcount, bool motion,
-                     hipStream_t stream) {
+                     const float* dev_box, hipStream_t stream) {
   if (lp_refresh) {
     const size_t N = (size_t)U.width * U.height;
     const float lpL = log_polar_L(U.gaze, U.screen * 0.25f);
@@ -393,10 +404,14 @@ void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* posit
                        stream, U, lpL, nu, inv, lp_cache);
   }
   dim3 grid((U.width + 15) / 16, (U.height + 15) / 16);
-  auto k = U.front_need ? (motion ? k_sampling<true, true> : k_sampling<true, false>)
-                        : (motion ? k_sampling<false, true> : k_sampling<false, false>);
+  auto pick = [&](auto local) {
+    constexpr bool L = decltype(local)::value;
+    return dev_box ? (motion ? k_sampling<L, true, true> : k_sampling<L, false, true>)
+                      : (motion ? k_sampling<L, true, false> : k_sampling<L, false, false>);
+  };
+  auto k = U.front_need ? pick(std::true_type{}) : pick(std::false_type{});
   hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, U, sc, position, depth, depth_cache, weight, normal, diffuse, extra,
-                     mask, gclass, words, counts, write_extra, lp_cache, bcount);
+                     mask, gclass, words, counts, write_extra, lp_cache, bcount, dev_box);
 }
 
 // ------------------------------------------------------------------------------------------

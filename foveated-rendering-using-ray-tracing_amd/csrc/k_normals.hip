@@ -27,7 +27,13 @@ constexpr int kBlock = 256;
 
 FR_DEV bool normalisable(float d) { return d >= FLT_MIN && d < INFINITY; }
 
-__global__ void k_face_cross(const f3* __restrict__ pos, int nt, f3* __restrict__ face) {
+// GATED (every kernel that writes): the form of an enqueued update (fr_update_geometry_enqueue). *reject
+// (GeoUpdateState::reject, one uniform load per kernel) != 0: the update was rejected on the device and the kernel
+// writes nothing. The plain instances never read the pointer.
+template <bool GATED>
+__global__ void k_face_cross(const f3* __restrict__ pos, int nt, f3* __restrict__ face,
+                             const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nt) return;
   const f3 p0 = pos[3 * t], p1 = pos[3 * t + 1], p2 = pos[3 * t + 2];
@@ -35,8 +41,11 @@ __global__ void k_face_cross(const f3* __restrict__ pos, int nt, f3* __restrict_
 }
 
 // vnrm[v] = (normal, 1), or (0, 0, 0, 0): the corners of v fall back on their own triangles.
+template <bool GATED>
 __global__ void k_vertex_normals(const int32_t* __restrict__ off, const int32_t* __restrict__ corners, int nv,
-                                 const f3* __restrict__ face, f4* __restrict__ vnrm) {
+                                 const f3* __restrict__ face, f4* __restrict__ vnrm,
+                                 const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= nv) return;
   f3 acc = mk3(0.0f);
@@ -51,8 +60,11 @@ FR_DEV void store_xyz(f4* dst, f3 n) {
   dst->z = n.z;
 }
 
+template <bool GATED>
 __global__ void k_scatter_recomputed(const int32_t* __restrict__ corner_vertex, int nt, const f4* __restrict__ vnrm,
-                                     const f3* __restrict__ face, TriShade* __restrict__ shade) {
+                                     const f3* __restrict__ face, TriShade* __restrict__ shade,
+                                     const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nt) return;
   f4* const dst[3] = {&shade[t].n0, &shade[t].n1, &shade[t].n2};
@@ -77,8 +89,10 @@ __global__ void k_check_normals(const float* __restrict__ nrm, const int32_t* __
   if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
 }
 
+template <bool GATED>
 __global__ void k_scatter_given(const int32_t* __restrict__ corner_vertex, int nt, const float* __restrict__ nrm,
-                                TriShade* __restrict__ shade) {
+                                TriShade* __restrict__ shade, const uint32_t* __restrict__ reject) {
+  if (GATED && *reject) return;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nt) return;
   f4* const dst[3] = {&shade[t].n0, &shade[t].n1, &shade[t].n2};
@@ -157,26 +171,51 @@ static bool finish(hipStream_t s, const char* what, std::string& err) {
   return true;
 }
 
-// The rule above over pos (3 vertices per triangle, device) into shade's normals. Waits for its kernels.
-bool gpu_recompute_normals(NormalsWork* w, const f3* pos, TriShade* shade, hipStream_t s, std::string& err) {
-  if (!w) { err = "normals: no workspace"; return false; }
-  if (w->nv > 0) {
-    hipLaunchKernelGGL(k_face_cross, dim3(blocks(w->nt)), dim3(kBlock), 0, s, pos, w->nt, w->face);
-    hipLaunchKernelGGL(k_vertex_normals, dim3(blocks(w->nv)), dim3(kBlock), 0, s, w->off, w->corners, w->nv, w->face,
-                       w->vnrm);
-    hipLaunchKernelGGL(k_scatter_recomputed, dim3(blocks(w->nt)), dim3(kBlock), 0, s, w->corner_vertex, w->nt, w->vnrm,
-                       w->face, shade);
+static bool launched(const char* what, std::string& err) {
+  if (hipGetLastError() != hipSuccess) {
+    err = std::string(what) + ": launch failure";
+    return false;
   }
-  return finish(s, "normals recompute", err);
+  return true;
 }
 
-// *finite: every float of nrm (device, 9 per triangle) on a corner that has a vertex is finite.
-bool gpu_check_normals(NormalsWork* w, const float* nrm, bool* finite, hipStream_t s, std::string& err) {
+// Each of the three calls below has an enqueue half, which launches and returns, and the call itself, which also
+// waits. reject: NULL, or the device verdict word of an enqueued update (the gated kernels).
+
+// The rule above over pos (3 vertices per triangle, device) into shade's normals.
+bool gpu_recompute_normals_enqueue(NormalsWork* w, const f3* pos, TriShade* shade, const uint32_t* reject, hipStream_t s,
+                                   std::string& err) {
   if (!w) { err = "normals: no workspace"; return false; }
+  if (w->nv > 0) {
+    auto fc = reject ? k_face_cross<true> : k_face_cross<false>;
+    auto vn = reject ? k_vertex_normals<true> : k_vertex_normals<false>;
+    auto sr = reject ? k_scatter_recomputed<true> : k_scatter_recomputed<false>;
+    hipLaunchKernelGGL(fc, dim3(blocks(w->nt)), dim3(kBlock), 0, s, pos, w->nt, w->face, reject);
+    hipLaunchKernelGGL(vn, dim3(blocks(w->nv)), dim3(kBlock), 0, s, w->off, w->corners, w->nv, w->face, w->vnrm, reject);
+    hipLaunchKernelGGL(sr, dim3(blocks(w->nt)), dim3(kBlock), 0, s, w->corner_vertex, w->nt, w->vnrm, w->face, shade,
+                       reject);
+  }
+  return launched("normals recompute", err);
+}
+
+bool gpu_recompute_normals(NormalsWork* w, const f3* pos, TriShade* shade, hipStream_t s, std::string& err) {
+  return gpu_recompute_normals_enqueue(w, pos, shade, nullptr, s, err) && finish(s, "normals recompute", err);
+}
+
+// Every float of nrm (device, 9 per triangle) on a corner that has a vertex is finite: *flag (device; NULL: the
+// workspace's own word, which gpu_check_normals reads back) stays 0.
+bool gpu_check_normals_enqueue(NormalsWork* w, const float* nrm, uint32_t* flag, hipStream_t s, std::string& err) {
+  if (!w) { err = "normals: no workspace"; return false; }
+  if (!flag) flag = w->bad;
   const size_t nc = 3 * (size_t)w->nt;
-  hipMemsetAsync(w->bad, 0, sizeof(uint32_t), s);
+  hipMemsetAsync(flag, 0, sizeof(uint32_t), s);
   hipLaunchKernelGGL(k_check_normals, dim3(blocks(nc) < 2048 ? blocks(nc) : 2048), dim3(kBlock), 0, s, nrm,
-                     w->corner_vertex, nc, w->bad);
+                     w->corner_vertex, nc, flag);
+  return launched("normals check", err);
+}
+
+bool gpu_check_normals(NormalsWork* w, const float* nrm, bool* finite, hipStream_t s, std::string& err) {
+  if (!gpu_check_normals_enqueue(w, nrm, nullptr, s, err)) return false;
   hipMemcpyAsync(w->host, w->bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   if (!finish(s, "normals check", err)) {
     err += " (is the pointer device memory of ntris x 9 floats?)";
@@ -186,12 +225,19 @@ bool gpu_check_normals(NormalsWork* w, const float* nrm, bool* finite, hipStream
   return true;
 }
 
-// nrm (device, 9 floats per triangle) into shade's normals, on the corners that have a vertex. Waits.
-bool gpu_scatter_normals(NormalsWork* w, const float* nrm, TriShade* shade, hipStream_t s, std::string& err) {
+// nrm (device, 9 floats per triangle) into shade's normals, on the corners that have a vertex.
+bool gpu_scatter_normals_enqueue(NormalsWork* w, const float* nrm, TriShade* shade, const uint32_t* reject, hipStream_t s,
+                                 std::string& err) {
   if (!w) { err = "normals: no workspace"; return false; }
-  if (w->nv > 0)
-    hipLaunchKernelGGL(k_scatter_given, dim3(blocks(w->nt)), dim3(kBlock), 0, s, w->corner_vertex, w->nt, nrm, shade);
-  return finish(s, "normals scatter", err);
+  if (w->nv > 0) {
+    auto sg = reject ? k_scatter_given<true> : k_scatter_given<false>;
+    hipLaunchKernelGGL(sg, dim3(blocks(w->nt)), dim3(kBlock), 0, s, w->corner_vertex, w->nt, nrm, shade, reject);
+  }
+  return launched("normals scatter", err);
+}
+
+bool gpu_scatter_normals(NormalsWork* w, const float* nrm, TriShade* shade, hipStream_t s, std::string& err) {
+  return gpu_scatter_normals_enqueue(w, nrm, shade, nullptr, s, err) && finish(s, "normals scatter", err);
 }
 
 }  // namespace fr

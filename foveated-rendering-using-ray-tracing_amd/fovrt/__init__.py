@@ -178,6 +178,9 @@ _SIGS = {
     "fr_update_positions": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int],
     "fr_bvh_sah_cost": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_update_geometry": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int],
+    "fr_update_geometry_enqueue": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
+    "fr_geometry_consumed": [C.c_void_p, C.c_void_p],
+    "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -403,6 +406,10 @@ class PathTracer:
     def _check(self, rc):
         if rc:
             raise FovrtError(rc, _lib.fr_last_error(self._ctx).decode())
+
+    def last_error(self) -> str:
+        """fr_last_error: the message of this context's last failure (or of the last rejected enqueued update)."""
+        return _lib.fr_last_error(self._ctx).decode()
 
     @property
     def width(self):
@@ -646,6 +653,43 @@ class PathTracer:
         else:
             self._check(_lib.fr_update_geometry(self._ctx, C.c_void_p(device_ptr), nrm, int(ntris), FR_MEM_DEVICE,
                                                 self._update_kind(update), kind))
+
+    @staticmethod
+    def _device_ptr(x):
+        """A device pointer (int), or an object with data_ptr() (a torch tensor); None stays None."""
+        if x is None:
+            return None
+        return C.c_void_p(int(x.data_ptr() if hasattr(x, "data_ptr") else x))
+
+    def update_geometry_enqueue(self, xyz, ntris=None, normals="keep", ready_event=None):
+        """fr_update_geometry_enqueue: set_positions_device(update="refit") in stream order, without waiting for
+        the GPU. xyz: a device pointer or an object with data_ptr() (ntris x 9 float32 on this context's device;
+        ntris defaults to its numel() // 9). normals: "keep", "recompute", or the normals as xyz (a pointer or a
+        tensor). ready_event: a torch event (its cuda_event) or a raw hipEvent_t recorded after the arrays were
+        produced. A bad array is rejected on the device: geometry_update_status(). Keep the arrays untouched until
+        geometry_consumed() has ordered your stream behind the update's reads."""
+        if ntris is None:
+            ntris = xyz.numel() // 9
+        if isinstance(normals, (str, int)):
+            kind, nrm = self._normals_kind(normals), None
+        else:
+            kind, nrm = FR_NORMALS_GIVEN, self._device_ptr(normals)
+        ev = getattr(ready_event, "cuda_event", ready_event)
+        self._check(_lib.fr_update_geometry_enqueue(self._ctx, self._device_ptr(xyz), nrm, int(ntris), kind,
+                                                    C.c_void_p(int(ev)) if ev else None))
+
+    def geometry_consumed(self, stream=None):
+        """fr_geometry_consumed: `stream` (a torch stream, a raw hipStream_t, or None for the null stream) waits on
+        the device for the last enqueued update's reads of the caller's arrays. Does not block the host."""
+        s = getattr(stream, "cuda_stream", stream)
+        self._check(_lib.fr_geometry_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
+
+    def geometry_update_status(self):
+        """(applied, rejected): enqueued updates by their verdict on the device since the context was created.
+        Waits for the context's pending work; after a new rejection last_error() names the array."""
+        a, r = C.c_uint64(), C.c_uint64()
+        self._check(_lib.fr_geometry_update_status(self._ctx, C.byref(a), C.byref(r)))
+        return a.value, r.value
 
     def set_normals(self, nrm: np.ndarray):
         """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have

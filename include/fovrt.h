@@ -399,9 +399,9 @@ int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
  *   1 + (sum over non-empty slots of area(slot box) * (1 for an inner slot | triangles of a leaf slot))
  *       / area(union of the root's slot boxes)
  * so a caller can compare a refitted tree with the same tree when it was built and rebuild when it has grown.
- * Not covered: an update without host synchronisation (these calls wait for the context's pending work and
- * for their own kernels); groups (each rank's context is updated by its caller). Shading normals are kept by
- * these calls; fr_update_geometry below moves them with the positions. */
+ * These calls wait for the context's pending work and for their own kernels (fr_update_geometry_enqueue below
+ * is the update without host synchronisation). Not covered: groups (each rank's context is updated by its
+ * caller). Shading normals are kept by these calls; fr_update_geometry below moves them with the positions. */
 #define FR_BVH_REBUILD 0
 #define FR_BVH_REFIT   1
 #define FR_MEM_HOST    0
@@ -437,6 +437,46 @@ int fr_update_geometry(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntr
 int fr_set_normals(fr_ctx* ctx, const void* nrm, size_t ntris, int where);
 int fr_recompute_normals(fr_ctx* ctx, float* ms);
 int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* nverts);
+/* fr_update_geometry (device memory, refit) without host synchronisation: a caller who deforms the mesh before
+ * every frame keeps the frame pipeline full. xyz is device memory the context's device can read, 9 floats per
+ * triangle; nrm the same kind of array, required for FR_NORMALS_GIVEN and ignored otherwise. The tree is always
+ * refitted (FR_BVH_REFIT; a rebuild keeps its synchronous call). The update is enqueued on the context stream
+ * after the work already there and the call returns without waiting for the GPU: it synchronises no stream and no
+ * event, copies nothing to the host and allocates nothing (what it needs is made by fr_create).
+ * ready_event: a hipEvent_t the caller recorded after producing the arrays (the update's first read waits for it
+ * on the device), or NULL when the arrays are already complete. The arrays must stay untouched until the update
+ * has read them: fr_geometry_consumed(ctx, stream) makes `stream` (a hipStream_t; 0 = the null stream) wait, on
+ * the device, for the last enqueued update's reads of the caller's arrays (an event recorded after the last kernel
+ * that reads them), so work submitted to that stream afterwards may overwrite them. It does not block the host;
+ * with no update enqueued it does nothing.
+ * Rejected at once, with nothing enqueued: a NULL context (FR_E_INVALID); NULL xyz, a wrong triangle count, a
+ * bad `normals` value, FR_NORMALS_GIVEN with nrm NULL (FR_E_INVALID, fr_last_error); a context that is a rank of a
+ * group or has a shard plan of more than one rank (FR_E_UNSUPPORTED: groups stay "each rank's context is updated
+ * by its caller", through the synchronous calls).
+ * Checked on the device: the finiteness checks of fr_update_geometry run first, and everything of the update that
+ * writes scene state reads their verdict from device memory: the taken-over positions, the leaf triangles, every
+ * slot box, the normals and the scene box. An update with a position that is not finite, or with a given normal
+ * that is not finite on a triangle that has normals, writes none of it: positions, tree, normals, scene box and
+ * every later frame are as if the call had not been made, bit for bit (given normals of triangles without normals
+ * are ignored, as above). Counters on the device record each verdict: fr_geometry_update_status waits for the
+ * context's pending work, as fr_synchronize does, and returns how many enqueued updates were applied and how many
+ * rejected since fr_create (either pointer may be NULL); when the rejected count grew since its last call,
+ * fr_last_error says which array was not finite.
+ * An accepted update equals the synchronous fr_update_geometry(xyz, nrm, ntris, FR_MEM_DEVICE, FR_BVH_REFIT,
+ * normals) in every byte of positions, tree, normals and scene box and in every later frame. It counts as a
+ * position update for fr_set_motion_reprojection (of several updates before one G-buffer the positions that
+ * G-buffer traced are kept; after a rejected update prev equals cur and the frame is the plain one). The scene
+ * box (the depth term of the saliency mask) stays in device memory from a context's first enqueued update on;
+ * fr_scene_export fetches it, with positions and normals, when asked. The next pipelined frame's front stages
+ * start after the update, so they no longer overlap the previous frame's path trace (the tree is refitted in
+ * place). Synchronous updates, fr_refit_bvh, fr_set_normals, fr_recompute_normals, fr_snapshot and fr_restore
+ * keep their behaviour after enqueued updates (they wait for pending work as always).
+ * Not covered: groups and sharded contexts, a rebuild without synchronisation, host-memory arrays, a second tree
+ * that would let the front stages overlap the previous path trace again. */
+int fr_update_geometry_enqueue(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntris, int normals,
+                               void* ready_event);
+int fr_geometry_consumed(fr_ctx* ctx, void* stream);
+int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected);
 /* History that follows moving geometry (off by default). The G-buffer reprojects a hit point with the previous
  * camera, and the sampling stage accepts the history there only when the depth stored a frame ago equals the
  * point's distance from the previous eye: both assume the point stood still. With motion reprojection on, the

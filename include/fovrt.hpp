@@ -176,6 +176,20 @@ class PathTracer {
   void update_geometry(const void* xyz, const void* nrm, size_t ntris, int where, int how, int normals) {
     check(fr_update_geometry(ctx(), xyz, nrm, ntris, where, how, normals), ctx_, "update_geometry");
   }
+  // update_geometry (device arrays, refit) in stream order, without waiting for the GPU. ready_event: a hipEvent_t
+  // recorded after the arrays were produced, or nullptr; a bad array is rejected on the device
+  // (geometry_update_status). The arrays stay untouched until geometry_consumed has ordered a stream behind the
+  // update's reads of them.
+  void update_geometry_enqueue(const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event = nullptr) {
+    check(fr_update_geometry_enqueue(ctx(), xyz, nrm, ntris, normals, ready_event), ctx_, "update_geometry_enqueue");
+  }
+  void geometry_consumed(void* stream = nullptr) {  // stream: a hipStream_t (nullptr: the null stream); no host wait
+    check(fr_geometry_consumed(ctx(), stream), ctx_, "geometry_consumed");
+  }
+  // enqueued updates applied / rejected on the device since the context was created (waits for pending work)
+  void geometry_update_status(uint64_t* applied, uint64_t* rejected) {
+    check(fr_geometry_update_status(ctx(), applied, rejected), ctx_, "geometry_update_status");
+  }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
