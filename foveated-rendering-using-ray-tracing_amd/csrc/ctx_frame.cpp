@@ -1,0 +1,656 @@
+// ctx_frame.cpp — what a frame enqueues: the four stage enqueues, the reconstruction enqueues, the frame driver
+// (frame_half) with its latency schedule, and the stage-call entry points over them. Everything frame_half calls
+// per frame is defined here, in one translation unit: other files reach it through fri::.
+#include <immintrin.h>
+#include <sched.h>
+
+#include <chrono>
+#include <cmath>
+#include <functional>
+
+#include "ctx_internal.h"
+
+using namespace fr;
+using namespace fri;
+
+namespace {
+// Host-side waits of the latency mode poll (a blocking wait woke the host up to milliseconds late). The spin
+// pauses between queries, yields the core every 64 polls (RCCL proxy threads or other ranks' host threads may
+// share it), and gives up after a deadline instead of spinning forever on an event that never completes.
+constexpr float kPollDeadlineMs = 10000.0f;
+inline void cpu_relax() { _mm_pause(); }
+hipError_t poll_event(hipEvent_t ev, float deadline_ms) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t n = 1;; n++) {
+    const hipError_t e = hipEventQuery(ev);
+    if (e != hipErrorNotReady) return e;
+    if ((n & 63u) == 0) {
+      if (std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() > deadline_ms)
+        return hipErrorNotReady;
+      sched_yield();
+    } else {
+      cpu_relax();
+    }
+  }
+}
+float elapsed(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.0f;
+  hipEventElapsedTime(&ms, a, b);
+  return ms;
+}
+int slotted(const fr_ctx* c, int p0, int pb) { return c->slot == 0 ? p0 : pb + 4 * (c->slot - 1); }
+int P_nrm(const fr_ctx* c) { return slotted(c, P_NORMAL, P_NORMAL_B); }
+}  // namespace
+
+namespace fri {
+int P_pos(const fr_ctx* c) { return slotted(c, P_POSITION, P_POSITION_B); }
+int P_shd(const fr_ctx* c) { return slotted(c, P_SHADING, P_SHADING_B); }
+int P_wgt(const fr_ctx* c) { return slotted(c, P_WEIGHT, P_WEIGHT_B); }
+
+int check_launch(fr_ctx* c) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(c, FR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return FR_OK;
+}
+
+// Sums the elapsed times of ring slot i (its last event is synchronised first).
+void kt_harvest(fr_ctx* c, int i) {
+  hipEventSynchronize(c->kt_ev[i][3]);
+  c->kt_stage_ms += elapsed(c->kt_ev[i][0], c->kt_ev[i][3]);
+  c->kt_kernel_ms += elapsed(c->kt_ev[i][1], c->kt_ev[i][2]);
+  c->kt_frames++;
+}
+
+// One frame of the frame clock (fr_frame_clock): its latency, and its interval after the previous frame.
+void fc_harvest(fr_ctx* c, int i) {
+  hipEventSynchronize(c->fc_ev[i][1]);
+  const float s = elapsed(c->fc_ref, c->fc_ev[i][0]), e = elapsed(c->fc_ref, c->fc_ev[i][1]);
+  c->fc_latency.push_back(e - s);
+  if (c->fc_prev_end >= 0.0) c->fc_interval.push_back((float)(e - c->fc_prev_end));
+  c->fc_prev_end = e;
+}
+
+void join_recon(fr_ctx* c) {
+  c->stream_dirty = true;  // the caller is about to enqueue on `stream` outside a pipelined frame
+  for (int k = 0; k < fr_ctx::MAX_SLOTS; k++)
+    if (c->recon_pending[k]) { hipStreamWaitEvent(c->stream, c->ev_recon[k], 0); c->recon_pending[k] = false; }
+  if (c->front_pending) { hipStreamWaitEvent(c->stream, c->ev_front, 0); c->front_pending = false; }
+}
+
+int quiesce(fr_ctx* c) {
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FR_OK;
+}
+}  // namespace fri
+
+// fs: the stream of the front stages (entries 0-2): `stream`, or stream5 in a pipelined frame.
+static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
+  // a new frame: move to the next slot, once the reconstruction that read it has finished
+  c->slot = (c->slot + 1) % c->nslots;
+  c->setup_early = false;
+  const int sl = c->slot;
+  c->mask = c->mask_p[sl]; c->active = c->active_p[sl]; c->ray_count = c->ray_count_p[sl];
+  if (c->recon_pending[sl]) {
+    hipStreamWaitEvent(fs, c->ev_recon[sl], 0);  // entry 3 on `stream` waits for fs (ev_front)
+    c->recon_pending[sl] = false;
+  }
+  if (fs != c->stream && c->trace_pending[sl]) {
+    hipStreamWaitEvent(fs, c->ev_trace[sl], 0);
+    c->trace_pending[sl] = false;
+  }
+  if (c->lat_arm) hipEventRecord(c->lat_ev[sl][0], fs);
+  if (c->fc_arm) {  // fr_frame_clock: where this frame's G-buffer (the first stage to read the gaze) may start
+    const int i = c->fc_next;
+    if (c->fc_pending == fr_ctx::FC_RING) { fc_harvest(c, i); c->fc_pending--; }
+    c->fc_cur = i;
+    c->fc_next = (i + 1) % fr_ctx::FC_RING;
+    c->fc_pending++;
+    hipEventRecord(c->fc_ev[i][0], fs);
+  }
+  // frame = m_accumFrame++ ; a light change resets the counter afterwards (FR/PathTracer.cpp:99-116)
+  c->U.frame = c->accum++;
+  if (c->light_pending) { c->light_pending = false; c->accum = 0; }
+  if (c->U.frame < 1) {  // d_buffer_init (g_buffer_trace_camera.cu:73-82)
+    const size_t bytes = (size_t)c->W * c->H * sizeof(f4);
+    hipMemsetAsync(c->img[c->hist_cur], 0, bytes, c->stream);
+    hipMemsetAsync(c->img[c->hist_cache], 0, bytes, c->stream);
+  }
+  if (c->front_local) {  // the primaries this G-buffer traces: the needed tiles and the gaze pixel's
+    const int t8 = gaze_tile8(c->U);
+    const int tx8 = (c->W + 7) / 8;
+    const uint32_t gw = (uint32_t)std::min(8, c->W - (t8 % tx8) * 8), gh = (uint32_t)std::min(8, c->H - (t8 / tx8) * 8);
+    c->U.front_pixels = c->front_need_px + (c->front_need_h[t8] ? 0u : gw * gh);
+  }
+  // motion reprojection: the first G-buffer after a position update reprojects from the positions the previous
+  // one traced, and leaves the sampling launch of this frame a distance in WEIGHT.z
+  const bool motion = c->motion_on && c->moved;
+  launch_gbuffer(c->dsc, c->U, c->img[P_pos(c)], c->img[P_nrm(c)], c->img[c->depth_cur], c->img[P_DIFFUSE],
+                 c->img[P_wgt(c)], c->gclass, c->stats, motion ? c->d_pos : nullptr, motion ? c->prev_pos : nullptr,
+                 fs);
+  c->motion_frame = motion;
+  c->moved = false;
+  c->compacted = false;
+  return check_launch(c);
+}
+
+static int enqueue_sampling(fr_ctx* c, hipStream_t fs) {
+  c->mask_dirty = false;
+  const bool lp = c->U.mask_mode == FR_MASK_LOGPOLAR || c->U.mask_mode == FR_MASK_LOGPOLAR_SIGNED;
+  const bool lp_refresh = lp && (c->lp_mode != c->U.mask_mode || c->lp_gaze.x != c->U.gaze.x ||
+                                 c->lp_gaze.y != c->U.gaze.y);
+  if (lp_refresh) { c->lp_mode = c->U.mask_mode; c->lp_gaze = c->U.gaze; }
+  // EXTRA on demand (fr_ctx::extra): the launch stores no heat map and, unless the saliency mask
+  // reads them, evaluates no saliency features; what k_extra needs of it is recorded. A tile-local front and tile
+  // sharding keep the eager form (their G-buffer inputs do not cover the screen).
+  const bool lazy = c->extra_lazy && c->cfg.write_extra && !c->U.front_need && c->U.shard_count <= 1;
+  launch_sampling(c->U, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
+                  c->img[P_nrm(c)], c->img[P_DIFFUSE], c->img[P_EXTRA], c->mask, c->gclass, c->words, c->counts,
+                  lazy ? 0 : c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh,
+                  c->U.shard_count > 1 ? c->bcount : nullptr, c->motion_frame, c->dev_box, fs);
+  c->motion_frame = false;  // WEIGHT.z is the validity from here on: a repeated sampling launch runs the plain test
+  if (c->cfg.write_extra) c->extra.owed = lazy;  // (write_extra = 0: EXTRA is never written, nothing is ever owed)
+  if (lazy) c->extra.record(c);
+  if (c->U.shard_count > 1) {
+    // every rank's active count of this frame (fr_shard_counts, the group's transfer sizes), to pinned
+    // host memory with its own event: reading it waits for this frame's front stages only
+    launch_owner_counts(c->U, c->bcount, c->owner_counts_p[c->slot], fs);
+    hipMemcpyAsync(c->h_counts + (size_t)c->slot * FR_MAX_SHARD_RANKS, c->owner_counts_p[c->slot],
+                   sizeof(uint32_t) * FR_MAX_SHARD_RANKS, hipMemcpyDeviceToHost, fs);
+    hipEventRecord(c->ev_counts[c->slot], fs);
+    c->counts_valid[c->slot] = true;
+  }
+  c->compacted = false;
+  return check_launch(c);
+}
+
+static int enqueue_optimize(fr_ctx* c, hipStream_t fs) {
+  if (c->mask_dirty) {
+    launch_mask_words(c->mask, c->gclass, c->W, c->H, c->words, c->counts, fs);
+    c->mask_dirty = false;
+  }
+  launch_compaction(c->W, c->H, c->words, c->counts, c->offsets, c->tiles, c->ray_count, c->active, fs);
+  c->compacted = true;
+  return check_launch(c);
+}
+
+int fri::enqueue_shading(fr_ctx* c) {
+  if (!c->compacted) {  // g_isOptimize = 0: the active list is still needed by this design
+    if (int rc = enqueue_optimize(c, c->stream)) return rc;
+  }
+  if (c->front_pending) {  // a pipelined frame: entry 3 waits for its own front stages
+    hipStreamWaitEvent(c->stream, c->ev_front, 0);
+    c->front_pending = false;
+  }
+  hipEvent_t* kt = nullptr;
+  if (c->kt_on) {
+    const int i = c->kt_next;
+    if (c->kt_pending == fr_ctx::KT_RING) { kt_harvest(c, i); c->kt_pending--; }
+    kt = c->kt_ev[i];
+    c->kt_next = (i + 1) % fr_ctx::KT_RING;
+    c->kt_pending++;
+    hipEventRecord(kt[0], c->stream);
+  }
+  // this frame's sample setup: enqueued by its front stages into the other aux buffer (frame_half), or here
+  if (c->setup_early) {
+    c->aux_i ^= 1;
+    c->aux = c->aux_p[c->aux_i];
+    c->aux_seed = c->aux_seed_p[c->aux_i];
+  }
+  const bool early = c->setup_early;
+  c->setup_early = false;
+  // The inactive pixels' history carry (HBM-bound) touches no buffer k_shade_paths reads or writes:
+  // it runs on stream4 beside the latency-bound megakernel and joins before the resolve. In latency mode, with one
+  // untiled view, it also writes the validity bits of the history this frame leaves (the next frame's early setup).
+  const bool hv = c->pipeline_mode == FR_PIPELINE_LATENCY && c->early_setup && c->U.shard_count <= 1 && !c->U.front_need;
+  hipEventRecord(c->ev[11], c->stream);
+  hipStreamWaitEvent(c->stream4, c->ev[11], 0);
+  launch_carry_history(c->U, c->mask, c->img[P_wgt(c)], c->img[c->hist_cache], c->img[c->hist_cur],
+                       c->img[P_shd(c)], hv ? c->hvalid : nullptr, c->stream4);
+  hipEventRecord(c->ev[12], c->stream4);
+  const uint32_t N = (uint32_t)((size_t)c->W * c->H);
+  if (!early)
+    launch_sample_setup(c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache], nullptr, c->aux,
+                        c->aux_seed, c->stream);
+  if (c->time_kernels) hipEventRecord(c->ev[9], c->stream);
+  if (kt) hipEventRecord(kt[1], c->stream);
+  launch_shade_paths(c->dsc, c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache],
+                     c->shade_ctr, c->samples, c->sample_help, c->stats, c->aux, c->aux_seed, c->chunk_refr,
+                     c->xcd_bands, c->handoff, c->shade_blocks_per_cu, c->item_store, c->stream);
+  if (c->time_kernels) hipEventRecord(c->ev[10], c->stream);
+  if (kt) hipEventRecord(kt[2], c->stream);
+  hipStreamWaitEvent(c->stream, c->ev[12], 0);
+  launch_shade_resolve(c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache], c->samples,
+                       c->sample_help, c->img[c->hist_cur], c->img[P_shd(c)], c->shade_ctr, c->handoff,
+                       c->shade_blocks_per_cu, c->U.shard_count > 1 ? c->shade_radiance : nullptr, c->stream);
+  if (kt) hipEventRecord(kt[3], c->stream);
+  // this slot's WEIGHT / mask / active list are free for the front stages of frame + nslots after this
+  hipEventRecord(c->ev_trace[c->slot], c->stream);
+  c->trace_pending[c->slot] = true;
+  int rc = check_launch(c);
+  // swapBuffer("history_cache", "history_buffer"); swapBuffer("depth_cache", "depth_buffer") (:226-227)
+  std::swap(c->hist_cur, c->hist_cache);
+  c->hvalid_fresh = hv;
+  std::swap(c->depth_cur, c->depth_cache);
+  return rc;
+}
+
+// JFA_COORD owed by the last JumpFlooding (launch_jfa with outputs = false), written on `s`, which the caller has
+// ordered after that JumpFlooding (from its final state and JFA_COLOR: nothing but the next JumpFlooding or a write of
+// JFA_COLOR changes those).
+static void materialize_jfa(fr_ctx* c, hipStream_t s) {
+  if (!c->jfa_coord_owed) return;
+  launch_jfa_coord(c->jfa_final, c->img[P_JFA_COLOR], c->img[P_JFA_COORD], c->W, c->H, s);
+  c->jfa_coord_owed = false;
+}
+
+// EXTRA owed by the last sampling: settled before anything reads it or, outside a frame, overwrites what k_extra reads
+void fr_ctx::ExtraDebt::record(const fr_ctx* c) {
+  U = c->U;
+  sc = c->dsc;
+  box = c->dev_box;
+  depth = c->depth_cur;
+  nrm = P_nrm(c);
+  wgt = P_wgt(c);
+}
+void fr_ctx::ExtraDebt::settle(fr_ctx* c) {
+  if (!owed) return;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  launch_extra(U, sc, c->img[depth], c->img[wgt], c->img[nrm], c->img[P_DIFFUSE], c->img[P_EXTRA], box, c->stream);
+  owed = false;
+}
+bool fr_ctx::ExtraDebt::reads(int phys) const {
+  return owed && (phys == P_DIFFUSE || phys == depth || phys == nrm || phys == wgt);
+}
+
+int fri::resolve(fr_ctx* c, int id, int* phys) {
+  // JFA_COORD read by a caller or a pass outside the frame chain, or JFA_COLOR about to be written: JFA_COORD is
+  // written first when owed (on the context stream, after the pending reconstruction)
+  if ((id == FR_BUF_JFA_COORD || id == FR_BUF_JFA_COLOR) && c->jfa_coord_owed) {
+    join_recon(c);
+    materialize_jfa(c, c->stream);
+  }
+  if (id == FR_BUF_EXTRA) c->extra.settle(c);  // the same for a read of EXTRA
+  switch (id) {
+    case FR_BUF_POSITION: *phys = P_pos(c); return FR_OK;
+    case FR_BUF_NORMAL: *phys = P_nrm(c); return FR_OK;
+    case FR_BUF_DEPTH: *phys = c->depth_cur; return FR_OK;
+    case FR_BUF_DEPTH_CACHE: *phys = c->depth_cache; return FR_OK;
+    case FR_BUF_DIFFUSE: *phys = P_DIFFUSE; return FR_OK;
+    case FR_BUF_WEIGHT: *phys = P_wgt(c); return FR_OK;
+    case FR_BUF_HISTORY: *phys = c->hist_cur; return FR_OK;
+    case FR_BUF_HISTORY_CACHE: *phys = c->hist_cache; return FR_OK;
+    case FR_BUF_SHADING: *phys = P_shd(c); return FR_OK;
+    case FR_BUF_EXTRA: *phys = P_EXTRA; return FR_OK;
+    case FR_BUF_JFA_COORD: *phys = P_JFA_COORD; return FR_OK;
+    case FR_BUF_JFA_COLOR: *phys = P_JFA_COLOR; return FR_OK;
+    case FR_BUF_SIBSON: *phys = P_SIBSON; return FR_OK;
+    case FR_BUF_PULLPUSH: *phys = P_PULLPUSH; return FR_OK;
+    case FR_BUF_ATROUS: *phys = c->atrous_out; return FR_OK;
+    case FR_BUF_LOGPOLAR: *phys = P_LOGPOLAR; return FR_OK;
+    case FR_BUF_LOGPOLAR_INVERSE: *phys = P_LOGPOLAR_INV; return FR_OK;
+    default: return FR_E_INVALID;
+  }
+}
+
+// JFA_COORD is written only when something asks for it (materialize_jfa: a caller's read, copy or view of a JFA
+// output, a pass reading one, a write of JFA_COLOR). Sibson's run form takes the seeds from the final state and a frame
+// reads nothing else of it: 133 MB less per 4K frame. (FOVRT_JFA_LAZY_OUTPUTS=0: always written.)
+static int enqueue_jfa(fr_ctx* c, int in_buffer, hipStream_t stream = nullptr) {
+  int p;
+  if (resolve(c, in_buffer, &p)) return fail(c, FR_E_INVALID, "jfa: bad input buffer");
+  const bool run_form = c->cfg.sibson_mode == 0;
+  const bool lazy = run_form && c->lazy_jfa_outputs;
+  c->jfa_final = launch_jfa(c->img[p], c->jfa_a, c->jfa_b, c->img[P_JFA_COORD], c->img[P_JFA_COLOR], c->ftab, c->W,
+                            c->H, run_form ? c->sib_prefix : nullptr, run_form ? c->sib_blocks : nullptr, !lazy,
+                            c->jfa_xcd, stream ? stream : c->stream);
+  c->jfa_coord_owed = lazy;
+  c->sib_prefix_fresh = run_form;
+  return check_launch(c);
+}
+static int enqueue_sibson(fr_ctx* c, hipStream_t stream = nullptr) {
+  if (c->cfg.sibson_mode == 1) {  // per tap, bit-exact against the oracle (reads JFA_COORD)
+    materialize_jfa(c, stream ? stream : c->stream);
+    launch_sibson(c->img[P_JFA_COORD], c->img[P_JFA_COLOR], c->img[P_SIBSON], c->W, c->H, stream ? stream : c->stream);
+  } else {  // run form (default): exact tap sets, rounding-level differences
+    launch_sibson_runs(c->img[P_JFA_COORD], c->jfa_final, c->img[P_JFA_COLOR], c->sib_prefix, c->sib_blocks, c->sib_rowp, c->sib_wide,
+                       c->sib_strips, c->img[P_SIBSON], c->W, c->H, c->sib_prefix_fresh, c->sib_strip, c->sib_strip_mid,
+                       c->jfa_coord_owed,
+                       stream ? stream : c->stream);
+  }
+  return check_launch(c);
+}
+static int enqueue_pullpush(fr_ctx* c, int in_buffer, hipStream_t stream = nullptr) {
+  int p;
+  if (resolve(c, in_buffer, &p)) return fail(c, FR_E_INVALID, "pullpush: bad input buffer");
+  launch_pullpush(c->img[p], c->pull, c->push, c->snap, c->img[P_PULLPUSH], c->W, c->H, stream ? stream : c->stream);
+  return check_launch(c);
+}
+static int enqueue_atrous(fr_ctx* c, int count, int pos, int nrm, int col, hipStream_t stream = nullptr) {
+  if (!stream) stream = c->stream;
+  int pp, pn, pc;
+  if (count < 1 || resolve(c, pos, &pp) || resolve(c, nrm, &pn) || resolve(c, col, &pc))
+    return fail(c, FR_E_INVALID, "atrous: bad arguments");
+  if (pc == P_ATROUS_A || pc == P_ATROUS_B) return fail(c, FR_E_INVALID, "atrous: colour input aliases the output");
+  float c_phi = 1.f, n_phi = 1.f, p_phi = 1.f;
+  int sw = 1;
+  // (phis and step widths stay powers of two below, which launch_atrous requires)
+  const f4* in = c->img[pc];
+  int out = P_ATROUS_B;
+  for (int k = 0; k < count; k++) {  // FR/ATrous.cpp:90-113
+    if (k) { c_phi *= 1.0f; n_phi *= 0.5f; p_phi *= 1.0f; sw *= 2; }
+    out = out == P_ATROUS_A ? P_ATROUS_B : P_ATROUS_A;
+    if (!launch_atrous(c->img[pp], c->img[pn], in, c->img[out], c->W, c->H, c_phi, n_phi, p_phi, (float)sw,
+                       c->atrous_rows2, c->atrous_xcd, stream))
+      return fail(c, FR_E_INVALID, "atrous: bad arguments");
+    in = c->img[out];
+  }
+  c->atrous_out = out;
+  return check_launch(c);
+}
+
+static int timed(fr_ctx* c, const std::function<int()>& f, float* ms) {
+  hipSetDevice(c->cfg.device);
+  join_recon(c);
+  hipEventRecord(c->ev[0], c->stream);
+  if (int rc = f()) return rc;
+  hipEventRecord(c->ev[1], c->stream);
+  hipError_t e = hipEventSynchronize(c->ev[1]);
+  if (e != hipSuccess) return fail(c, FR_E_HIP, std::string("stage failed: ") + hipGetErrorString(e));
+  if (ms) *ms = elapsed(c->ev[0], c->ev[1]);
+  return FR_OK;
+}
+
+// Frame halves: the trace half (update -> entries 0..3) and the reconstruction half (JFA -> SI ->
+// PPI -> AT). fr_frame runs both; a tile-sharded view runs the trace half on every rank and the
+// reconstruction half on the rank that composites (after fr_shard_unpack of the other ranks' tiles).
+int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
+  if (!c) return FR_E_INVALID;
+  hipSetDevice(c->cfg.device);
+  hipEvent_t* ev = c->ev;
+  int rc;
+  // fr_frame_clock: a frame that fails after enqueue_geometry reserved its ring entry gives the entry
+  // back (it would never get its end event)
+  struct FcGuard {
+    fr_ctx* c;
+    ~FcGuard() {
+      if (c->fc_cur < 0) return;
+      c->fc_next = c->fc_cur;
+      c->fc_pending--;
+      c->fc_cur = -1;
+    }
+  } fc_guard{c};
+  if (t) hipEventRecord(ev[0], c->stream);
+  if (trace) {
+    // untimed frames pipeline: the front stages go to stream5 and overlap the previous frame's
+    // entry 3 (timed frames keep every stage on `stream`, one after the other)
+    hipStream_t fs = t ? c->stream : c->stream5;
+    const bool latency = !t && c->pipeline_mode == FR_PIPELINE_LATENCY;
+    const int prev = c->slot;  // the previous frame's slot
+    if (latency && (c->jfa_pending[prev] || c->trace_pending[prev])) {
+      // one frame ahead at most: the host waits until the previous frame's JumpFlooding has ended (its
+      // path trace, when this context does not run that chain), then samples the gaze and enqueues this
+      // frame, whose front stages (G-buffer, sampling, compaction) overlap the previous frame's Sibson
+      // and pull-push -> A-Trous; its path trace starts after them (below)
+      // (polled: a blocking wait woke the host up to milliseconds late, and the GPU idled meanwhile)
+      hipEvent_t w = c->jfa_pending[prev] ? c->ev_jfa[prev] : c->ev_trace[prev];
+      hipError_t e;
+      if ((e = poll_event(w, kPollDeadlineMs)) != hipSuccess)
+        return fail(c, FR_E_HIP, e == hipErrorNotReady ? std::string("frame failed: the previous frame did not complete within the poll deadline")
+                                                        : std::string("frame failed: ") + hipGetErrorString(e));
+      // Just in time: the front stages should end about when the previous frame's Sibson does (its path
+      // trace waits for both). A completed frame's times estimate the two; when its Sibson took longer than
+      // half its front stages, the host waits the difference more (an eye-tracked gaze's big discs: 2-5 ms of
+      // Sibson against ~1.3 ms of front stages), so the gaze is sampled that much later.
+      for (int k = 0; k < c->nslots; k++) {
+        if (!c->lat_rec[k] || hipEventQuery(c->lat_ev[k][3]) != hipSuccess) continue;
+        float f = 0.0f, sb = 0.0f;
+        if (hipEventElapsedTime(&f, c->lat_ev[k][0], c->lat_ev[k][1]) == hipSuccess &&
+            hipEventElapsedTime(&sb, c->lat_ev[k][2], c->lat_ev[k][3]) == hipSuccess) {
+          // The front stages' span is the smallest of the last eight: a front stage that overlapped the
+          // previous Sibson ran slower, and estimating from it started the next front stages earlier still (into
+          // more of that Sibson: a feedback that held the eye-tracked circle's fronts at ~4 ms instead of ~1)
+          c->lat_front_hist[c->lat_front_n++ & 7] = f;
+          c->lat_front_ms = f;
+          for (int j = 1; j < std::min(8, c->lat_front_n); j++)
+            c->lat_front_ms = std::min(c->lat_front_ms, c->lat_front_hist[(c->lat_front_n - 1 - j) & 7]);
+          c->lat_sib_ms = sb;
+        }
+        c->lat_rec[k] = false;
+      }
+      // Only half of the front stages' span is overlapped: the big discs' strip kernel fills every CU, and a
+      // front stage started further into it ran ~4 ms instead of ~1, with its gaze sampled that much earlier
+      // (eye-tracked circle latency p99 16.2 -> 12.6 ms at 142 fps; C3 p50 6.15 -> 5.81 ms; overlapping none:
+      // p99 12.5 ms at 139 fps, the serial loop's rate). A short Sibson (no big discs: below kLatShortSibMs) takes the
+      // whole span: the front stages then end with it without slowing down (4K bunny centred 186.0 -> 189.3 fps at
+      // latency p50 5.72 -> 5.79 ms, 4K vokselia 233.1 -> 235.2 fps; profiles/r06_lat_overlap_*). FOVRT_LAT_OVERLAP:
+      // one percentage for every frame instead (A/B knob).
+      constexpr float kLatShortSibMs = 1.5f;
+      static const float ovl_env = [] { const char* v = getenv("FOVRT_LAT_OVERLAP"); return v ? atoi(v) / 100.0f : -1.0f; }();
+      const float ovl = ovl_env >= 0.0f ? ovl_env : c->lat_sib_ms < kLatShortSibMs ? 1.0f : 0.5f;
+      const float delay_ms = c->jfa_pending[prev] ? c->lat_sib_ms - ovl * c->lat_front_ms : 0.0f;
+      if (delay_ms > 0.05f) {
+        const auto t0 = std::chrono::steady_clock::now();
+        while (std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() < delay_ms &&
+               hipEventQuery(c->ev_recon[prev]) == hipErrorNotReady) {
+          cpu_relax();
+        }
+      }
+      c->jfa_pending[prev] = false;
+    }
+    if (!t && c->stream_dirty) {
+      // the front stages overwrite buffers (gclass, DIFFUSE, EXTRA, depth, ballots, counts, lp_cache) that
+      // work enqueued on `stream` by other calls may still read: order them after it explicitly
+      hipEventRecord(c->ev[18], c->stream);
+      hipStreamWaitEvent(fs, c->ev[18], 0);
+    }
+    c->stream_dirty = false;
+    c->fc_arm = c->fc_on && recon;  // whole frames only (a group's trace half has no end of its own)
+    c->lat_arm = latency && recon;
+    rc = enqueue_geometry(c, fs);
+    c->fc_arm = false;
+    if (rc) { c->lat_arm = false; return rc; }
+    if (t) hipEventRecord(ev[1], c->stream);
+    if ((rc = enqueue_sampling(c, fs))) return rc;
+    if (t) hipEventRecord(ev[2], c->stream);
+    if ((rc = enqueue_optimize(c, fs))) return rc;
+    if (t) hipEventRecord(ev[3], c->stream);
+    if (latency && fs != c->stream && c->hvalid_fresh && c->U.shard_count <= 1 && !c->U.front_need && c->early_setup) {
+      // Early sample setup (latency mode): from the validity bits of the previous frame's history (its carry, ev[12])
+      // instead of the history itself, so it runs here with the front stages, and this frame's megakernel starts as
+      // soon as the previous frame's reconstruction ends (the setup sat between them on the context stream, ~0.1 ms
+      // on the CUs the reconstruction had just filled). Into the aux buffer the previous megakernel does not read.
+      // (Throughput mode keeps the setup after the resolve: there the megakernel then started beside the previous
+      // frame's reconstruction burst and ran 3.9 -> 4.1 ms, 240 -> 232 fps; profiles/r06_early_setup_ab.txt.)
+      hipStreamWaitEvent(fs, c->ev[12], 0);
+      const int o = c->aux_i ^ 1;
+      launch_sample_setup(c->U, c->active, c->ray_count, (uint32_t)((size_t)c->W * c->H), c->img[P_wgt(c)], nullptr,
+                          c->hvalid, c->aux_p[o], c->aux_seed_p[o], fs);
+      if ((rc = check_launch(c))) return rc;
+      c->setup_early = true;
+    }
+    if (!t) {
+      hipEventRecord(c->ev_front, fs);
+      c->front_pending = true;
+    }
+    if (c->lat_arm) hipEventRecord(c->lat_ev[c->slot][1], fs);
+    // latency mode: this frame's path trace starts after the previous frame's reconstruction. The
+    // megakernel fills every CU, so a reconstruction running beside it waited for it to end and then
+    // delayed this frame's own reconstruction (pipelined latency p50 10-12 ms against a 5.6 ms frame).
+    if (latency && c->recon_pending[prev]) hipStreamWaitEvent(c->stream, c->ev_recon[prev], 0);
+    c->time_kernels = t != nullptr;
+    rc = enqueue_shading(c);
+    c->time_kernels = false;
+    if (rc) return rc;
+  } else if (t) {
+    for (int i = 1; i <= 3; i++) hipEventRecord(ev[i], c->stream);
+    hipEventRecord(ev[9], c->stream);
+    hipEventRecord(ev[10], c->stream);
+  }
+  if (t) hipEventRecord(ev[4], c->stream);
+  if (recon) {
+    // The reconstruction of this frame's shading runs on its own streams, so the next frame's trace
+    // half (on `stream`) overlaps it. Two independent chains read the shading: JFA -> Sibson
+    // (stream3) and pull-push -> A-Trous (stream2; atFS binds the JFA texture but never reads it,
+    // FR/shader/atFS.glsl:40-90). Both resolve their inputs now, at this frame's slot.
+    // (a group's reconstruction rank may run only one of the chains: c->recon_chains)
+    hipEventRecord(ev[16], c->stream);
+    hipStreamWaitEvent(c->stream3, ev[16], 0);
+    hipStreamWaitEvent(c->stream2, ev[16], 0);
+    if (t) hipEventRecord(ev[20], c->stream3);
+    if ((c->recon_chains & 1) && (rc = enqueue_jfa(c, FR_BUF_SHADING, c->stream3))) return rc;
+    if (t) hipEventRecord(ev[21], c->stream3);
+    if (c->pipeline_mode == FR_PIPELINE_LATENCY && (c->recon_chains & 1)) {
+      hipEventRecord(c->ev_jfa[c->slot], c->stream3);
+      c->jfa_pending[c->slot] = true;
+      if (c->lat_arm) hipEventRecord(c->lat_ev[c->slot][2], c->stream3);
+    }
+    if ((c->recon_chains & 1) && (rc = enqueue_sibson(c, c->stream3))) return rc;
+    if (t) hipEventRecord(ev[22], c->stream3);
+    if (c->recon_gate) hipStreamWaitEvent(c->stream2, c->recon_gate, 0);
+    if (t) hipEventRecord(ev[13], c->stream2);
+    if ((c->recon_chains & 2) && (rc = enqueue_pullpush(c, FR_BUF_SHADING, c->stream2))) return rc;
+    if (t) hipEventRecord(ev[14], c->stream2);
+    if ((c->recon_chains & 2) && (rc = enqueue_atrous(c, c->cfg.atrous_iterations, FR_BUF_POSITION, FR_BUF_NORMAL,
+                                                      FR_BUF_PULLPUSH, c->stream2))) return rc;
+    if (t) hipEventRecord(ev[15], c->stream2);
+    hipEventRecord(ev[17], c->stream2);
+    hipStreamWaitEvent(c->stream3, ev[17], 0);
+    hipEventRecord(c->ev_recon[c->slot], c->stream3);  // this slot's buffers are free again after this
+    c->recon_pending[c->slot] = true;
+    if (c->lat_arm && (c->recon_chains & 1)) {
+      hipEventRecord(c->lat_ev[c->slot][3], c->stream3);
+      c->lat_rec[c->slot] = true;
+    }
+    c->lat_arm = false;
+    if (c->fc_cur >= 0) {  // fr_frame_clock: both chains of this frame are done
+      hipEventRecord(c->fc_ev[c->fc_cur][1], c->stream3);
+      c->fc_cur = -1;
+    }
+    if (t) join_recon(c);
+  }
+  if (t) {
+    hipEventRecord(ev[8], c->stream);
+    hipError_t e = hipEventSynchronize(ev[8]);
+    if (e != hipSuccess) return fail(c, FR_E_HIP, std::string("frame failed: ") + hipGetErrorString(e));
+    t->geometry_ms = elapsed(ev[0], ev[1]);
+    t->sampling_ms = elapsed(ev[1], ev[2]);
+    t->optimize_ms = elapsed(ev[2], ev[3]);
+    t->shading_ms = elapsed(ev[3], ev[4]);
+    t->jfa_ms = recon ? elapsed(ev[20], ev[21]) : 0.0f;
+    t->sibson_ms = recon ? elapsed(ev[21], ev[22]) : 0.0f;
+    t->pullpush_ms = recon ? elapsed(ev[13], ev[14]) : 0.0f;
+    t->atrous_ms = recon ? elapsed(ev[14], ev[15]) : 0.0f;
+    t->total_ms = elapsed(ev[0], ev[8]);
+    t->shade_paths_ms = elapsed(ev[9], ev[10]);
+    hipMemcpy(&t->ray_count, c->ray_count, 4, hipMemcpyDeviceToHost);
+  }
+  return FR_OK;
+}
+
+extern "C" {
+
+int fr_geometry_launch(fr_ctx* c, float* ms) {
+  if (!c) return FR_E_INVALID;
+  c->extra.settle(c);  // the stage call overwrites DIFFUSE and DEPTH, and the caller may read EXTRA before the next sampling
+  return timed(c, [&] { return enqueue_geometry(c, c->stream); }, ms);
+}
+int fr_sampling_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_sampling(c, c->stream); }, ms); }
+int fr_optimize_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_optimize(c, c->stream); }, ms); }
+int fr_shading_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_shading(c); }, ms); }
+
+static int ns_timed(fr_ctx* c, std::function<int()> f, uint64_t* ns) {
+  float ms = 0;
+  int rc = timed(c, f, &ms);
+  if (ns) *ns = (uint64_t)((double)ms * 1e6);
+  return rc;
+}
+int fr_jfa_render(fr_ctx* c, int in_buffer, uint64_t* ns) { if (!c) return FR_E_INVALID; return ns_timed(c, [&] { return enqueue_jfa(c, in_buffer); }, ns); }
+int fr_sibson_render(fr_ctx* c, uint64_t* ns) { if (!c) return FR_E_INVALID; return ns_timed(c, [&] { return enqueue_sibson(c); }, ns); }
+int fr_pullpush_render(fr_ctx* c, int in_buffer, uint64_t* ns) { if (!c) return FR_E_INVALID; return ns_timed(c, [&] { return enqueue_pullpush(c, in_buffer); }, ns); }
+static int enqueue_logpolar(fr_ctx* c, int in_buffer) {
+  int p;
+  if (resolve(c, in_buffer, &p)) return fail(c, FR_E_INVALID, "logpolar: bad input buffer");
+  if (p == P_LOGPOLAR || p == P_LOGPOLAR_INV) return fail(c, FR_E_INVALID, "logpolar: input is one of its outputs");
+  launch_logpolar(c->img[p], c->img[P_LOGPOLAR], c->img[P_LOGPOLAR_INV], c->W, c->H, c->U.gaze, c->stream);
+  return check_launch(c);
+}
+int fr_logpolar_render(fr_ctx* c, int in_buffer, uint64_t* ns) {
+  if (!c) return FR_E_INVALID;
+  return ns_timed(c, [&] { return enqueue_logpolar(c, in_buffer); }, ns);
+}
+
+// g_gaze is a Win32 POINT (LONG x, y; FR/gui.h:14) and the cursor a double: the assignment truncates
+// toward zero (clamped to the LONG range here, where C++ leaves it undefined)
+static long to_long(double v) { return (long)std::max(-2147483648.0, std::min(2147483647.0, std::trunc(v))); }
+static void set_g_gaze(fr_ctx* c, long gx, long gy) {
+  // m_context["gaze"] = (float(g_gaze.x), float(g_screenSize.cy - g_gaze.y)) (FR/PathTracer.cpp:795); off-window
+  // cursors are kept as given (the log-polar mask and the gaze distance are defined for any gaze); the two
+  // texel reads at the gaze clamp to the screen (k_sampling, fr_gaze_target)
+  c->U.gaze = mk2((float)gx, (float)((long)c->H - gy));
+}
+int fr_set_gaze(fr_ctx* c, double xpos, double ypos, int fullscreen) {
+  // cursorPosCallback (FR/gui.cpp:48-66): adjust_scale = g_fullScreen ? 1 : 1.25 (:51-56);
+  // g_gaze.x = xpos; g_gaze.y = ypos * adjust_scale (:65-66, and :59-60 on the first call)
+  if (!c || !std::isfinite(xpos) || !std::isfinite(ypos)) return FR_E_INVALID;
+  const float adjust_scale = fullscreen ? 1.0f : 1.25f;
+  set_g_gaze(c, to_long(xpos), to_long(ypos * adjust_scale));
+  return FR_OK;
+}
+int fr_reset_gaze(fr_ctx* c) {
+  // framebufferSizeCallback (FR/gui.cpp:32-35): g_gaze = (w / 2, h / 2), integer division
+  if (!c) return FR_E_INVALID;
+  set_g_gaze(c, c->W / 2, c->H / 2);
+  return FR_OK;
+}
+
+int fr_atrous_render(fr_ctx* c, int count, int pos, int nrm, int col, uint64_t* ns) {
+  if (!c) return FR_E_INVALID;
+  return ns_timed(c, [&] { return enqueue_atrous(c, count, pos, nrm, col); }, ns);
+}
+
+int fr_frame(fr_ctx* c, fr_frame_timing* t) { return frame_half(c, t, true, true); }
+int fr_set_pipeline_mode(fr_ctx* c, int mode) {
+  if (!c) return FR_E_INVALID;
+  if (mode != FR_PIPELINE_THROUGHPUT && mode != FR_PIPELINE_LATENCY)
+    return fail(c, FR_E_INVALID, "fr_set_pipeline_mode: FR_PIPELINE_THROUGHPUT (0) or FR_PIPELINE_LATENCY (1)");
+  c->pipeline_mode = mode;
+  return FR_OK;
+}
+int fr_set_sample_sum(fr_ctx* c, int mode) {
+  if (!c) return FR_E_INVALID;
+  if (mode < 0 || mode > 2) return fail(c, FR_E_INVALID, "fr_set_sample_sum: mode 0 (fp32), 1 (by frame size) or 2 (fixed point)");
+  if ((uint32_t)mode == c->handoff) return FR_OK;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipDeviceSynchronize());
+  // the fixed-point form keeps 32-B sample records and a 32-B help record per sample
+  const size_t N = (size_t)c->W * c->H;
+  const size_t need_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode, c->shade_blocks_per_cu));
+  const size_t need_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, (uint32_t)mode, c->shade_blocks_per_cu), 1);
+  const size_t have_s = std::max(N * c->cfg.spp, 2 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff, c->shade_blocks_per_cu));
+  const size_t have_h = std::max<size_t>(4 * shade_fx_slots((uint32_t)N, c->cfg.spp, c->handoff, c->shade_blocks_per_cu), 1);
+  if (need_s > have_s) {
+    hipFree(c->samples); c->samples = nullptr;
+    if (dalloc(&c->samples, need_s) != hipSuccess) return fail(c, FR_E_NOMEM, "fr_set_sample_sum: allocation failed");
+  }
+  if (need_h > have_h) {
+    hipFree(c->sample_help); c->sample_help = nullptr;
+    if (dalloc(&c->sample_help, need_h) != hipSuccess) return fail(c, FR_E_NOMEM, "fr_set_sample_sum: allocation failed");
+  }
+  c->handoff = (uint32_t)mode;
+  return FR_OK;
+}
+
+int fr_set_recon_chains(fr_ctx* c, int chains) {
+  if (!c) return FR_E_INVALID;
+  if (chains < 0 || chains > 3) return fail(c, FR_E_INVALID, "fr_set_recon_chains: chains is a mask of bits 0 and 1");
+  c->recon_chains = chains;
+  return FR_OK;
+}
+int fr_trace_frame(fr_ctx* c, fr_frame_timing* t) { return frame_half(c, t, true, false); }
+int fr_reconstruct_frame(fr_ctx* c, fr_frame_timing* t) { return frame_half(c, t, false, true); }
+
+}  // extern "C"

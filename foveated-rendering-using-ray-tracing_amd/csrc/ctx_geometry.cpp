@@ -1,0 +1,542 @@
+// ctx_geometry.cpp — the scene's geometry after fr_create: the tree (GPU rebuild, refit, SAH cost), position and
+// normal updates (synchronous and in stream order), motion reprojection's switch, and the scene export calls.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#include "ctx_internal.h"
+
+using namespace fr;
+using namespace fri;
+
+// GPU build over `pos` (device; k_bvh.hip) into the spare arrays, which become the scene's tree when every
+// step succeeded (the old tree becomes the spare). No allocation after the first rebuild, no read-back
+// of the tree: the host keeps its node count, stack need and depth (fr_scene_export).
+int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
+  const int nt = c->scene.num_tris();
+  const size_t cap = (size_t)std::max(nt, 1);
+  auto alloc_spare = [&] {
+    return hipMalloc((void**)&c->spare_nodes, cap * sizeof(BvhNode)) == hipSuccess &&
+           hipMalloc((void**)&c->spare_tri, cap * sizeof(TriGeo)) == hipSuccess &&
+           hipMalloc((void**)&c->spare_prim, cap * sizeof(int32_t)) == hipSuccess;
+  };
+  if (!c->spare_nodes && !alloc_spare()) {  // (a failed re-allocation below left none)
+    c->err = "GPU BVH: device allocation failed";
+    return FR_E_NOMEM;
+  }
+  int nn = 0, max_stack = 0, depth = 0;
+  std::string err;
+  if (!gpu_build_bvh(&c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri, c->spare_prim, &nn, &max_stack, &depth,
+                     c->stream, err)) {
+    c->err = err;
+    return FR_E_HIP;
+  }
+  if (max_stack > FR_BVH_STACK) {
+    c->err = "GPU BVH needs a traversal stack deeper than FR_BVH_STACK";
+    return FR_E_UNSUPPORTED;
+  }
+  std::swap(c->d_nodes, c->spare_nodes);
+  std::swap(c->d_tri, c->spare_tri);
+  std::swap(c->d_prim, c->spare_prim);
+  if (!c->tree_full_cap) {
+    // the replaced tree was sized for the host builder's node count (or there was none): the next spare
+    // needs room for any device-built tree (at most one node per triangle)
+    if (c->spare_nodes) { hipFree(c->spare_nodes); hipFree(c->spare_tri); hipFree(c->spare_prim); }
+    c->spare_nodes = nullptr; c->spare_tri = nullptr; c->spare_prim = nullptr;
+    c->tree_full_cap = true;
+    if (!alloc_spare()) {
+      hipFree(c->spare_nodes); hipFree(c->spare_tri); hipFree(c->spare_prim);
+      c->spare_nodes = nullptr; c->spare_tri = nullptr; c->spare_prim = nullptr;  // allocated again next time
+    }
+  }
+  c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim;
+  Bvh b;
+  b.root_count = 0; b.max_stack = max_stack; b.max_depth = depth;
+  b.gpu_nodes = nn;
+  b.host_nodes = 0;
+  c->bvh = std::move(b);
+  return FR_OK;
+}
+
+static int tree_nodes(const Bvh& b) {
+  return b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size();
+}
+
+// Refit of the tree in use (either builder's) over `pos` (device), in place (k_bvh.hip). The caller has joined
+// and synchronised the context stream.
+static int gpu_refit(fr_ctx* c, const f3* pos) {
+  std::string err;
+  const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->d_nodes, nn, c->d_tri, c->d_prim, c->stream, err)) {
+    c->err = err;
+    return c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED;
+  }
+  return FR_OK;
+}
+
+// The host's time of `body` on a quiet context (fr_rebuild_bvh, fr_refit_bvh, fr_recompute_normals).
+template <class F>
+static int host_timed(fr_ctx* c, float* ms, F body) {
+  if (!c) return FR_E_INVALID;
+  if (int rc = quiesce(c)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = body();
+  if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+extern "C" {
+
+int fr_rebuild_bvh(fr_ctx* c, float* ms) { return host_timed(c, ms, [&] { return gpu_rebuild(c, c->d_pos); }); }
+int fr_refit_bvh(fr_ctx* c, float* ms) { return host_timed(c, ms, [&] { return gpu_refit(c, c->d_pos); }); }
+
+int fr_bvh_sah_cost(fr_ctx* c, float* cost) {
+  if (!c || !cost) return FR_E_INVALID;
+  if (c->bvh.root_count > 0) { *cost = (float)c->bvh.root_count; return FR_OK; }  // one leaf: its triangles
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  std::string err;
+  if (!gpu_bvh_cost(c->bvh_work, c->d_nodes, tree_nodes(c->bvh), cost, c->stream, err))
+    return fail(c, c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED, err);
+  return FR_OK;
+}
+
+static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
+// A caller's host normals: finite on every triangle that has normals (the others are ignored).
+static bool host_normals_finite(const fr_ctx* c, const float* nrm) {
+  const HostScene& s = c->scene;
+  for (size_t t = 0; t < (size_t)s.num_tris(); t++) {
+    if (!(s.flags[t] & FR_SHADE_HAS_NORMALS)) continue;
+    for (size_t i = 9 * t; i < 9 * t + 9; i++)
+      if (!std::isfinite(nrm[i])) return false;
+  }
+  return true;
+}
+
+// Normals from the caller's array into d_shade (the caller has joined and synchronised the context stream and
+// checked the array). Host normals are staged in spare_pos, which is free between updates and of the right size.
+static int write_given_normals(fr_ctx* c, const void* nrm, int where, const std::string& name) {
+  const float* src = static_cast<const float*>(nrm);
+  if (where == FR_MEM_HOST) {
+    HIP_TRY(c, hipMemcpy(c->spare_pos, nrm, c->scene.pos.size() * sizeof(f3), hipMemcpyHostToDevice));
+    src = &c->spare_pos[0].x;
+  }
+  std::string err;
+  if (!gpu_scatter_normals(c->nrm_work, src, c->d_shade, c->stream, err)) return fail(c, FR_E_HIP, name + ": " + err);
+  c->nrm_mirror_stale = true;  // refreshed by the next fr_scene_export
+  return FR_OK;
+}
+
+static int recompute_normals(fr_ctx* c, const std::string& name) {
+  std::string err;
+  if (!gpu_recompute_normals(c->nrm_work, c->d_pos, c->d_shade, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  c->nrm_mirror_stale = true;
+  return FR_OK;
+}
+
+// The steps update_positions and fr_update_geometry_enqueue share. The arguments (enqueued: device memory, refit):
+static int check_update_args(fr_ctx* c, const std::string& name, size_t ntris, int where, int how, const void* nrm,
+                             int normals) {
+  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
+  if (where != FR_MEM_HOST && where != FR_MEM_DEVICE) return fail(c, FR_E_INVALID, name + ": bad memory kind");
+  if (how != FR_BVH_REBUILD && how != FR_BVH_REFIT) return fail(c, FR_E_INVALID, name + ": bad update kind");
+  if (normals != FR_NORMALS_KEEP && normals != FR_NORMALS_GIVEN && normals != FR_NORMALS_RECOMPUTE)
+    return fail(c, FR_E_INVALID, name + ": bad normals kind");
+  if (normals == FR_NORMALS_GIVEN && !nrm) return fail(c, FR_E_INVALID, name + ": FR_NORMALS_GIVEN without normals");
+  return FR_OK;
+}
+// spare_pos, holding the new positions, becomes d_pos. Motion reprojection: spare_pos then holds the outgoing
+// positions; if the last G-buffer traced them they become prev_pos (a three-pointer rotation, no copy); after an
+// earlier update since that G-buffer prev_pos already holds what it traced and stays.
+static void rotate_positions(fr_ctx* c) {
+  std::swap(c->d_pos, c->spare_pos);
+  if (c->motion_on && !c->moved) {
+    std::swap(c->spare_pos, c->prev_pos);
+    c->moved = true;
+  }
+}
+// An owed EXTRA keeps the box its sampling launch saw: when that is geo->box, about to change, the debt moves to
+// geo->xbox, and the caller enqueues the copy there ahead of the change (true).
+static bool extra_keeps_box(fr_ctx* c) {
+  if (!c->extra.owed || c->extra.box != c->geo->box) return false;
+  c->extra.box = c->geo->xbox;
+  return true;
+}
+
+// What fr_set_positions, fr_update_positions and fr_update_geometry share. Everything that can reject the update
+// runs before anything of the scene is written: the new positions go to the spare device array, which becomes
+// d_pos only when the tree over it exists (a failed rebuild leaves d_pos, the tree, the box and the mirror as
+// they were). A caller's normals (FR_NORMALS_GIVEN) are checked with the positions, and the normals are written
+// last, when positions and tree are in place: nothing after that point rejects the update.
+static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how, const char* fn,
+                            const void* nrm = nullptr, int normals = FR_NORMALS_KEEP) {
+  const std::string name = fn;
+  if (int rc = check_update_args(c, name, ntris, where, how, nrm, normals)) return rc;
+  if (where == FR_MEM_HOST) {
+    const float* h = static_cast<const float*>(xyz);
+    for (size_t i = 0; i < ntris * 9; i++)
+      if (!std::isfinite(h[i])) return fail(c, FR_E_INVALID, name + ": position not finite");
+    if (normals == FR_NORMALS_GIVEN && !host_normals_finite(c, static_cast<const float*>(nrm)))
+      return fail(c, FR_E_INVALID, name + ": normal not finite");
+  }
+  if (int rc = quiesce(c)) return rc;
+  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+  if (where == FR_MEM_DEVICE) {
+    // finiteness and the scene box in one kernel over the caller's array, read back before d_pos changes
+    bool finite = false;
+    float box[6];
+    std::string err;
+    if (!gpu_check_positions(c->bvh_work, static_cast<const float*>(xyz), (int)ntris, &finite, box, c->stream, err))
+      return fail(c, c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED, name + ": " + err);
+    if (!finite) return fail(c, FR_E_INVALID, name + ": position not finite");
+    lo = mk3(box[0], box[1], box[2]);
+    hi = mk3(box[3], box[4], box[5]);
+    if (normals == FR_NORMALS_GIVEN) {
+      if (!gpu_check_normals(c->nrm_work, static_cast<const float*>(nrm), &finite, c->stream, err))
+        return fail(c, FR_E_HIP, name + ": " + err);
+      if (!finite) return fail(c, FR_E_INVALID, name + ": normal not finite");
+    }
+  }
+  const size_t bytes = ntris * 9 * sizeof(float);
+  // (a device-to-device hipMemcpy returns before the copy ran, and the context stream is non-blocking: the
+  // copy goes on the context stream, ahead of the kernels that read it)
+  if (where == FR_MEM_HOST) HIP_TRY(c, hipMemcpy(c->spare_pos, xyz, bytes, hipMemcpyHostToDevice));
+  else HIP_TRY(c, hipMemcpyAsync(c->spare_pos, xyz, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (how == FR_BVH_REBUILD) {
+    if (const int rc = gpu_rebuild(c, c->spare_pos)) return fail(c, rc, name + ": rebuild failed, scene unchanged: " + c->err);
+  } else if (const int rc = gpu_refit(c, c->spare_pos)) {
+    return fail(c, rc, name + ": " + c->err);
+  }
+  rotate_positions(c);
+  if (where == FR_MEM_HOST) {
+    memcpy(c->scene.pos.data(), xyz, bytes);
+    c->pos_mirror_stale = false;
+    for (const f3& v : c->scene.pos) {
+      lo = mk3(fminf(lo.x, v.x), fminf(lo.y, v.y), fminf(lo.z, v.z));
+      hi = mk3(fmaxf(hi.x, v.x), fmaxf(hi.y, v.y), fmaxf(hi.z, v.z));
+    }
+  } else {
+    c->pos_mirror_stale = true;  // refreshed by the next fr_scene_export
+  }
+  // bbox_min / bbox_max (the depth-saliency theta of k_sampling) follow the geometry, as the
+  // reference's scene AABB does at load time (FR/PathTracer.cpp:601-602,663)
+  c->scene.bbox_min = c->dsc.bbox_min = lo;
+  c->scene.bbox_max = c->dsc.bbox_max = hi;
+  if (c->dev_box) {
+    // the context has enqueued updates: the saliency stage reads the box from device memory, kept current here
+    // (an owed EXTRA keeps the one its sampling launch saw)
+    const float box[6] = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z};
+    if (extra_keeps_box(c))
+      HIP_TRY(c, hipMemcpyAsync(c->geo->xbox, c->geo->box, sizeof(box), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->geo->box, box, sizeof(box), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->box_mirror_stale = false;
+  }
+  // the normals last, over the positions and the tree now in place (spare_pos holds the replaced positions
+  // and is free again)
+  if (normals == FR_NORMALS_GIVEN) return write_given_normals(c, nrm, where, name);
+  if (normals == FR_NORMALS_RECOMPUTE) return recompute_normals(c, name);
+  return FR_OK;
+}
+
+int fr_set_positions(fr_ctx* c, const float* xyz, size_t ntris) {
+  if (!c || !xyz) return FR_E_INVALID;
+  return update_positions(c, xyz, ntris, FR_MEM_HOST, FR_BVH_REBUILD, "fr_set_positions");
+}
+
+int fr_update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where, int how) {
+  if (!c || !xyz) return FR_E_INVALID;
+  return update_positions(c, xyz, ntris, where, how, "fr_update_positions");
+}
+
+int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int where, int how, int normals) {
+  if (!c) return FR_E_INVALID;
+  if (!xyz) return fail(c, FR_E_INVALID, "fr_update_geometry: positions are NULL");
+  return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
+}
+
+// fr_update_geometry (device memory, refit) in stream order: every launch below goes on the context stream and
+// nothing here waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no synchronisation, no copy to
+// the host, no allocation). What the host learnt from the device in update_positions stays there: the verdict of
+// the two checks is a device word that k_take_over publishes and every later kernel of the update reads, and the
+// scene box goes from the check's result into geo->box, where the saliency stage reads it from now on.
+// The three position arrays rotate here, at enqueue time and whatever the verdict, exactly as in update_positions;
+// their contents follow in stream order (k_take_over fills the array that becomes d_pos with the caller's
+// positions, or with the current ones when the update is rejected). That is safe because every reader and writer
+// of the three arrays, the tree and the normals is ordered on the context stream: the front stages of a pipelined
+// frame run on stream5, but entry 3 of that frame waits for them on the context stream (ev_front) before this
+// update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
+// The reconstruction streams read none of it, so they are not joined.
+int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_update_geometry_enqueue";
+  if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
+  if (int rc = check_update_args(c, name, ntris, FR_MEM_DEVICE, FR_BVH_REFIT, nrm, normals)) return rc;
+  if (c->group_refs > 0 || c->U.shard_count > 1)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_update_geometry)");
+  if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
+  hipSetDevice(c->cfg.device);
+  c->stream_dirty = true;  // the next pipelined frame's front stages (stream5) start after this update
+  // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
+  if (c->front_pending) { hipStreamWaitEvent(c->stream, c->ev_front, 0); c->front_pending = false; }
+  if (ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ready_event), 0));
+  const int nt = (int)ntris;
+  std::string err;
+  if (!gpu_check_positions_enqueue(c->bvh_work, static_cast<const float*>(xyz), nt, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  const bool given = normals == FR_NORMALS_GIVEN;
+  if (given && !gpu_check_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), &c->geo->bad_nrm, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  // the box: seeded from the host's at the first enqueue; an owed EXTRA keeps the one its sampling launch saw
+  const int flags = (c->dev_box ? 0 : 1) | (extra_keeps_box(c) ? 2 : 0);  // (2: k_take_over makes the copy)
+  if (!gpu_take_over_positions(c->bvh_work, static_cast<const f3*>(xyz), c->d_pos, nt, c->spare_pos,
+                               given ? &c->geo->bad_nrm : nullptr, c->geo, flags, c->scene.bbox_min, c->scene.bbox_max,
+                               c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  c->dev_box = c->geo->box;
+  c->box_mirror_stale = true;
+  if (!given) HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // xyz has been read
+  const uint32_t* reject = &c->geo->reject;
+  const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  if (!gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  rotate_positions(c);
+  c->pos_mirror_stale = true;
+  if (given) {
+    if (!gpu_scatter_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), c->d_shade, reject, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // nrm has been read as well
+    c->nrm_mirror_stale = true;
+  } else if (normals == FR_NORMALS_RECOMPUTE) {
+    if (!gpu_recompute_normals_enqueue(c->nrm_work, c->d_pos, c->d_shade, reject, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    c->nrm_mirror_stale = true;
+  }
+  c->geo_read_pending = true;
+  return FR_OK;
+}
+
+int fr_geometry_consumed(fr_ctx* c, void* stream) {
+  if (!c) return FR_E_INVALID;
+  if (!c->geo_read_pending) return FR_OK;
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipStreamWaitEvent(static_cast<hipStream_t>(stream), c->ev_geo_read, 0));
+  return FR_OK;
+}
+
+int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) {
+  if (!c) return FR_E_INVALID;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(c->h_geo, c->geo, sizeof(fr::GeoUpdateState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const fr::GeoUpdateState& g = *c->h_geo;
+  if (applied) *applied = g.applied;
+  if (rejected) *rejected = g.rejected;
+  if (g.rejected > c->geo_rejected_seen[0]) {
+    const bool pos = g.rejected_pos > c->geo_rejected_seen[1], nr = g.rejected_nrm > c->geo_rejected_seen[2];
+    c->err = std::string("fr_update_geometry_enqueue: ") +
+             (pos && nr ? "position not finite, normal not finite" : pos ? "position not finite" : "normal not finite") +
+             " (update rejected on the device, scene unchanged)";
+  }
+  c->geo_rejected_seen[0] = g.rejected;
+  c->geo_rejected_seen[1] = g.rejected_pos;
+  c->geo_rejected_seen[2] = g.rejected_nrm;
+  return FR_OK;
+}
+
+int fr_set_motion_reprojection(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  if (on != 0 && on != 1) return fail(c, FR_E_INVALID, "fr_set_motion_reprojection: on is 0 or 1");
+  if (int rc = quiesce(c)) return rc;
+  if (on && !c->prev_pos && dalloc(&c->prev_pos, c->scene.pos.size()) != hipSuccess) {
+    (void)hipGetLastError();
+    if (c->prev_pos) hipFree(c->prev_pos);
+    c->prev_pos = nullptr;
+    return fail(c, FR_E_NOMEM, "fr_set_motion_reprojection: device allocation (previous positions) failed");
+  }
+  c->motion_on = on != 0;
+  if (!on) c->moved = false;  // a pending motion is dropped: the next G-buffer is the plain one
+  return FR_OK;
+}
+
+int fr_set_normals(fr_ctx* c, const void* nrm, size_t ntris, int where) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_normals";
+  if (!nrm) return fail(c, FR_E_INVALID, name + ": normals are NULL");
+  if (ntris != (size_t)c->scene.num_tris()) return fail(c, FR_E_INVALID, name + ": triangle count differs");
+  if (where != FR_MEM_HOST && where != FR_MEM_DEVICE) return fail(c, FR_E_INVALID, name + ": bad memory kind");
+  if (where == FR_MEM_HOST && !host_normals_finite(c, static_cast<const float*>(nrm)))
+    return fail(c, FR_E_INVALID, name + ": normal not finite");
+  if (int rc = quiesce(c)) return rc;
+  if (where == FR_MEM_DEVICE) {
+    bool finite = false;
+    std::string err;
+    if (!gpu_check_normals(c->nrm_work, static_cast<const float*>(nrm), &finite, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    if (!finite) return fail(c, FR_E_INVALID, name + ": normal not finite");
+  }
+  return write_given_normals(c, nrm, where, name);
+}
+
+int fr_recompute_normals(fr_ctx* c, float* ms) {
+  return host_timed(c, ms, [&] { return recompute_normals(c, "fr_recompute_normals"); });
+}
+
+static int copy_groups(const NormalGroups& g, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (corner_vertex) {
+    if (ncorners != g.corner_vertex.size()) return FR_E_INVALID;
+    memcpy(corner_vertex, g.corner_vertex.data(), ncorners * sizeof(int32_t));
+  }
+  if (nverts) *nverts = g.num_verts;
+  return FR_OK;
+}
+
+int fr_normal_groups(fr_ctx* c, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (!c) return FR_E_INVALID;
+  if (copy_groups(c->groups, corner_vertex, ncorners, nverts))
+    return fail(c, FR_E_INVALID, "fr_normal_groups: ncorners is not 3 per triangle");
+  return FR_OK;
+}
+
+// Test hook (not part of include/fovrt.h): the tree in use, whichever builder made it, copied to the host:
+// fr_scene_export's bvh_nodes BvhNode, then num_tris TriGeo and num_tris leaf-order primitive indices.
+int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size_t tri_bytes, int32_t* prim,
+                 size_t prim_bytes) {
+  if (!c || !nodes || !tri_geo || !prim) return FR_E_INVALID;
+  const Bvh& b = c->bvh;
+  const size_t nn = (size_t)tree_nodes(b);
+  const size_t nt = (size_t)c->scene.num_tris();
+  if (nodes_bytes < nn * sizeof(BvhNode) || tri_bytes < nt * sizeof(TriGeo) || prim_bytes < nt * sizeof(int32_t))
+    return fail(c, FR_E_INVALID, "fr__bvh_read: buffer too small");
+  if (int rc = quiesce(c)) return rc;
+  HIP_TRY(c, hipMemcpy(nodes, c->d_nodes, nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(tri_geo, c->d_tri, nt * sizeof(TriGeo), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(prim, c->d_prim, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return FR_OK;
+}
+
+}  // extern "C"
+
+struct fr_scene {
+  HostScene scene;
+  Bvh bvh;
+  NormalGroups groups;
+  std::string err;
+  std::vector<const float*> tex_ptrs;
+  std::vector<int32_t> tex_dims, mat_pairs;
+};
+
+static void fill_arrays(const HostScene& s, const Bvh& bvh, f3 emission, std::vector<int32_t>& mat_pairs,
+                        std::vector<int32_t>& tex_dims, std::vector<const float*>& tex_ptrs, fr_scene_arrays* o) {
+  memset(o, 0, sizeof(*o));
+  o->num_tris = s.num_tris();
+  o->pos = &s.pos[0].x; o->nrm = &s.nrm[0].x; o->uv = &s.uv[0].x; o->flags = s.flags.data();
+  mat_pairs.clear();
+  for (auto& m : s.mats) { mat_pairs.push_back(m.type); mat_pairs.push_back(m.tex); }
+  o->num_materials = (int)s.mats.size();
+  o->materials = mat_pairs.data();
+  tex_dims.clear(); tex_ptrs.clear();
+  for (auto& t : s.texs) { tex_dims.push_back(t.w); tex_dims.push_back(t.h); tex_ptrs.push_back(&t.data[0].x); }
+  o->num_textures = (int)s.texs.size();
+  o->tex_dims = tex_dims.data();
+  o->tex_data = tex_ptrs.data();
+  o->envmap = s.envmap;
+  const f3 L[5] = {s.light_position, s.light_v1, s.light_v2, s.light_normal, emission};
+  for (int i = 0; i < 5; i++) { o->light[3 * i] = L[i].x; o->light[3 * i + 1] = L[i].y; o->light[3 * i + 2] = L[i].z; }
+  o->bbox[0] = s.bbox_min.x; o->bbox[1] = s.bbox_min.y; o->bbox[2] = s.bbox_min.z;
+  o->bbox[3] = s.bbox_max.x; o->bbox[4] = s.bbox_max.y; o->bbox[5] = s.bbox_max.z;
+  o->bvh_nodes = tree_nodes(bvh);
+  o->bvh_depth = bvh.max_depth;
+  o->bvh_max_stack = bvh.max_stack;
+}
+
+extern "C" {
+
+int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
+  if (!c || !o) return FR_E_INVALID;
+  if (c->geo_read_pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
+    // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
+    hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (c->pos_mirror_stale) {  // positions last came from device memory (fr_update_positions): fetch them now
+    hipSetDevice(c->cfg.device);
+    HIP_TRY(c, hipMemcpy(c->scene.pos.data(), c->d_pos, c->scene.pos.size() * sizeof(f3), hipMemcpyDeviceToHost));
+    c->pos_mirror_stale = false;
+  }
+  if (c->box_mirror_stale) {  // an enqueued update left the scene box on the device (fr_update_geometry_enqueue)
+    hipSetDevice(c->cfg.device);
+    float box[6];
+    HIP_TRY(c, hipMemcpy(box, c->geo->box, sizeof(box), hipMemcpyDeviceToHost));
+    c->scene.bbox_min = c->dsc.bbox_min = mk3(box[0], box[1], box[2]);
+    c->scene.bbox_max = c->dsc.bbox_max = mk3(box[3], box[4], box[5]);
+    c->box_mirror_stale = false;
+  }
+  if (c->nrm_mirror_stale) {  // normals were last written on the device: they are d_shade's n0 / n1 / n2 .xyz
+    hipSetDevice(c->cfg.device);
+    std::vector<TriShade> shade(c->scene.flags.size());
+    HIP_TRY(c, hipMemcpy(shade.data(), c->d_shade, shade.size() * sizeof(TriShade), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < shade.size(); i++) {
+      c->scene.nrm[3 * i] = xyz(shade[i].n0);
+      c->scene.nrm[3 * i + 1] = xyz(shade[i].n1);
+      c->scene.nrm[3 * i + 2] = xyz(shade[i].n2);
+    }
+    c->nrm_mirror_stale = false;
+  }
+  fill_arrays(c->scene, c->bvh, c->dsc.light_emission, c->mat_pairs, c->tex_dims, c->tex_ptrs, o);
+  return FR_OK;
+}
+
+int fr_scene_create(const fr_config* cfg_in, fr_scene** out) {
+  if (!out) return fail(nullptr, FR_E_INVALID, "out is NULL");
+  *out = nullptr;
+  fr_config cfg;
+  if (cfg_in) cfg = *cfg_in; else fr_config_default(&cfg);
+  if (cfg.scene < 0 || cfg.scene > 2) return fail(nullptr, FR_E_INVALID, "bad scene preset");
+  if (cfg.mesh_mode < 0 || cfg.mesh_mode > 2) return fail(nullptr, FR_E_INVALID, "bad mesh_mode");
+  fr_scene* sc = new fr_scene();
+  std::string err;
+  if (!build_preset_scene(cfg.scene, cfg.asset_dir ? cfg.asset_dir : "assets", cfg.texture_mode, cfg.light_power,
+                          cfg.detail, sc->scene, err, cfg.mesh_mode)) {
+    delete sc;
+    return fail(nullptr, FR_E_IO, "scene: " + err);
+  }
+  build_bvh(sc->scene, sc->bvh);
+  build_normal_groups(sc->scene, sc->groups);
+  *out = sc;
+  return FR_OK;
+}
+
+int fr_scene_get_arrays(fr_scene* sc, fr_scene_arrays* o) {
+  if (!sc || !o) return FR_E_INVALID;
+  fill_arrays(sc->scene, sc->bvh, sc->scene.light_emission, sc->mat_pairs, sc->tex_dims, sc->tex_ptrs, o);
+  return FR_OK;
+}
+
+int fr_scene_normal_groups(fr_scene* sc, int32_t* corner_vertex, size_t ncorners, int* nverts) {
+  if (!sc) return FR_E_INVALID;
+  return copy_groups(sc->groups, corner_vertex, ncorners, nverts);
+}
+
+// Test hook (not part of include/fovrt.h): the host-built tree of an fr_scene (pointers into it, valid until
+// fr_scene_destroy): num_nodes BvhNode, then num_leaf_tris TriGeo and leaf-order primitive indices.
+int fr__scene_bvh(fr_scene* sc, const void** nodes, int* num_nodes, const void** tri_geo, const int32_t** prim,
+                  int* num_leaf_tris) {
+  if (!sc || !nodes || !num_nodes || !tri_geo || !prim || !num_leaf_tris) return FR_E_INVALID;
+  *nodes = sc->bvh.nodes.data();
+  *num_nodes = (int)sc->bvh.nodes.size();
+  *tri_geo = sc->bvh.tri_geo.data();
+  *prim = sc->bvh.tri_prim.data();
+  *num_leaf_tris = (int)sc->bvh.tri_prim.size();
+  return FR_OK;
+}
+
+int fr_scene_destroy(fr_scene* sc) {
+  if (!sc) return FR_E_INVALID;
+  delete sc;
+  return FR_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,10 @@
-// ctx_internal.h — the fr_ctx context (device memory, streams, frame slots) shared by the C ABI in
-// context.cpp and the multi-GPU group in group.cpp. Not part of the public interface (include/fovrt.h).
+// ctx_internal.h — the fr_ctx context (device memory, streams, frame slots) and the helpers shared by the C ABI in
+// ctx_*.cpp (one file per concern) and the multi-GPU group in group.cpp. Not part of the public
+// interface (include/fovrt.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -91,7 +93,7 @@ uint32_t diag_recorded_queries(hipStream_t);
 void diag_sample_trace(uint32_t*, uint32_t, uint32_t*, uint32_t, hipStream_t);
 #endif
 void launch_pullpush(const f4*, f4*, f4*, f4*, f4*, int, int, hipStream_t);
-void launch_atrous(const f4*, const f4*, const f4*, f4*, int, int, float, float, float, float, bool, int, hipStream_t);
+bool launch_atrous(const f4*, const f4*, const f4*, f4*, int, int, float, float, float, float, bool, int, hipStream_t);
 int pp_size(int W, int H);
 size_t pp_snap_count(int S);
 }  // namespace fr
@@ -110,7 +112,6 @@ using fr::DevStats;
 using fr::FrameUniforms;
 using fr::HostScene;
 using fr::Bvh;
-
 
 enum Phys {
   P_POSITION, P_NORMAL, P_DEPTH_A, P_DEPTH_B, P_DIFFUSE, P_WEIGHT, P_HIST_A, P_HIST_B, P_SHADING, P_EXTRA,
@@ -217,14 +218,14 @@ struct fr_ctx {
   bool pos_mirror_stale = false;
   // Enqueued updates (fr_update_geometry_enqueue). geo: their record on the device (verdict, counters, the scene
   // box), made by fr_create; h_geo: its pinned copy for fr_geometry_update_status. Once a context has enqueued an
-  // update the box lives in geo->box (dev_box points there, the saliency stage reads it; extra_box: the box an owed
+  // update the box lives in geo->box (dev_box points there, the saliency stage reads it; extra.box: the box an owed
   // EXTRA's sampling launch saw, geo->box or geo->xbox) and scene.bbox_min / bbox_max may be behind
   // (box_mirror_stale; fr_scene_export fetches it). ev_geo_read: recorded on the context
   // stream after the last kernel that reads the caller's arrays of the last enqueued update (fr_geometry_consumed).
   // geo_rejected_seen: the rejected counts fr_geometry_update_status last reported (total, positions, normals).
   fr::GeoUpdateState* geo = nullptr;
   fr::GeoUpdateState* h_geo = nullptr;
-  const float *dev_box = nullptr, *extra_box = nullptr;
+  const float* dev_box = nullptr;
   hipEvent_t ev_geo_read = nullptr;
   bool geo_read_pending = false;
   bool box_mirror_stale = false;
@@ -304,16 +305,23 @@ struct fr_ctx {
   // materialize_jfa writes it (k_jfa_coord, from jfa_final and JFA_COLOR) before anything reads it or writes JFA_COLOR.
   bool jfa_coord_owed = false;
   bool lazy_jfa_outputs = true;  // FOVRT_JFA_LAZY_OUTPUTS=0: every JumpFlooding writes JFA_COORD
-  // k_sampling leaves the EXTRA heat map unwritten (nothing in a frame reads it): while extra_owed, materialize_extra_now
+  // k_sampling leaves the EXTRA heat map unwritten (nothing in a frame reads it): while extra.owed, extra.settle
   // writes it (k_extra) from what the owing launch saw, before anything reads EXTRA or overwrites one of those inputs
   // outside a frame: the launch's uniforms and scene (gaze, screen, bbox: copies, so later setters do not reach them),
   // DIFFUSE, and the physical buffers that were its DEPTH (the ping-pong swaps in enqueue_shading), NORMAL and WEIGHT
-  // (its slot's; the sampling leaves WEIGHT.xy as they were). The next sampling replaces the debt.
-  bool extra_owed = false;
+  // (its slot's; the sampling leaves WEIGHT.xy as they were). The next sampling replaces the debt. Inside a frame
+  // nothing settles it: no caller can see EXTRA between a frame's G-buffer and its sampling. (ctx_frame.cpp)
+  struct ExtraDebt {
+    bool owed = false;
+    FrameUniforms U;
+    DevScene sc;
+    const float* box = nullptr;  // the scene box the launch saw: dev_box then (NULL, geo->box), or geo->xbox
+    int depth = P_DEPTH_A, nrm = P_NORMAL, wgt = P_WEIGHT;
+    void record(const fr_ctx* c);  // what the sampling launch being enqueued sees
+    bool reads(int phys) const;    // does the owed heat map read this physical buffer?
+    void settle(fr_ctx* c);  // writes it: on the context stream, after the pending reconstruction and front stages
+  } extra;
   bool extra_lazy = true;  // FOVRT_EXTRA_LAZY=0: every sampling writes EXTRA; also after fr_get_buffer(EXTRA) gave a view
-  FrameUniforms extra_U;
-  DevScene extra_sc;
-  int extra_depth = P_DEPTH_A, extra_nrm = P_NORMAL, extra_wgt = P_WEIGHT;
   int pp_S = 0;
   DevStats* stats = nullptr;
   FrameUniforms U;
@@ -350,15 +358,34 @@ struct fr_ctx {
   std::vector<int32_t> tex_dims, mat_pairs;
 };
 
-
-// Internal helpers of context.cpp used by group.cpp (same semantics as the ABI calls they back).
+// Helpers shared by the ctx_*.cpp files and group.cpp (same semantics as the ABI calls they back). What a frame calls
+// (frame_half and below) is defined in ctx_frame.cpp, so the per-frame host path stays in one translation unit.
 namespace fri {
-int fail(fr_ctx* c, int code, const std::string& msg);
+int fail(fr_ctx* c, int code, const std::string& msg);  // sets the error text (of fr_create when c is NULL)
 int check_launch(fr_ctx* c);
+// The context stream waits for every reconstruction still in flight (before any call that reads or
+// writes what the reconstruction uses, or hands buffers to the caller).
 void join_recon(fr_ctx* c);
+int quiesce(fr_ctx* c);  // join_recon, then the host waits for the context stream
 // one frame half on the context; trace / recon as fr_trace_frame / fr_reconstruct_frame (recon runs the
 // chains in c->recon_chains)
 int frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon);
-int P_shd(const fr_ctx* c);
-int P_wgt(const fr_ctx* c);
+int enqueue_shading(fr_ctx* c);  // entry 3 alone (the FR_STAMPS probes launch it)
+int P_pos(const fr_ctx* c), P_shd(const fr_ctx* c), P_wgt(const fr_ctx* c);  // this frame slot's physical images
+int resolve(fr_ctx* c, int id, int* phys);  // buffer id -> physical image, with the lazy outputs it names written
+void kt_harvest(fr_ctx* c, int i), fc_harvest(fr_ctx* c, int i);  // one ring entry of fr_kernel_timing / fr_frame_clock
+int gpu_rebuild(fr_ctx* c, const f3* pos);  // ctx_geometry.cpp
 }  // namespace fri
+
+#define HIP_TRY(ctx, expr)                                                                                      \
+  do {                                                                                                          \
+    hipError_t e_ = (expr);                                                                                     \
+    if (e_ != hipSuccess) return fri::fail(ctx, FR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+template <class T>
+inline hipError_t dalloc(T** p, size_t count) {
+  hipError_t e = hipMalloc((void**)p, count * sizeof(T) + 16);
+  if (e != hipSuccess) return e;
+  return hipMemset(*p, 0, count * sizeof(T) + 16);
+}

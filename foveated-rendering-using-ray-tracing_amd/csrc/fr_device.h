@@ -44,7 +44,7 @@ struct alignas(16) TriShade {
 #define FR_SHADE_HAS_NORMALS 0x100
 #define FR_SHADE_HAS_UV 0x200
 
-// Texel storage, the densest exact form per texture (context.cpp, pack_texture): RGBA32F; RGBA8 when
+// Texel storage, the densest exact form per texture (ctx_create.cpp, pack_texture): RGBA32F; RGBA8 when
 // every channel is exactly b / 255.0f (the 8-bit PPM / PNG textures sutil::loadTexture reads as
 // normalised bytes); RGBE when every texel is (m * 2^(e - 136), alpha 1) (the Radiance .hdr environment
 // map, FR/PathTracer.cpp:454-455). Decoding is exact (tex_texel, k_trace.hip): a lookup returns the

@@ -18,15 +18,15 @@ __constant__ float c_at_kernel[25] = {
 FR_DEV float gl_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504f); }
 
 // One atFS pass over a 16x16 block. TILE: position / normal / colour of the block plus its
-// 2*stepWidth halo are staged in LDS once (each texel is read by up to 25 pixels). POW2: c_phi,
-// n_phi, p_phi and stepWidth^2 are powers of two (always so in ATrous::render: 1, 2^-k, 1, 4^k), so
-// the divisions are exact multiplications by the reciprocal: bit-identical, without the division
-// sequence.
+// 2*stepWidth halo are staged in LDS once (each texel is read by up to 25 pixels). c_phi, n_phi,
+// p_phi and stepWidth^2 are powers of two (always so in ATrous::render: 1, 2^-k, 1, 4^k; launch_atrous
+// launches nothing otherwise), so the divisions are exact multiplications by the reciprocal:
+// bit-identical, without the division sequence.
 FR_DEV float at_dot(f4 t) {
   return __builtin_fmaf(t.w, t.w, __builtin_fmaf(t.z, t.z, __builtin_fmaf(t.y, t.y, t.x * t.x)));
 }
 
-template <bool TILE, bool POW2>
+template <bool TILE>
 __global__ __launch_bounds__(256) void k_atrous(const f4* __restrict__ pos, const f4* __restrict__ nrm,
                                                 const f4* __restrict__ col, f4* __restrict__ out, int W, int H,
                                                 float c_phi, float n_phi, float p_phi, float stepWidth) {
@@ -72,15 +72,15 @@ __global__ __launch_bounds__(256) void k_atrous(const f4* __restrict__ pos, cons
     f4 ctmp = TILE ? lc[lq] : col[q];
     f4 t = cval - ctmp;
     float dist2 = at_dot(t);
-    const float ec = fmaxf(POW2 ? dist2 * inv_c : dist2 / c_phi, 0.0f);
+    const float ec = fmaxf(dist2 * inv_c, 0.0f);
     f4 ntmp = TILE ? ln[lq] : nrm[q];
     t = nval - ntmp;
-    dist2 = fmaxf(POW2 ? at_dot(t) * inv_sw2 : at_dot(t) / (stepWidth * stepWidth), 0.0f);
-    const float en = fmaxf(POW2 ? dist2 * inv_n : dist2 / n_phi, 0.0f);
+    dist2 = fmaxf(at_dot(t) * inv_sw2, 0.0f);
+    const float en = fmaxf(dist2 * inv_n, 0.0f);
     f4 ptmp = TILE ? lp[lq] : pos[q];
     t = pval - ptmp;
     dist2 = at_dot(t);
-    const float ep = fmaxf(POW2 ? dist2 * inv_p : dist2 / p_phi, 0.0f);
+    const float ep = fmaxf(dist2 * inv_p, 0.0f);
     const float wk = gl_exp(-(ec + en + ep)) * c_at_kernel[i];
     sum = mk4(__builtin_fmaf(ctmp.x, wk, sum.x), __builtin_fmaf(ctmp.y, wk, sum.y), __builtin_fmaf(ctmp.z, wk, sum.z),
               __builtin_fmaf(ctmp.w, wk, sum.w));
@@ -94,26 +94,25 @@ __global__ __launch_bounds__(256) void k_atrous(const f4* __restrict__ pos, cons
 // 4 of their 6 texel rows, so each thread reads 6x5 position / normal / colour texels from LDS for
 // both pixels (45 ds_read_b128 per pixel instead of 75). Each pixel accumulates its own taps in
 // atFS order (rows from oy = +2 down to -2, ox ascending) with k_atrous's arithmetic, so the output
-// is bit-identical to k_atrous<true, POW2>. Interior blocks (every tap inside the image) run
+// is bit-identical to k_atrous<true>. Interior blocks (every tap inside the image) run
 // without bounds tests.
-template <bool POW2>
 FR_DEV float at_weight(f4 cval, f4 nval, f4 pval, f4 ctmp, f4 ntmp, f4 ptmp, float inv_c, float inv_n, float inv_p,
-                       float c_phi, float n_phi, float p_phi, float kern) {
+                       float kern) {
   f4 t = cval - ctmp;
   float dist2 = at_dot(t);
-  const float ec = fmaxf(POW2 ? dist2 * inv_c : dist2 / c_phi, 0.0f);
+  const float ec = fmaxf(dist2 * inv_c, 0.0f);
   t = nval - ntmp;
   dist2 = fmaxf(at_dot(t), 0.0f);  // stepWidth^2 = 1
-  const float en = fmaxf(POW2 ? dist2 * inv_n : dist2 / n_phi, 0.0f);
+  const float en = fmaxf(dist2 * inv_n, 0.0f);
   t = pval - ptmp;
   dist2 = at_dot(t);
-  const float ep = fmaxf(POW2 ? dist2 * inv_p : dist2 / p_phi, 0.0f);
+  const float ep = fmaxf(dist2 * inv_p, 0.0f);
   return gl_exp(-(ec + en + ep)) * kern;
 }
 
-template <bool POW2, bool CHECK>
+template <bool CHECK>
 FR_DEV void atrous_rows2(const f4* lp, const f4* ln, const f4* lc, int u, int v, int x, int y, int W, int H, float inv_c,
-                         float inv_n, float inv_p, float c_phi, float n_phi, float p_phi, f4& outA, f4& outB) {
+                         float inv_n, float inv_p, f4& outA, f4& outB) {
   constexpr int TW = 20;
   const int la = v * TW + u, lb = la + TW;
   const f4 cA = lc[la], nA = ln[la], pA = lp[la];
@@ -131,8 +130,7 @@ FR_DEV void atrous_rows2(const f4* lp, const f4* ln, const f4* lc, int u, int v,
       if (r >= 1) {
         const int oy = 3 - r;
         if (colok && (!CHECK || (y + oy >= 0 && y + oy < H))) {
-          const float wk = at_weight<POW2>(cA, nA, pA, c, n, p, inv_c, inv_n, inv_p, c_phi, n_phi, p_phi,
-                                           c_at_kernel[(2 - oy) * 5 + ox + 2]);
+          const float wk = at_weight(cA, nA, pA, c, n, p, inv_c, inv_n, inv_p, c_at_kernel[(2 - oy) * 5 + ox + 2]);
           sA = mk4(__builtin_fmaf(c.x, wk, sA.x), __builtin_fmaf(c.y, wk, sA.y), __builtin_fmaf(c.z, wk, sA.z),
                    __builtin_fmaf(c.w, wk, sA.w));
           wA += wk;
@@ -141,8 +139,7 @@ FR_DEV void atrous_rows2(const f4* lp, const f4* ln, const f4* lc, int u, int v,
       if (r <= 4) {
         const int oy = 2 - r;
         if (colok && (!CHECK || (y + 1 + oy >= 0 && y + 1 + oy < H))) {
-          const float wk = at_weight<POW2>(cB, nB, pB, c, n, p, inv_c, inv_n, inv_p, c_phi, n_phi, p_phi,
-                                           c_at_kernel[(2 - oy) * 5 + ox + 2]);
+          const float wk = at_weight(cB, nB, pB, c, n, p, inv_c, inv_n, inv_p, c_at_kernel[(2 - oy) * 5 + ox + 2]);
           sB = mk4(__builtin_fmaf(c.x, wk, sB.x), __builtin_fmaf(c.y, wk, sB.y), __builtin_fmaf(c.z, wk, sB.z),
                    __builtin_fmaf(c.w, wk, sB.w));
           wB += wk;
@@ -154,7 +151,6 @@ FR_DEV void atrous_rows2(const f4* lp, const f4* ln, const f4* lc, int u, int v,
   outB = sB / wB;
 }
 
-template <bool POW2>
 __global__ __launch_bounds__(256) void k_atrous_rows2(const f4* __restrict__ pos, const f4* __restrict__ nrm,
                                                       const f4* __restrict__ col, f4* __restrict__ out, int W, int H,
                                                       float c_phi, float n_phi, float p_phi, int xcd) {
@@ -178,8 +174,8 @@ __global__ __launch_bounds__(256) void k_atrous_rows2(const f4* __restrict__ pos
   const bool interior = ox0 >= 0 && oy0 >= 0 && ox0 + TW <= W && oy0 + TH <= H;  // block-uniform
   const float inv_c = 1.0f / c_phi, inv_n = 1.0f / n_phi, inv_p = 1.0f / p_phi;
   f4 a, b;
-  if (interior) atrous_rows2<POW2, false>(lp, ln, lc, u, v, x, y, W, H, inv_c, inv_n, inv_p, c_phi, n_phi, p_phi, a, b);
-  else atrous_rows2<POW2, true>(lp, ln, lc, u, v, x, y, W, H, inv_c, inv_n, inv_p, c_phi, n_phi, p_phi, a, b);
+  if (interior) atrous_rows2<false>(lp, ln, lc, u, v, x, y, W, H, inv_c, inv_n, inv_p, a, b);
+  else atrous_rows2<true>(lp, ln, lc, u, v, x, y, W, H, inv_c, inv_n, inv_p, a, b);
   out[(size_t)y * W + x] = a;
   if (y + 1 < H) out[(size_t)(y + 1) * W + x] = b;
 }
@@ -189,31 +185,28 @@ static bool pow2f(float v) {
   return v > 0.0f && std::isfinite(v) && std::frexp(v, &e) == 0.5f;
 }
 
-void launch_atrous(const f4* pos, const f4* nrm, const f4* col, f4* out, int W, int H, float c_phi, float n_phi,
+// false, with nothing launched: a phi or stepWidth^2 that is not a power of two (the kernels multiply by reciprocals)
+bool launch_atrous(const f4* pos, const f4* nrm, const f4* col, f4* out, int W, int H, float c_phi, float n_phi,
                    float p_phi, float stepWidth, bool rows2, int xcd, hipStream_t stream) {
   dim3 grid((W + 15) / 16, (H + 15) / 16);
   const bool pw = pow2f(c_phi) && pow2f(n_phi) && pow2f(p_phi) && pow2f(stepWidth * stepWidth) &&
                   pow2f(1.0f / c_phi) && pow2f(1.0f / n_phi) && pow2f(1.0f / p_phi) &&
                   pow2f(1.0f / (stepWidth * stepWidth));
+  if (!pw) return false;
   const int sw = (int)stepWidth;
   // rows2 = false (fr_ctx::atrous_rows2): k_atrous for the stepWidth-1 pass too (A/B of the two-row kernel)
   if (rows2 && stepWidth == 1.0f) {
     dim3 g2((W + 15) / 16, (H + 31) / 32);
-    if (pw) hipLaunchKernelGGL((k_atrous_rows2<true>), g2, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, xcd);
-    else hipLaunchKernelGGL((k_atrous_rows2<false>), g2, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, xcd);
-    return;
+    hipLaunchKernelGGL(k_atrous_rows2, g2, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, xcd);
+    return true;
   }
   const int tw = 16 + 4 * sw;
   const size_t lds = (size_t)3 * tw * tw * sizeof(f4);
-  const bool tile = sw >= 1 && lds <= 64 * 1024;
-  if (tile && pw)
-    hipLaunchKernelGGL((k_atrous<true, true>), grid, dim3(256), lds, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
-  else if (tile)
-    hipLaunchKernelGGL((k_atrous<true, false>), grid, dim3(256), lds, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
-  else if (pw)
-    hipLaunchKernelGGL((k_atrous<false, true>), grid, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
-  else
-    hipLaunchKernelGGL((k_atrous<false, false>), grid, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
+  if (sw >= 1 && lds <= 64 * 1024)
+    hipLaunchKernelGGL((k_atrous<true>), grid, dim3(256), lds, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
+  else  // (a halo beyond 64 KB of LDS: stepWidth >= 8)
+    hipLaunchKernelGGL((k_atrous<false>), grid, dim3(256), 0, stream, pos, nrm, col, out, W, H, c_phi, n_phi, p_phi, stepWidth);
+  return true;
 }
 
 }  // namespace fr

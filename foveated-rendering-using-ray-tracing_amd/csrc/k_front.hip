@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void k_sampling(FrameUniforms U, DevScene sc, 
   }
 }
 
-// The heat map a k_sampling launch left unwritten (context.cpp, materialize_extra_now): the same cell phase and
+// The heat map a k_sampling launch left unwritten (ctx_frame.cpp, fr_ctx::extra): the same cell phase and
 // per-pixel expressions over that launch's inputs (its uniforms, DIFFUSE, NORMAL, DEPTH and WEIGHT.xy, which
 // the sampling does not change), so EXTRA is what that launch would have stored, bit for bit.
 template <bool DEVBOX>

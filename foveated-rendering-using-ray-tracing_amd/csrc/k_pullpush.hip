@@ -33,27 +33,6 @@ FR_DEV f4 pp_pull(const PPArgs& a, int x, int y) {
   return a.pull[(size_t)y * a.AW + x];
 }
 
-// Pull level s (size 2^s at (S, 2^s - 1)) from level s+1 (or the input when s+1 == e).
-__global__ void k_pull_level(PPArgs a, int s) {
-  const int n = 1 << s;
-  const int total = n * n;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int lx = t % n, ly = t / n;
-    const int ox[4] = {0, 1, 1, 0}, oy[4] = {0, 0, 1, 1};
-    int hitCount = 0;
-    f4 f = mk4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      int cx = 2 * lx + ox[i], cy = 2 * ly + oy[i];
-      f4 r = (s + 1 == a.e) ? pp_in(a, cx, cy) : a.pull[(size_t)((1 << (s + 1)) - 1 + cy) * a.AW + a.S + cx];
-      if (r.w > 0.0f) { f = f + r; hitCount++; }
-    }
-    if (hitCount > 0) f = f / f.w;
-    f = mk4(f.x, f.y, f.z, hitCount > 0 ? 1.0f : 0.0f);
-    a.pull[(size_t)((1 << s) - 1 + ly) * a.AW + a.S + lx] = f;
-  }
-}
-
 // pullFS.glsl:48-75 for one texel: the children with alpha > 0 in offset order (0,0) (1,0) (1,1)
 // (0,1), summed, divided by the summed alpha; alpha = any child.
 FR_DEV f4 pull_combine(const f4 (&ch)[4]) {
@@ -68,8 +47,8 @@ FR_DEV f4 pull_combine(const f4 (&ch)[4]) {
 
 // Pull levels sl-1 .. sl-L (L <= 6) from level sl over 2^L x 2^L tiles of level sl: a block reduces
 // its tile through LDS and writes every level's texels to the atlas (the push stage reads them).
-// Same texel arithmetic as k_pull_level (pull_combine), so the atlas is bit-identical; the 12
-// dependent launches of the 4K pyramid become 2 (levels 11..6 over 64x64 input tiles, then 5..0).
+// Every texel is pull_combine of its four children, as in one launch per level, so the atlas is bit-identical;
+// the 12 dependent launches of the 4K pyramid become 2 (levels 11..6 over 64x64 input tiles, then 5..0).
 __global__ __launch_bounds__(256) void k_pull_tiles(PPArgs a, int sl, int L) {
   __shared__ f4 buf0[32 * 32];
   __shared__ f4 buf1[16 * 16];

@@ -998,7 +998,7 @@ FR_DEV f4 history_of(const FrameUniforms& U, const f4* __restrict__ weight, cons
 // draw the same r1, r2 and continue from the same seed. k_sample_setup evaluates
 // it once per pixel (tea16, the history gather, the two draws, the NDC pixel position) instead of once
 // per sample inside the megakernel's refill.
-// hvalid (the early form, context.cpp frame_half): instead of history_cache's .w, the bit k_carry_history of the
+// hvalid (the early form, ctx_frame.cpp frame_half): instead of history_cache's .w, the bit k_carry_history of the
 // previous frame computed for it (.w > 0 of the history that frame wrote, which is this frame's history_cache), so the
 // setup needs neither that frame's k_shade_resolve nor the history buffer: it runs with the frame's front stages.
 __global__ void k_sample_setup(FrameUniforms U, const uint32_t* __restrict__ active, const uint32_t* __restrict__ ray_count,
@@ -1648,7 +1648,7 @@ void launch_gbuffer(const DevScene& sc, const FrameUniforms& U, f4* position, f4
   int tiles = ((U.width + 7) / 8) * ((U.height + 7) / 8);
   int threads = tiles * 64;
   int blocks = (threads + TRACE_BLOCK - 1) / TRACE_BLOCK;
-  // the motion form when the caller gives both position arrays (context.cpp, enqueue_geometry)
+  // the motion form when the caller gives both position arrays (ctx_frame.cpp, enqueue_geometry)
   const bool motion = cur_pos && prev_pos;
   auto k = U.front_need ? (motion ? k_gbuffer<true, true> : k_gbuffer<true, false>)
                         : (motion ? k_gbuffer<false, true> : k_gbuffer<false, false>);

@@ -1,4 +1,4 @@
-"""Packed texture storage (csrc/context.cpp pack_texture, csrc/k_trace.hip tex_texel), checked on the CPU:
+"""Packed texture storage (csrc/ctx_create.cpp pack_texture, csrc/k_trace.hip tex_texel), checked on the CPU:
 the 8-bit textures (PPM / PNG, every channel b / 255.0f) are stored as RGBA8 and the Radiance environment map
 (load_hdr: m * 2^(e - 136)) as RGBE, and both decode to the RGBA32F texels bit for bit, so every lookup is
 unchanged. The device's byte decode is the reciprocal product with one fma correction, checked here for all
