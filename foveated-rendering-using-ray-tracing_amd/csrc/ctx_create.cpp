@@ -375,6 +375,7 @@ int fr_destroy(fr_ctx* c) {
   auto fr = [](void* p) { if (p) hipFree(p); };
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
   fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos);
+  fr(c->pose_rest_pos); fr(c->pose_rest_nrm); fr(c->pose_stage_pos); fr(c->pose_stage_nrm);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   if (c->nrm_work) normals_work_free(c->nrm_work);
   for (auto p : c->d_tex) fr(p);

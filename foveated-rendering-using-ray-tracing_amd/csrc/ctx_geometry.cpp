@@ -1,5 +1,6 @@
 // ctx_geometry.cpp — the scene's geometry after fr_create: the tree (GPU rebuild, refit, SAH cost), position and
-// normal updates (synchronous and in stream order), motion reprojection's switch, and the scene export calls.
+// normal updates (synchronous and in stream order), the model table and poses by matrix, motion reprojection's switch,
+// and the scene export calls.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -268,13 +269,14 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 // frame run on stream5, but entry 3 of that frame waits for them on the context stream (ev_front) before this
 // update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
 // The reconstruction streams read none of it, so they are not joined.
-int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event) {
-  if (!c) return FR_E_INVALID;
-  const std::string name = "fr_update_geometry_enqueue";
+// (pose: fr_set_model_transforms_enqueue, whose k_pose produces xyz and nrm, the staging arrays, on the context stream)
+static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, const void* nrm, size_t ntris, int normals,
+                          void* ready_event, const fr::PoseArgs* pose = nullptr) {
   if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
   if (int rc = check_update_args(c, name, ntris, FR_MEM_DEVICE, FR_BVH_REFIT, nrm, normals)) return rc;
   if (c->group_refs > 0 || c->U.shard_count > 1)
-    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_update_geometry)");
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use " +
+                                         (pose ? "fr_set_model_transforms)" : "fr_update_geometry)"));
   if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
   hipSetDevice(c->cfg.device);
   c->stream_dirty = true;  // the next pipelined frame's front stages (stream5) start after this update
@@ -283,6 +285,9 @@ int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size
   if (ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ready_event), 0));
   const int nt = (int)ntris;
   std::string err;
+  if (pose && !gpu_pose_enqueue(*pose, c->pose_rest_pos, c->pose_rest_nrm, c->pose_stage_pos, c->pose_stage_nrm, nt,
+                                c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
   if (!gpu_check_positions_enqueue(c->bvh_work, static_cast<const float*>(xyz), nt, c->stream, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   const bool given = normals == FR_NORMALS_GIVEN;
@@ -317,6 +322,11 @@ int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size
   return FR_OK;
 }
 
+int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event) {
+  if (!c) return FR_E_INVALID;
+  return enqueue_update(c, "fr_update_geometry_enqueue", xyz, nrm, ntris, normals, ready_event);
+}
+
 int fr_geometry_consumed(fr_ctx* c, void* stream) {
   if (!c) return FR_E_INVALID;
   if (!c->geo_read_pending) return FR_OK;
@@ -343,6 +353,113 @@ int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) 
   c->geo_rejected_seen[0] = g.rejected;
   c->geo_rejected_seen[1] = g.rejected_pos;
   c->geo_rejected_seen[2] = g.rejected_nrm;
+  return FR_OK;
+}
+
+// Model poses. The models are the contiguous triangle ranges add_mesh recorded (scene.cpp), in scene order.
+static int model_info(const HostScene& s, int i, const char** name, int* first_tri, int* ntris) {
+  if (i < 0 || i >= (int)s.model_tri_count.size()) return FR_E_INVALID;
+  int first = 0;
+  for (int k = 0; k < i; k++) first += s.model_tri_count[k];
+  if (name) *name = s.model_names[i].c_str();
+  if (first_tri) *first_tri = first;
+  if (ntris) *ntris = s.model_tri_count[i];
+  return FR_OK;
+}
+
+int fr_model_count(fr_ctx* c, int* n) {
+  if (!c || !n) return FR_E_INVALID;
+  *n = (int)c->scene.model_tri_count.size();
+  return FR_OK;
+}
+
+int fr_model_info(fr_ctx* c, int i, const char** name, int* first_tri, int* ntris) {
+  if (!c) return FR_E_INVALID;
+  if (model_info(c->scene, i, name, first_tri, ntris)) return fail(c, FR_E_INVALID, "fr_model_info: no such model");
+  return FR_OK;
+}
+
+static_assert(FR_MAX_MODELS == FR_POSE_MAX_MODELS, "k_pose's kernel arguments hold FR_MAX_MODELS models");
+
+int fr_model_pose_enable(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_model_pose_enable";
+  if (on != 0 && on != 1) return fail(c, FR_E_INVALID, name + ": on is 0 or 1");
+  if (!on) { c->pose_on = false; return FR_OK; }
+  const size_t nm = c->scene.model_tri_count.size();
+  if (nm > FR_MAX_MODELS) return fail(c, FR_E_UNSUPPORTED, name + ": the scene has more than FR_MAX_MODELS models");
+  if (int rc = quiesce(c)) return rc;
+  const int nt = c->scene.num_tris();
+  if (!c->pose_stage_nrm) {
+    f3** const arrays[4] = {&c->pose_rest_pos, &c->pose_rest_nrm, &c->pose_stage_pos, &c->pose_stage_nrm};
+    const size_t bytes = pose_array_bytes(std::max(nt, 1));
+    bool ok = true;
+    for (f3** p : arrays) ok = ok && hipMalloc((void**)p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (f3** p : arrays) { if (*p) hipFree(*p); *p = nullptr; }
+      return fail(c, FR_E_NOMEM, name + ": device allocation (rest and staging arrays) failed");
+    }
+  }
+  std::string err;
+  if (!gpu_pose_capture_enqueue(c->d_pos, c->d_shade, c->pose_rest_pos, c->pose_rest_nrm, nt, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->pose_m.assign(12 * nm, 0.0f);
+  for (size_t i = 0; i < nm; i++) c->pose_m[12 * i] = c->pose_m[12 * i + 5] = c->pose_m[12 * i + 10] = 1.0f;
+  c->pose_on = true;
+  return FR_OK;
+}
+
+// What the two pose calls refuse before anything is enqueued, and the kernel arguments of an accepted pose.
+static int check_pose(fr_ctx* c, const std::string& name, const float* m, size_t nmodels, fr::PoseArgs* args) {
+  if (!m) return fail(c, FR_E_INVALID, name + ": matrices are NULL");
+  if (!c->pose_on) return fail(c, FR_E_STATE, name + ": model poses are not enabled (fr_model_pose_enable)");
+  const size_t nm = c->scene.model_tri_count.size();
+  if (nmodels != nm) return fail(c, FR_E_INVALID, name + ": model count differs");
+  int first[FR_MAX_MODELS];
+  for (size_t i = 0; i < nm; i++) model_info(c->scene, (int)i, nullptr, &first[i], nullptr);
+  if (const char* why = pose_args(args, m, (int)nm, first)) return fail(c, FR_E_INVALID, name + ": " + why);
+  return FR_OK;
+}
+
+int fr_set_model_transforms(fr_ctx* c, const float* m, size_t nmodels, int how) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_model_transforms";
+  fr::PoseArgs args;
+  if (int rc = check_pose(c, name, m, nmodels, &args)) return rc;
+  if (how != FR_BVH_REBUILD && how != FR_BVH_REFIT) return fail(c, FR_E_INVALID, name + ": bad update kind");
+  if (int rc = quiesce(c)) return rc;
+  const int nt = c->scene.num_tris();
+  std::string err;
+  if (!gpu_pose_enqueue(args, c->pose_rest_pos, c->pose_rest_nrm, c->pose_stage_pos, c->pose_stage_nrm, nt, c->stream, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  if (int rc = update_positions(c, c->pose_stage_pos, (size_t)nt, FR_MEM_DEVICE, how, name.c_str(), c->pose_stage_nrm,
+                                FR_NORMALS_GIVEN))
+    return rc;
+  c->pose_m.assign(m, m + 12 * nmodels);
+  return FR_OK;
+}
+
+int fr_set_model_transforms_enqueue(fr_ctx* c, const float* m, size_t nmodels) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_model_transforms_enqueue";
+  fr::PoseArgs args;
+  if (int rc = check_pose(c, name, m, nmodels, &args)) return rc;
+  if (int rc = enqueue_update(c, name, c->pose_stage_pos, c->pose_stage_nrm, (size_t)c->scene.num_tris(),
+                              FR_NORMALS_GIVEN, nullptr, &args))
+    return rc;
+  c->pose_m.assign(m, m + 12 * nmodels);
+  return FR_OK;
+}
+
+int fr_model_transforms(fr_ctx* c, float* m, size_t nmodels) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_model_transforms";
+  if (!m) return fail(c, FR_E_INVALID, name + ": matrices are NULL");
+  if (!c->pose_on) return fail(c, FR_E_STATE, name + ": model poses are not enabled (fr_model_pose_enable)");
+  if (12 * nmodels != c->pose_m.size()) return fail(c, FR_E_INVALID, name + ": model count differs");
+  memcpy(m, c->pose_m.data(), c->pose_m.size() * sizeof(float));
   return FR_OK;
 }
 
@@ -518,6 +635,17 @@ int fr_scene_get_arrays(fr_scene* sc, fr_scene_arrays* o) {
 int fr_scene_normal_groups(fr_scene* sc, int32_t* corner_vertex, size_t ncorners, int* nverts) {
   if (!sc) return FR_E_INVALID;
   return copy_groups(sc->groups, corner_vertex, ncorners, nverts);
+}
+
+int fr_scene_model_count(fr_scene* sc, int* n) {
+  if (!sc || !n) return FR_E_INVALID;
+  *n = (int)sc->scene.model_tri_count.size();
+  return FR_OK;
+}
+
+int fr_scene_model_info(fr_scene* sc, int i, const char** name, int* first_tri, int* ntris) {
+  if (!sc) return FR_E_INVALID;
+  return model_info(sc->scene, i, name, first_tri, ntris);
 }
 
 // Test hook (not part of include/fovrt.h): the host-built tree of an fr_scene (pointers into it, valid until

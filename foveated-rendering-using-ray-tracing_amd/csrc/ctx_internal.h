@@ -86,6 +86,12 @@ bool gpu_scatter_normals(NormalsWork*, const float*, TriShade*, hipStream_t, std
 bool gpu_recompute_normals_enqueue(NormalsWork*, const f3*, TriShade*, const uint32_t*, hipStream_t, std::string&);
 bool gpu_check_normals_enqueue(NormalsWork*, const float*, uint32_t*, hipStream_t, std::string&);
 bool gpu_scatter_normals_enqueue(NormalsWork*, const float*, TriShade*, const uint32_t*, hipStream_t, std::string&);
+// model poses (k_pose.hip): a pose's kernel arguments (NULL, or why the pose is refused), the launch that writes the
+// posed rest arrays into the staging arrays, the capture of the rest arrays, and the bytes of one such array
+const char* pose_args(PoseArgs*, const float*, int, const int*);
+bool gpu_pose_enqueue(const PoseArgs&, const f3*, const f3*, f3*, f3*, int, hipStream_t, std::string&);
+bool gpu_pose_capture_enqueue(const f3*, const TriShade*, f3*, f3*, int, hipStream_t, std::string&);
+size_t pose_array_bytes(int);
 #ifdef FR_STAMPS
 void launch_trace_queries(const DevScene&, const f4*, uint32_t, f4*, uint32_t*, hipStream_t, int);
 void diag_record_queries(f4*, uint32_t, hipStream_t);
@@ -230,6 +236,13 @@ struct fr_ctx {
   bool geo_read_pending = false;
   bool box_mirror_stale = false;
   unsigned long long geo_rejected_seen[3] = {};
+  // Model poses (fr_model_pose_enable, fr_set_model_transforms). Four arrays of 9 floats per triangle, made by the
+  // first enable: the rest geometry a pose is relative to (positions, and d_shade's normals expanded) and the
+  // staging arrays k_pose writes and the update path then reads as a caller's device arrays. All four are read
+  // and written on the context stream only. pose_m: the pose last submitted, 12 floats per model.
+  f3 *pose_rest_pos = nullptr, *pose_rest_nrm = nullptr, *pose_stage_pos = nullptr, *pose_stage_nrm = nullptr;
+  bool pose_on = false;
+  std::vector<float> pose_m;
   int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
   // the smooth-vertex weld of the scene as fr_create built it (host), and on the device with the scratch of

@@ -104,6 +104,16 @@ struct GeoUpdateState {
   float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
 };
 
+// A pose of the scene's models (fr_set_model_transforms), passed to k_pose by value: everything the kernel needs
+// travels in its kernel arguments (1.4 KB), so a pose costs no copy to the device and keeps nothing alive.
+#define FR_POSE_MAX_MODELS 16  // FR_MAX_MODELS of include/fovrt.h
+struct PoseArgs {
+  int32_t first_tri[FR_POSE_MAX_MODELS];  // model i holds triangles [first_tri[i], first_tri[i + 1]); unused: INT32_MAX
+  uint32_t identity;                      // bit i: model i's matrix is the identity (it takes its rest bits)
+  float M[FR_POSE_MAX_MODELS][12];        // row-major 3 x 4: v' = A v + t
+  float K[FR_POSE_MAX_MODELS][9];         // cofactors of A, row-major (pose_args)
+};
+
 // Per-frame uniforms (FR/PathTracer.cpp:85-116, 774-820).
 struct FrameUniforms {
   mat4 inv_vp;              // "mvp" on the device: inverse(P*V), row-major

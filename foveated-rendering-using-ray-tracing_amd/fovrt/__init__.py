@@ -181,6 +181,14 @@ _SIGS = {
     "fr_update_geometry_enqueue": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "fr_geometry_consumed": [C.c_void_p, C.c_void_p],
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "fr_model_count": [C.c_void_p, C.POINTER(C.c_int)],
+    "fr_model_info": [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "fr_scene_model_count": [C.c_void_p, C.POINTER(C.c_int)],
+    "fr_scene_model_info": [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "fr_model_pose_enable": [C.c_void_p, C.c_int],
+    "fr_set_model_transforms": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int],
+    "fr_set_model_transforms_enqueue": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
+    "fr_model_transforms": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -691,6 +699,40 @@ class PathTracer:
         self._check(_lib.fr_geometry_update_status(self._ctx, C.byref(a), C.byref(r)))
         return a.value, r.value
 
+    def models(self):
+        """[(name, first_tri, ntris)]: the scene's models, contiguous triangle ranges in scene order."""
+        return _models(_lib.fr_model_count, _lib.fr_model_info, self._ctx, self._check)
+
+    def enable_model_pose(self, on=True):
+        """fr_model_pose_enable: captures the current device positions and normals as the rest geometry that
+        set_model_transforms poses (four device arrays of 36 B per triangle at the first call); calling it again
+        captures again. on=False: the pose calls fail (FR_E_STATE) until the next enable."""
+        self._check(_lib.fr_model_pose_enable(self._ctx, int(bool(on))))
+
+    def set_model_transforms(self, m, update="refit", enqueue=False):
+        """One row-major 3 x 4 matrix per model (float32, shape (nmodels, 3, 4) or (nmodels, 12)), v' = A v + t
+        over the rest geometry: positions and normals are posed on the device and taken as by set_positions_device
+        with given normals (fr_set_model_transforms), or with enqueue=True in stream order without waiting for the
+        GPU, always a refit (fr_set_model_transforms_enqueue; geometry_update_status() counts it)."""
+        a = np.ascontiguousarray(m, dtype=np.float32)
+        if a.ndim < 2 or a.size != a.shape[0] * 12:
+            raise ValueError(f"m has shape {a.shape}, not (nmodels, 3, 4) or (nmodels, 12)")
+        p = a.ctypes.data_as(C.POINTER(C.c_float))
+        if enqueue:
+            if self._update_kind(update) != FR_BVH_REFIT:
+                raise ValueError("an enqueued pose always refits")
+            self._check(_lib.fr_set_model_transforms_enqueue(self._ctx, p, a.shape[0]))
+        else:
+            self._check(_lib.fr_set_model_transforms(self._ctx, p, a.shape[0], self._update_kind(update)))
+
+    def model_transforms(self) -> np.ndarray:
+        """The pose last submitted, shape (nmodels, 3, 4) (identities after enable_model_pose)."""
+        n = C.c_int()
+        self._check(_lib.fr_model_count(self._ctx, C.byref(n)))
+        m = np.empty((n.value, 3, 4), np.float32)
+        self._check(_lib.fr_model_transforms(self._ctx, m.ctypes.data_as(C.POINTER(C.c_float)), n.value))
+        return m
+
     def set_normals(self, nrm: np.ndarray):
         """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have
         normals; positions, tree, texture coordinates and flags stay."""
@@ -789,6 +831,17 @@ class PathTracer:
         return _arrays_to_dict(a)
 
 
+def _models(count_fn, info_fn, handle, check):
+    n = C.c_int()
+    check(count_fn(handle, C.byref(n)))
+    out = []
+    for i in range(n.value):
+        name, first, nt = C.c_char_p(), C.c_int(), C.c_int()
+        check(info_fn(handle, i, C.byref(name), C.byref(first), C.byref(nt)))
+        out.append((name.value.decode(), first.value, nt.value))
+    return out
+
+
 def _arrays_to_dict(a: fr_scene_arrays) -> dict:
         n = a.num_tris
         tex = []
@@ -829,6 +882,13 @@ class Scene:
         if rc:
             raise FovrtError(rc, "fr_scene_get_arrays")
         return _arrays_to_dict(a)
+
+    def models(self):
+        """[(name, first_tri, ntris)] as PathTracer.models, on the host."""
+        def check(rc):
+            if rc:
+                raise FovrtError(rc, "fr_scene_model_info")
+        return _models(_lib.fr_scene_model_count, _lib.fr_scene_model_info, self._h, check)
 
     def normal_groups(self):
         """(corner_vertex, nverts) as PathTracer.normal_groups, on the host."""

@@ -477,6 +477,56 @@ int fr_update_geometry_enqueue(fr_ctx* ctx, const void* xyz, const void* nrm, si
                                void* ready_event);
 int fr_geometry_consumed(fr_ctx* ctx, void* stream);
 int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected);
+/* The scene's models, posed by matrix on the device. A scene is assembled from rigid models (ground, box, bunny,
+ * earth, vokselia_spawn: PathTracer::load_obj's meshes with their transforms baked in), each a contiguous range of
+ * the scene's triangles. The ranges partition [0, num_tris) in scene order: fr_model_count gives their number,
+ * fr_model_info one model's name (borrowed, valid for the life of the context), first triangle and triangle
+ * count (any of the three pointers may be NULL); FR_E_INVALID for a NULL context or an index outside the table.
+ * A pose is one matrix per model, 12 floats each, row-major 3 x 4: M[r][0..3], v' = A v + t, relative to the rest
+ * geometry (below). A posed array has one right answer in bytes. fp32, every operation rounded on its own, no
+ * fma, for a corner (p, n) of a model whose matrix is not the identity:
+ *   p'.c = ((M[c][0] p.x + M[c][1] p.y) + M[c][2] p.z) + M[c][3]                                    c = 0, 1, 2
+ *   K[r][c] = A[r1][c1] A[r2][c2] - A[r1][c2] A[r2][c1]     (r1, r2) = ((r + 1) % 3, (r + 2) % 3), (c1, c2) likewise
+ *   n'.c = (K[c][0] n.x + K[c][1] n.y) + K[c][2] n.z
+ *   det = (A[0][0] K[0][0] + A[0][1] K[0][1]) + A[0][2] K[0][2]
+ * K is the cofactor matrix, det times the inverse transpose, so with det > 0 a normal keeps the direction the
+ * inverse transpose gives it; normals are not renormalised (the shader normalises where it reads them). A model
+ * is at the identity when its 12 floats compare equal (==, so -0 counts as 0) to (1,0,0,0, 0,1,0,0, 0,0,1,0): it
+ * takes its rest positions and rest normals bit for bit (the arithmetic would turn a -0 coordinate into +0).
+ * Triangles without normals (flags & 0x100 clear) keep what they have, as in every update with given normals.
+ * Rest geometry: fr_model_pose_enable(ctx, 1) waits for the context's pending work, allocates at its first call
+ * four device arrays of 36 B per triangle (rest positions, rest normals, and the two arrays the posed geometry is
+ * staged in; FR_E_NOMEM, with nothing kept), captures the current device positions and normals as rest and
+ * resets the stored pose to identities. Calling it again captures again: that is how a mesh deformed through
+ * fr_update_positions is posed. on = 0 makes the pose calls return FR_E_STATE until the next on = 1; it frees
+ * nothing and changes nothing of the scene. A scene of more than FR_MAX_MODELS models: FR_E_UNSUPPORTED. No pose
+ * call allocates.
+ * fr_set_model_transforms computes X and N, the posed rest positions and normals, on the device (one kernel,
+ * the matrices travel in its arguments: no copy, nothing of the caller's is read after the call returns) and then
+ * is fr_update_geometry(X, N, ntris, FR_MEM_DEVICE, how, FR_NORMALS_GIVEN): every later frame, positions,
+ * normals, tree, scene box and fr_bvh_sah_cost are byte for byte what that call leaves, a pose counts as a
+ * position update for fr_set_motion_reprojection, and like it the call waits for the context's pending work.
+ * fr_set_model_transforms_enqueue is the same against fr_update_geometry_enqueue(X, N, ntris, FR_NORMALS_GIVEN,
+ * NULL): a refit in stream order with no host wait, which a caller without device code of their own can use
+ * before every frame; consecutive poses need no event and no fr_geometry_consumed (the staged arrays belong to
+ * the context). fr_model_transforms returns the pose last submitted (identities after an enable).
+ * Refused at once, with nothing enqueued and the scene untouched: a NULL context or NULL m, nmodels other than
+ * the model count, a bad `how`, a float of m that is not finite, a model whose det (the rule above) is not finite
+ * or is <= 0 (a mirrored model flips the triangle winding, and with it the geometric normal refraction depends
+ * on): FR_E_INVALID; posing not enabled: FR_E_STATE; for the enqueued form a rank of a group or a sharded
+ * context: FR_E_UNSUPPORTED (the synchronous form works on a group's contexts one by one).
+ * A finite pose can still overflow the positions. That is caught where fr_update_geometry catches an array that
+ * is not finite: the synchronous call returns FR_E_INVALID, the enqueued one is rejected on the device and
+ * counted by fr_geometry_update_status; both leave the scene untouched.
+ * Not covered: per-model visibility or materials, instancing, a two-level tree, changed triangle counts, groups
+ * in stream order. */
+#define FR_MAX_MODELS 16
+int fr_model_count(fr_ctx* ctx, int* n);
+int fr_model_info(fr_ctx* ctx, int i, const char** name, int* first_tri, int* ntris);
+int fr_model_pose_enable(fr_ctx* ctx, int on);
+int fr_set_model_transforms(fr_ctx* ctx, const float* m, size_t nmodels, int how);  /* FR_BVH_REFIT | FR_BVH_REBUILD */
+int fr_set_model_transforms_enqueue(fr_ctx* ctx, const float* m, size_t nmodels);
+int fr_model_transforms(fr_ctx* ctx, float* m, size_t nmodels);
 /* History that follows moving geometry (off by default). The G-buffer reprojects a hit point with the previous
  * camera, and the sampling stage accepts the history there only when the depth stored a frame ago equals the
  * point's distance from the previous eye: both assume the point stood still. With motion reprojection on, the
@@ -569,6 +619,8 @@ typedef struct fr_scene fr_scene;
 int fr_scene_create(const fr_config* cfg, fr_scene** out);
 int fr_scene_get_arrays(fr_scene* scene, fr_scene_arrays* out);
 int fr_scene_normal_groups(fr_scene* scene, int32_t* corner_vertex, size_t ncorners, int* nverts);  /* fr_normal_groups */
+int fr_scene_model_count(fr_scene* scene, int* n);  /* fr_model_count */
+int fr_scene_model_info(fr_scene* scene, int i, const char** name, int* first_tri, int* ntris);  /* fr_model_info */
 int fr_scene_destroy(fr_scene* scene);
 
 #ifdef __cplusplus

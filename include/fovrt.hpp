@@ -190,6 +190,40 @@ class PathTracer {
   void geometry_update_status(uint64_t* applied, uint64_t* rejected) {
     check(fr_geometry_update_status(ctx(), applied, rejected), ctx_, "geometry_update_status");
   }
+  // The scene's models (load_obj's meshes, FR/PathTracer.cpp:604-772): contiguous triangle ranges in scene order.
+  struct Model {
+    std::string name;
+    int first_tri, ntris;
+  };
+  std::vector<Model> models() {
+    int n = 0;
+    check(fr_model_count(ctx(), &n), ctx_, "models");
+    std::vector<Model> out(static_cast<size_t>(n));
+    for (int i = 0; i < n; i++) {
+      const char* name = nullptr;
+      check(fr_model_info(ctx(), i, &name, &out[i].first_tri, &out[i].ntris), ctx_, "models");
+      out[i].name = name;
+    }
+    return out;
+  }
+  // Poses by matrix (fr_set_model_transforms): enable captures the current geometry as rest; m holds one row-major
+  // 3 x 4 matrix per model (v' = A v + t over the rest geometry), posed on the device and taken as update_geometry
+  // with given normals, or in stream order without waiting for the GPU (the enqueued form, always a refit).
+  void enable_model_pose(bool on = true) { check(fr_model_pose_enable(ctx(), on ? 1 : 0), ctx_, "enable_model_pose"); }
+  void set_model_transforms(const std::vector<std::array<float, 12>>& m, int how = FR_BVH_REFIT) {
+    check(fr_set_model_transforms(ctx(), m.empty() ? nullptr : m[0].data(), m.size(), how), ctx_, "set_model_transforms");
+  }
+  void set_model_transforms_enqueue(const std::vector<std::array<float, 12>>& m) {
+    check(fr_set_model_transforms_enqueue(ctx(), m.empty() ? nullptr : m[0].data(), m.size()), ctx_,
+          "set_model_transforms_enqueue");
+  }
+  std::vector<std::array<float, 12>> model_transforms() {  // the pose last submitted
+    int n = 0;
+    check(fr_model_count(ctx(), &n), ctx_, "model_transforms");
+    std::vector<std::array<float, 12>> m(static_cast<size_t>(n));
+    check(fr_model_transforms(ctx(), n ? m[0].data() : nullptr, m.size()), ctx_, "model_transforms");
+    return m;
+  }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
