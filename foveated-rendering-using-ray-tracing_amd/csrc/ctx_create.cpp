@@ -88,7 +88,8 @@ static int pack_texture(const HostTexture& t, std::vector<uint32_t>& out) {
 
 // The FOVRT_* environment knobs of a context, read once per fr_create; the kernels' launchers take them as arguments.
 // (Read where they act instead: the host BVH builder's in scene.cpp, FOVRT_BVH_PHASES in k_bvh.hip, FOVRT_DIAG_DUMP
-// in fr_diag_trace_queries, and once per process FOVRT_LAT_OVERLAP in frame_half and FOVRT_GROUP_VRING in group.cpp.)
+// in fr_diag_trace_queries, and once per process FOVRT_LAT_OVERLAP in wait_for_previous_frame (ctx_frame.cpp) and
+// FOVRT_GROUP_VRING in group.cpp.)
 static void read_env_knobs(fr_ctx* c) {
   if (const char* v = getenv("FOVRT_SHADE_CHUNK_REFR")) c->chunk_refr = (uint32_t)std::max(0, atoi(v));
   if (const char* v = getenv("FOVRT_SHADE_XCD_BANDS")) c->xcd_bands = atoi(v) != 0;
@@ -109,6 +110,19 @@ static void read_env_knobs(fr_ctx* c) {
   if (const char* v = getenv("FOVRT_SIB_STRIP_MID")) c->sib_strip_mid = atoi(v);
   if (const char* v = getenv("FOVRT_ATROUS_ROWS2")) c->atrous_rows2 = atoi(v) != 0;
   if (const char* v = getenv("FOVRT_ATROUS_XCD")) c->atrous_xcd = atoi(v) != 0;
+}
+
+// The context's events that can be timed (plain hipEventCreate): the stage timing, the ordering events inside a frame
+// and latency mode's schedule. fr_create makes them, fr_destroy destroys them.
+static std::vector<hipEvent_t*> timed_events(fr_ctx* c) {
+  fr_ctx::StageEvents& t = c->tev;
+  std::vector<hipEvent_t*> v = {&t.begin, &t.geometry, &t.sampling, &t.optimize, &t.shading, &t.end, &t.paths_begin,
+                                &t.paths_end, &t.chain2_begin, &t.pullpush, &t.atrous, &t.chain1_begin, &t.jfa,
+                                &t.sibson, &t.stage_begin, &t.stage_end, &c->ev_carry_fork, &c->ev_carry_done,
+                                &c->ev_recon_fork, &c->ev_chain2_done, &c->ev_stream_join};
+  for (auto& s : c->lat.ev)
+    for (hipEvent_t* e : {&s.front_begin, &s.front_end, &s.jfa_end, &s.recon_end}) v.push_back(e);
+  return v;
 }
 
 int fr_create(const fr_config* cfg_in, fr_ctx** out) {
@@ -138,20 +152,20 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   c->W = cfg.width; c->H = cfg.height;
   auto bail = [&](int code) { g_create_error = c->err; fr_destroy(c); return code; };
   if (hipSetDevice(cfg.device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(FR_E_HIP); }
-  for (hipStream_t* st : {&c->stream, &c->stream2, &c->stream3, &c->stream4, &c->stream5}) {
+  // (this order: five streams share four hardware queues by default)
+  for (hipStream_t* st : {&c->stream, &c->atrous_stream, &c->sibson_stream, &c->carry_stream, &c->front_stream}) {
     if (hipStreamCreateWithPriority(st, hipStreamNonBlocking, 0) != hipSuccess) {
       c->err = "stream create failed";
       return bail(FR_E_HIP);
     }
   }
-  for (auto& e : c->ev) hipEventCreate(&e);
-  hipEventCreateWithFlags(&c->ev_front, hipEventDisableTiming);
-  for (auto& e : c->ev_trace) hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  for (auto& e : c->ev_recon) hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  for (auto& e : c->ev_jfa) hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  for (auto& row : c->lat_ev) for (auto& e : row) hipEventCreate(&e);
+  for (hipEvent_t* e : timed_events(c)) hipEventCreate(e);
+  hipEventCreateWithFlags(&c->front_done.ev, hipEventDisableTiming);
+  for (auto& f : c->trace_done) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
+  for (auto& f : c->recon_done) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
+  for (auto& f : c->jfa_done) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
   for (auto& e : c->ev_counts) hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  hipEventCreateWithFlags(&c->ev_geo_read, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->geo_read.ev, hipEventDisableTiming);
   read_env_knobs(c);
 
   std::string err;
@@ -370,7 +384,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
 int fr_destroy(fr_ctx* c) {
   if (!c) return FR_E_INVALID;
   hipSetDevice(c->cfg.device);
-  const hipStream_t streams[5] = {c->stream, c->stream2, c->stream3, c->stream4, c->stream5};
+  const hipStream_t streams[5] = {c->stream, c->atrous_stream, c->sibson_stream, c->carry_stream, c->front_stream};
   for (hipStream_t s : streams) if (s) hipStreamSynchronize(s);
   auto fr = [](void* p) { if (p) hipFree(p); };
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
@@ -386,16 +400,15 @@ int fr_destroy(fr_ctx* c) {
   if (c->h_counts) hipHostFree(c->h_counts);
   fr(c->geo);
   if (c->h_geo) hipHostFree(c->h_geo);
-  if (c->ev_geo_read) hipEventDestroy(c->ev_geo_read);
+  if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
   for (auto e : c->ev_counts) if (e) hipEventDestroy(e);
   fr(c->gclass); fr(c->lp_cache); fr(c->lp_inv); fr(c->words); fr(c->counts); fr(c->offsets); fr(c->tiles); fr(c->shade_ctr); fr(c->samples); fr(c->sample_help); fr(c->aux_p[0]); fr(c->aux_p[1]); fr(c->aux_seed_p[0]); fr(c->aux_seed_p[1]); fr(c->hvalid); fr(c->item_store); fr(c->jfa_a); fr(c->jfa_b); fr(c->ftab);
   fr(c->pull); fr(c->push); fr(c->snap); fr(c->stats); fr(c->sib_prefix); fr(c->sib_blocks); fr(c->sib_wide); fr(c->sib_strips); fr(c->sib_rowp);
-  for (auto e : c->ev) if (e) hipEventDestroy(e);
-  if (c->ev_front) hipEventDestroy(c->ev_front);
-  for (auto e : c->ev_trace) if (e) hipEventDestroy(e);
-  for (auto e : c->ev_recon) if (e) hipEventDestroy(e);
-  for (auto e : c->ev_jfa) if (e) hipEventDestroy(e);
-  for (auto& row : c->lat_ev) for (auto e : row) if (e) hipEventDestroy(e);
+  for (hipEvent_t* e : timed_events(c)) if (*e) hipEventDestroy(*e);
+  if (c->front_done.ev) hipEventDestroy(c->front_done.ev);
+  for (auto& f : c->trace_done) if (f.ev) hipEventDestroy(f.ev);
+  for (auto& f : c->recon_done) if (f.ev) hipEventDestroy(f.ev);
+  for (auto& f : c->jfa_done) if (f.ev) hipEventDestroy(f.ev);
   for (auto& q : c->kt_ev)
     for (auto e : q) if (e) hipEventDestroy(e);
   for (auto& q : c->fc_ev)

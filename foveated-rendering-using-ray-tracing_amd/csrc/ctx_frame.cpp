@@ -72,9 +72,8 @@ void fc_harvest(fr_ctx* c, int i) {
 
 void join_recon(fr_ctx* c) {
   c->stream_dirty = true;  // the caller is about to enqueue on `stream` outside a pipelined frame
-  for (int k = 0; k < fr_ctx::MAX_SLOTS; k++)
-    if (c->recon_pending[k]) { hipStreamWaitEvent(c->stream, c->ev_recon[k], 0); c->recon_pending[k] = false; }
-  if (c->front_pending) { hipStreamWaitEvent(c->stream, c->ev_front, 0); c->front_pending = false; }
+  for (Fence& f : c->recon_done) f.consume(c->stream);
+  c->front_done.consume(c->stream);
 }
 
 int quiesce(fr_ctx* c) {
@@ -85,22 +84,16 @@ int quiesce(fr_ctx* c) {
 }
 }  // namespace fri
 
-// fs: the stream of the front stages (entries 0-2): `stream`, or stream5 in a pipelined frame.
+// fs: the stream of the front stages (entries 0-2): `stream`, or front_stream in a pipelined frame.
 static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
   // a new frame: move to the next slot, once the reconstruction that read it has finished
   c->slot = (c->slot + 1) % c->nslots;
   c->setup_early = false;
   const int sl = c->slot;
   c->mask = c->mask_p[sl]; c->active = c->active_p[sl]; c->ray_count = c->ray_count_p[sl];
-  if (c->recon_pending[sl]) {
-    hipStreamWaitEvent(fs, c->ev_recon[sl], 0);  // entry 3 on `stream` waits for fs (ev_front)
-    c->recon_pending[sl] = false;
-  }
-  if (fs != c->stream && c->trace_pending[sl]) {
-    hipStreamWaitEvent(fs, c->ev_trace[sl], 0);
-    c->trace_pending[sl] = false;
-  }
-  if (c->lat_arm) hipEventRecord(c->lat_ev[sl][0], fs);
+  c->recon_done[sl].consume(fs);  // entry 3 on `stream` waits for fs (front_done)
+  if (fs != c->stream) c->trace_done[sl].consume(fs);
+  if (c->lat.arm) hipEventRecord(c->lat.ev[sl].front_begin, fs);
   if (c->fc_arm) {  // fr_frame_clock: where this frame's G-buffer (the first stage to read the gaze) may start
     const int i = c->fc_next;
     if (c->fc_pending == fr_ctx::FC_RING) { fc_harvest(c, i); c->fc_pending--; }
@@ -179,10 +172,7 @@ int fri::enqueue_shading(fr_ctx* c) {
   if (!c->compacted) {  // g_isOptimize = 0: the active list is still needed by this design
     if (int rc = enqueue_optimize(c, c->stream)) return rc;
   }
-  if (c->front_pending) {  // a pipelined frame: entry 3 waits for its own front stages
-    hipStreamWaitEvent(c->stream, c->ev_front, 0);
-    c->front_pending = false;
-  }
+  c->front_done.consume(c->stream);  // a pipelined frame: entry 3 waits for its own front stages
   hipEvent_t* kt = nullptr;
   if (c->kt_on) {
     const int i = c->kt_next;
@@ -201,33 +191,33 @@ int fri::enqueue_shading(fr_ctx* c) {
   const bool early = c->setup_early;
   c->setup_early = false;
   // The inactive pixels' history carry (HBM-bound) touches no buffer k_shade_paths reads or writes:
-  // it runs on stream4 beside the latency-bound megakernel and joins before the resolve. In latency mode, with one
+  // it runs on carry_stream beside the latency-bound megakernel and joins before the resolve. In latency mode, with one
   // untiled view, it also writes the validity bits of the history this frame leaves (the next frame's early setup).
   const bool hv = c->pipeline_mode == FR_PIPELINE_LATENCY && c->early_setup && c->U.shard_count <= 1 && !c->U.front_need;
-  hipEventRecord(c->ev[11], c->stream);
-  hipStreamWaitEvent(c->stream4, c->ev[11], 0);
+  hipEventRecord(c->ev_carry_fork, c->stream);
+  hipStreamWaitEvent(c->carry_stream, c->ev_carry_fork, 0);
   launch_carry_history(c->U, c->mask, c->img[P_wgt(c)], c->img[c->hist_cache], c->img[c->hist_cur],
-                       c->img[P_shd(c)], hv ? c->hvalid : nullptr, c->stream4);
-  hipEventRecord(c->ev[12], c->stream4);
+                       c->img[P_shd(c)], hv ? c->hvalid : nullptr, c->carry_stream);
+  // (the next frame's early sample setup waits for this record as well: frame_half)
+  hipEventRecord(c->ev_carry_done, c->carry_stream);
   const uint32_t N = (uint32_t)((size_t)c->W * c->H);
   if (!early)
     launch_sample_setup(c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache], nullptr, c->aux,
                         c->aux_seed, c->stream);
-  if (c->time_kernels) hipEventRecord(c->ev[9], c->stream);
+  if (c->time_kernels) hipEventRecord(c->tev.paths_begin, c->stream);
   if (kt) hipEventRecord(kt[1], c->stream);
   launch_shade_paths(c->dsc, c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache],
                      c->shade_ctr, c->samples, c->sample_help, c->stats, c->aux, c->aux_seed, c->chunk_refr,
                      c->xcd_bands, c->handoff, c->shade_blocks_per_cu, c->item_store, c->stream);
-  if (c->time_kernels) hipEventRecord(c->ev[10], c->stream);
+  if (c->time_kernels) hipEventRecord(c->tev.paths_end, c->stream);
   if (kt) hipEventRecord(kt[2], c->stream);
-  hipStreamWaitEvent(c->stream, c->ev[12], 0);
+  hipStreamWaitEvent(c->stream, c->ev_carry_done, 0);
   launch_shade_resolve(c->U, c->active, c->ray_count, N, c->img[P_wgt(c)], c->img[c->hist_cache], c->samples,
                        c->sample_help, c->img[c->hist_cur], c->img[P_shd(c)], c->shade_ctr, c->handoff,
                        c->shade_blocks_per_cu, c->U.shard_count > 1 ? c->shade_radiance : nullptr, c->stream);
   if (kt) hipEventRecord(kt[3], c->stream);
   // this slot's WEIGHT / mask / active list are free for the front stages of frame + nslots after this
-  hipEventRecord(c->ev_trace[c->slot], c->stream);
-  c->trace_pending[c->slot] = true;
+  c->trace_done[c->slot].record(c->stream);
   int rc = check_launch(c);
   // swapBuffer("history_cache", "history_buffer"); swapBuffer("depth_cache", "depth_buffer") (:226-227)
   std::swap(c->hist_cur, c->hist_cache);
@@ -354,12 +344,67 @@ static int enqueue_atrous(fr_ctx* c, int count, int pos, int nrm, int col, hipSt
 static int timed(fr_ctx* c, const std::function<int()>& f, float* ms) {
   hipSetDevice(c->cfg.device);
   join_recon(c);
-  hipEventRecord(c->ev[0], c->stream);
+  hipEventRecord(c->tev.stage_begin, c->stream);
   if (int rc = f()) return rc;
-  hipEventRecord(c->ev[1], c->stream);
-  hipError_t e = hipEventSynchronize(c->ev[1]);
+  hipEventRecord(c->tev.stage_end, c->stream);
+  hipError_t e = hipEventSynchronize(c->tev.stage_end);
   if (e != hipSuccess) return fail(c, FR_E_HIP, std::string("stage failed: ") + hipGetErrorString(e));
-  if (ms) *ms = elapsed(c->ev[0], c->ev[1]);
+  if (ms) *ms = elapsed(c->tev.stage_begin, c->tev.stage_end);
+  return FR_OK;
+}
+
+// Latency mode, before a frame is enqueued: one frame ahead at most. The host waits until the previous frame's
+// (slot prev's) JumpFlooding has ended (its path trace, when this context does not run that chain), then the caller
+// samples the gaze and enqueues this frame, whose front stages (G-buffer, sampling, compaction) overlap the previous
+// frame's Sibson and pull-push -> A-Trous; its path trace starts after them (frame_half).
+// (polled: a blocking wait woke the host up to milliseconds late, and the GPU idled meanwhile)
+static int wait_for_previous_frame(fr_ctx* c, int prev) {
+  if (!c->jfa_done[prev].pending && !c->trace_done[prev].pending) return FR_OK;
+  fr_ctx::LatSchedule& L = c->lat;
+  hipEvent_t w = c->jfa_done[prev].pending ? c->jfa_done[prev].ev : c->trace_done[prev].ev;
+  hipError_t e;
+  if ((e = poll_event(w, kPollDeadlineMs)) != hipSuccess)
+    return fail(c, FR_E_HIP, e == hipErrorNotReady ? std::string("frame failed: the previous frame did not complete within the poll deadline")
+                                                    : std::string("frame failed: ") + hipGetErrorString(e));
+  // Just in time: the front stages should end about when the previous frame's Sibson does (its path
+  // trace waits for both). A completed frame's times estimate the two; when its Sibson took longer than
+  // half its front stages, the host waits the difference more (an eye-tracked gaze's big discs: 2-5 ms of
+  // Sibson against ~1.3 ms of front stages), so the gaze is sampled that much later.
+  for (int k = 0; k < c->nslots; k++) {
+    if (!L.rec[k] || hipEventQuery(L.ev[k].recon_end) != hipSuccess) continue;
+    float f = 0.0f, sb = 0.0f;
+    if (hipEventElapsedTime(&f, L.ev[k].front_begin, L.ev[k].front_end) == hipSuccess &&
+        hipEventElapsedTime(&sb, L.ev[k].jfa_end, L.ev[k].recon_end) == hipSuccess) {
+      // The front stages' span is the smallest of the last eight: a front stage that overlapped the
+      // previous Sibson ran slower, and estimating from it started the next front stages earlier still (into
+      // more of that Sibson: a feedback that held the eye-tracked circle's fronts at ~4 ms instead of ~1)
+      L.front_hist[L.front_n++ & 7] = f;
+      L.front_ms = f;
+      for (int j = 1; j < std::min(8, L.front_n); j++)
+        L.front_ms = std::min(L.front_ms, L.front_hist[(L.front_n - 1 - j) & 7]);
+      L.sib_ms = sb;
+    }
+    L.rec[k] = false;
+  }
+  // Only half of the front stages' span is overlapped: the big discs' strip kernel fills every CU, and a
+  // front stage started further into it ran ~4 ms instead of ~1, with its gaze sampled that much earlier
+  // (eye-tracked circle latency p99 16.2 -> 12.6 ms at 142 fps; C3 p50 6.15 -> 5.81 ms; overlapping none:
+  // p99 12.5 ms at 139 fps, the serial loop's rate). A short Sibson (no big discs: below kLatShortSibMs) takes the
+  // whole span: the front stages then end with it without slowing down (4K bunny centred 186.0 -> 189.3 fps at
+  // latency p50 5.72 -> 5.79 ms, 4K vokselia 233.1 -> 235.2 fps; profiles/r06_lat_overlap_*). FOVRT_LAT_OVERLAP:
+  // one percentage for every frame instead (A/B knob).
+  constexpr float kLatShortSibMs = 1.5f;
+  static const float ovl_env = [] { const char* v = getenv("FOVRT_LAT_OVERLAP"); return v ? atoi(v) / 100.0f : -1.0f; }();
+  const float ovl = ovl_env >= 0.0f ? ovl_env : L.sib_ms < kLatShortSibMs ? 1.0f : 0.5f;
+  const float delay_ms = c->jfa_done[prev].pending ? L.sib_ms - ovl * L.front_ms : 0.0f;
+  if (delay_ms > 0.05f) {
+    const auto t0 = std::chrono::steady_clock::now();
+    while (std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() < delay_ms &&
+           hipEventQuery(c->recon_done[prev].ev) == hipErrorNotReady) {
+      cpu_relax();
+    }
+  }
+  c->jfa_done[prev].pending = false;  // polled by the host: no stream waits for it
   return FR_OK;
 }
 
@@ -369,7 +414,7 @@ static int timed(fr_ctx* c, const std::function<int()>& f, float* ms) {
 int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
   if (!c) return FR_E_INVALID;
   hipSetDevice(c->cfg.device);
-  hipEvent_t* ev = c->ev;
+  const fr_ctx::StageEvents& T = c->tev;  // recorded by timed frames only (t)
   int rc;
   // fr_frame_clock: a frame that fails after enqueue_geometry reserved its ring entry gives the entry
   // back (it would never get its end event)
@@ -382,169 +427,115 @@ int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
       c->fc_cur = -1;
     }
   } fc_guard{c};
-  if (t) hipEventRecord(ev[0], c->stream);
+  if (t) hipEventRecord(T.begin, c->stream);
   if (trace) {
-    // untimed frames pipeline: the front stages go to stream5 and overlap the previous frame's
+    // untimed frames pipeline: the front stages go to front_stream and overlap the previous frame's
     // entry 3 (timed frames keep every stage on `stream`, one after the other)
-    hipStream_t fs = t ? c->stream : c->stream5;
+    hipStream_t fs = t ? c->stream : c->front_stream;
     const bool latency = !t && c->pipeline_mode == FR_PIPELINE_LATENCY;
     const int prev = c->slot;  // the previous frame's slot
-    if (latency && (c->jfa_pending[prev] || c->trace_pending[prev])) {
-      // one frame ahead at most: the host waits until the previous frame's JumpFlooding has ended (its
-      // path trace, when this context does not run that chain), then samples the gaze and enqueues this
-      // frame, whose front stages (G-buffer, sampling, compaction) overlap the previous frame's Sibson
-      // and pull-push -> A-Trous; its path trace starts after them (below)
-      // (polled: a blocking wait woke the host up to milliseconds late, and the GPU idled meanwhile)
-      hipEvent_t w = c->jfa_pending[prev] ? c->ev_jfa[prev] : c->ev_trace[prev];
-      hipError_t e;
-      if ((e = poll_event(w, kPollDeadlineMs)) != hipSuccess)
-        return fail(c, FR_E_HIP, e == hipErrorNotReady ? std::string("frame failed: the previous frame did not complete within the poll deadline")
-                                                        : std::string("frame failed: ") + hipGetErrorString(e));
-      // Just in time: the front stages should end about when the previous frame's Sibson does (its path
-      // trace waits for both). A completed frame's times estimate the two; when its Sibson took longer than
-      // half its front stages, the host waits the difference more (an eye-tracked gaze's big discs: 2-5 ms of
-      // Sibson against ~1.3 ms of front stages), so the gaze is sampled that much later.
-      for (int k = 0; k < c->nslots; k++) {
-        if (!c->lat_rec[k] || hipEventQuery(c->lat_ev[k][3]) != hipSuccess) continue;
-        float f = 0.0f, sb = 0.0f;
-        if (hipEventElapsedTime(&f, c->lat_ev[k][0], c->lat_ev[k][1]) == hipSuccess &&
-            hipEventElapsedTime(&sb, c->lat_ev[k][2], c->lat_ev[k][3]) == hipSuccess) {
-          // The front stages' span is the smallest of the last eight: a front stage that overlapped the
-          // previous Sibson ran slower, and estimating from it started the next front stages earlier still (into
-          // more of that Sibson: a feedback that held the eye-tracked circle's fronts at ~4 ms instead of ~1)
-          c->lat_front_hist[c->lat_front_n++ & 7] = f;
-          c->lat_front_ms = f;
-          for (int j = 1; j < std::min(8, c->lat_front_n); j++)
-            c->lat_front_ms = std::min(c->lat_front_ms, c->lat_front_hist[(c->lat_front_n - 1 - j) & 7]);
-          c->lat_sib_ms = sb;
-        }
-        c->lat_rec[k] = false;
-      }
-      // Only half of the front stages' span is overlapped: the big discs' strip kernel fills every CU, and a
-      // front stage started further into it ran ~4 ms instead of ~1, with its gaze sampled that much earlier
-      // (eye-tracked circle latency p99 16.2 -> 12.6 ms at 142 fps; C3 p50 6.15 -> 5.81 ms; overlapping none:
-      // p99 12.5 ms at 139 fps, the serial loop's rate). A short Sibson (no big discs: below kLatShortSibMs) takes the
-      // whole span: the front stages then end with it without slowing down (4K bunny centred 186.0 -> 189.3 fps at
-      // latency p50 5.72 -> 5.79 ms, 4K vokselia 233.1 -> 235.2 fps; profiles/r06_lat_overlap_*). FOVRT_LAT_OVERLAP:
-      // one percentage for every frame instead (A/B knob).
-      constexpr float kLatShortSibMs = 1.5f;
-      static const float ovl_env = [] { const char* v = getenv("FOVRT_LAT_OVERLAP"); return v ? atoi(v) / 100.0f : -1.0f; }();
-      const float ovl = ovl_env >= 0.0f ? ovl_env : c->lat_sib_ms < kLatShortSibMs ? 1.0f : 0.5f;
-      const float delay_ms = c->jfa_pending[prev] ? c->lat_sib_ms - ovl * c->lat_front_ms : 0.0f;
-      if (delay_ms > 0.05f) {
-        const auto t0 = std::chrono::steady_clock::now();
-        while (std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() < delay_ms &&
-               hipEventQuery(c->ev_recon[prev]) == hipErrorNotReady) {
-          cpu_relax();
-        }
-      }
-      c->jfa_pending[prev] = false;
-    }
+    if (latency && (rc = wait_for_previous_frame(c, prev))) return rc;
     if (!t && c->stream_dirty) {
       // the front stages overwrite buffers (gclass, DIFFUSE, EXTRA, depth, ballots, counts, lp_cache) that
       // work enqueued on `stream` by other calls may still read: order them after it explicitly
-      hipEventRecord(c->ev[18], c->stream);
-      hipStreamWaitEvent(fs, c->ev[18], 0);
+      hipEventRecord(c->ev_stream_join, c->stream);
+      hipStreamWaitEvent(fs, c->ev_stream_join, 0);
     }
     c->stream_dirty = false;
     c->fc_arm = c->fc_on && recon;  // whole frames only (a group's trace half has no end of its own)
-    c->lat_arm = latency && recon;
+    c->lat.arm = latency && recon;
     rc = enqueue_geometry(c, fs);
     c->fc_arm = false;
-    if (rc) { c->lat_arm = false; return rc; }
-    if (t) hipEventRecord(ev[1], c->stream);
+    if (rc) { c->lat.arm = false; return rc; }
+    if (t) hipEventRecord(T.geometry, c->stream);
     if ((rc = enqueue_sampling(c, fs))) return rc;
-    if (t) hipEventRecord(ev[2], c->stream);
+    if (t) hipEventRecord(T.sampling, c->stream);
     if ((rc = enqueue_optimize(c, fs))) return rc;
-    if (t) hipEventRecord(ev[3], c->stream);
+    if (t) hipEventRecord(T.optimize, c->stream);
     if (latency && fs != c->stream && c->hvalid_fresh && c->U.shard_count <= 1 && !c->U.front_need && c->early_setup) {
-      // Early sample setup (latency mode): from the validity bits of the previous frame's history (its carry, ev[12])
-      // instead of the history itself, so it runs here with the front stages, and this frame's megakernel starts as
+      // Early sample setup (latency mode): from the validity bits of the previous frame's history instead of the
+      // history itself, so it runs here with the front stages, and this frame's megakernel starts as
       // soon as the previous frame's reconstruction ends (the setup sat between them on the context stream, ~0.1 ms
       // on the CUs the reconstruction had just filled). Into the aux buffer the previous megakernel does not read.
       // (Throughput mode keeps the setup after the resolve: there the megakernel then started beside the previous
       // frame's reconstruction burst and ran 3.9 -> 4.1 ms, 240 -> 232 fps; profiles/r06_early_setup_ab.txt.)
-      hipStreamWaitEvent(fs, c->ev[12], 0);
+      // Across frames: ev_carry_done still holds the PREVIOUS frame's record here (enqueue_shading below makes this
+      // frame's), the carry that wrote those validity bits.
+      hipStreamWaitEvent(fs, c->ev_carry_done, 0);
       const int o = c->aux_i ^ 1;
       launch_sample_setup(c->U, c->active, c->ray_count, (uint32_t)((size_t)c->W * c->H), c->img[P_wgt(c)], nullptr,
                           c->hvalid, c->aux_p[o], c->aux_seed_p[o], fs);
       if ((rc = check_launch(c))) return rc;
       c->setup_early = true;
     }
-    if (!t) {
-      hipEventRecord(c->ev_front, fs);
-      c->front_pending = true;
-    }
-    if (c->lat_arm) hipEventRecord(c->lat_ev[c->slot][1], fs);
+    if (!t) c->front_done.record(fs);
+    if (c->lat.arm) hipEventRecord(c->lat.ev[c->slot].front_end, fs);
     // latency mode: this frame's path trace starts after the previous frame's reconstruction. The
     // megakernel fills every CU, so a reconstruction running beside it waited for it to end and then
     // delayed this frame's own reconstruction (pipelined latency p50 10-12 ms against a 5.6 ms frame).
-    if (latency && c->recon_pending[prev]) hipStreamWaitEvent(c->stream, c->ev_recon[prev], 0);
+    // (peek: the front stages of the frame that reuses slot prev still wait for it)
+    if (latency) c->recon_done[prev].peek(c->stream);
     c->time_kernels = t != nullptr;
     rc = enqueue_shading(c);
     c->time_kernels = false;
     if (rc) return rc;
   } else if (t) {
-    for (int i = 1; i <= 3; i++) hipEventRecord(ev[i], c->stream);
-    hipEventRecord(ev[9], c->stream);
-    hipEventRecord(ev[10], c->stream);
+    for (hipEvent_t e : {T.geometry, T.sampling, T.optimize, T.paths_begin, T.paths_end}) hipEventRecord(e, c->stream);
   }
-  if (t) hipEventRecord(ev[4], c->stream);
+  if (t) hipEventRecord(T.shading, c->stream);
   if (recon) {
     // The reconstruction of this frame's shading runs on its own streams, so the next frame's trace
     // half (on `stream`) overlaps it. Two independent chains read the shading: JFA -> Sibson
-    // (stream3) and pull-push -> A-Trous (stream2; atFS binds the JFA texture but never reads it,
+    // (sibson_stream) and pull-push -> A-Trous (atrous_stream; atFS binds the JFA texture but never reads it,
     // FR/shader/atFS.glsl:40-90). Both resolve their inputs now, at this frame's slot.
     // (a group's reconstruction rank may run only one of the chains: c->recon_chains)
-    hipEventRecord(ev[16], c->stream);
-    hipStreamWaitEvent(c->stream3, ev[16], 0);
-    hipStreamWaitEvent(c->stream2, ev[16], 0);
-    if (t) hipEventRecord(ev[20], c->stream3);
-    if ((c->recon_chains & 1) && (rc = enqueue_jfa(c, FR_BUF_SHADING, c->stream3))) return rc;
-    if (t) hipEventRecord(ev[21], c->stream3);
+    hipEventRecord(c->ev_recon_fork, c->stream);
+    hipStreamWaitEvent(c->sibson_stream, c->ev_recon_fork, 0);
+    hipStreamWaitEvent(c->atrous_stream, c->ev_recon_fork, 0);
+    if (t) hipEventRecord(T.chain1_begin, c->sibson_stream);
+    if ((c->recon_chains & 1) && (rc = enqueue_jfa(c, FR_BUF_SHADING, c->sibson_stream))) return rc;
+    if (t) hipEventRecord(T.jfa, c->sibson_stream);
     if (c->pipeline_mode == FR_PIPELINE_LATENCY && (c->recon_chains & 1)) {
-      hipEventRecord(c->ev_jfa[c->slot], c->stream3);
-      c->jfa_pending[c->slot] = true;
-      if (c->lat_arm) hipEventRecord(c->lat_ev[c->slot][2], c->stream3);
+      c->jfa_done[c->slot].record(c->sibson_stream);
+      if (c->lat.arm) hipEventRecord(c->lat.ev[c->slot].jfa_end, c->sibson_stream);
     }
-    if ((c->recon_chains & 1) && (rc = enqueue_sibson(c, c->stream3))) return rc;
-    if (t) hipEventRecord(ev[22], c->stream3);
-    if (c->recon_gate) hipStreamWaitEvent(c->stream2, c->recon_gate, 0);
-    if (t) hipEventRecord(ev[13], c->stream2);
-    if ((c->recon_chains & 2) && (rc = enqueue_pullpush(c, FR_BUF_SHADING, c->stream2))) return rc;
-    if (t) hipEventRecord(ev[14], c->stream2);
+    if ((c->recon_chains & 1) && (rc = enqueue_sibson(c, c->sibson_stream))) return rc;
+    if (t) hipEventRecord(T.sibson, c->sibson_stream);
+    if (c->recon_gate) hipStreamWaitEvent(c->atrous_stream, c->recon_gate, 0);
+    if (t) hipEventRecord(T.chain2_begin, c->atrous_stream);
+    if ((c->recon_chains & 2) && (rc = enqueue_pullpush(c, FR_BUF_SHADING, c->atrous_stream))) return rc;
+    if (t) hipEventRecord(T.pullpush, c->atrous_stream);
     if ((c->recon_chains & 2) && (rc = enqueue_atrous(c, c->cfg.atrous_iterations, FR_BUF_POSITION, FR_BUF_NORMAL,
-                                                      FR_BUF_PULLPUSH, c->stream2))) return rc;
-    if (t) hipEventRecord(ev[15], c->stream2);
-    hipEventRecord(ev[17], c->stream2);
-    hipStreamWaitEvent(c->stream3, ev[17], 0);
-    hipEventRecord(c->ev_recon[c->slot], c->stream3);  // this slot's buffers are free again after this
-    c->recon_pending[c->slot] = true;
-    if (c->lat_arm && (c->recon_chains & 1)) {
-      hipEventRecord(c->lat_ev[c->slot][3], c->stream3);
-      c->lat_rec[c->slot] = true;
+                                                      FR_BUF_PULLPUSH, c->atrous_stream))) return rc;
+    if (t) hipEventRecord(T.atrous, c->atrous_stream);
+    hipEventRecord(c->ev_chain2_done, c->atrous_stream);
+    hipStreamWaitEvent(c->sibson_stream, c->ev_chain2_done, 0);
+    c->recon_done[c->slot].record(c->sibson_stream);  // this slot's buffers are free again after this
+    if (c->lat.arm && (c->recon_chains & 1)) {
+      hipEventRecord(c->lat.ev[c->slot].recon_end, c->sibson_stream);
+      c->lat.rec[c->slot] = true;
     }
-    c->lat_arm = false;
+    c->lat.arm = false;
     if (c->fc_cur >= 0) {  // fr_frame_clock: both chains of this frame are done
-      hipEventRecord(c->fc_ev[c->fc_cur][1], c->stream3);
+      hipEventRecord(c->fc_ev[c->fc_cur][1], c->sibson_stream);
       c->fc_cur = -1;
     }
     if (t) join_recon(c);
   }
   if (t) {
-    hipEventRecord(ev[8], c->stream);
-    hipError_t e = hipEventSynchronize(ev[8]);
+    hipEventRecord(T.end, c->stream);
+    hipError_t e = hipEventSynchronize(T.end);
     if (e != hipSuccess) return fail(c, FR_E_HIP, std::string("frame failed: ") + hipGetErrorString(e));
-    t->geometry_ms = elapsed(ev[0], ev[1]);
-    t->sampling_ms = elapsed(ev[1], ev[2]);
-    t->optimize_ms = elapsed(ev[2], ev[3]);
-    t->shading_ms = elapsed(ev[3], ev[4]);
-    t->jfa_ms = recon ? elapsed(ev[20], ev[21]) : 0.0f;
-    t->sibson_ms = recon ? elapsed(ev[21], ev[22]) : 0.0f;
-    t->pullpush_ms = recon ? elapsed(ev[13], ev[14]) : 0.0f;
-    t->atrous_ms = recon ? elapsed(ev[14], ev[15]) : 0.0f;
-    t->total_ms = elapsed(ev[0], ev[8]);
-    t->shade_paths_ms = elapsed(ev[9], ev[10]);
+    t->geometry_ms = elapsed(T.begin, T.geometry);
+    t->sampling_ms = elapsed(T.geometry, T.sampling);
+    t->optimize_ms = elapsed(T.sampling, T.optimize);
+    t->shading_ms = elapsed(T.optimize, T.shading);
+    t->jfa_ms = recon ? elapsed(T.chain1_begin, T.jfa) : 0.0f;
+    t->sibson_ms = recon ? elapsed(T.jfa, T.sibson) : 0.0f;
+    t->pullpush_ms = recon ? elapsed(T.chain2_begin, T.pullpush) : 0.0f;
+    t->atrous_ms = recon ? elapsed(T.pullpush, T.atrous) : 0.0f;
+    t->total_ms = elapsed(T.begin, T.end);
+    t->shade_paths_ms = elapsed(T.paths_begin, T.paths_end);
     hipMemcpy(&t->ray_count, c->ray_count, 4, hipMemcpyDeviceToHost);
   }
   return FR_OK;

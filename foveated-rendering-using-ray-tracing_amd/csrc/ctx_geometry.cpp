@@ -266,7 +266,7 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 // their contents follow in stream order (k_take_over fills the array that becomes d_pos with the caller's
 // positions, or with the current ones when the update is rejected). That is safe because every reader and writer
 // of the three arrays, the tree and the normals is ordered on the context stream: the front stages of a pipelined
-// frame run on stream5, but entry 3 of that frame waits for them on the context stream (ev_front) before this
+// frame run on front_stream, but entry 3 of that frame waits for them on the context stream (front_done) before this
 // update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
 // The reconstruction streams read none of it, so they are not joined.
 // (pose: fr_set_model_transforms_enqueue, whose k_pose produces xyz and nrm, the staging arrays, on the context stream)
@@ -279,9 +279,9 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
                                          (pose ? "fr_set_model_transforms)" : "fr_update_geometry)"));
   if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
   hipSetDevice(c->cfg.device);
-  c->stream_dirty = true;  // the next pipelined frame's front stages (stream5) start after this update
+  c->stream_dirty = true;  // the next pipelined frame's front stages (front_stream) start after this update
   // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
-  if (c->front_pending) { hipStreamWaitEvent(c->stream, c->ev_front, 0); c->front_pending = false; }
+  c->front_done.consume(c->stream);
   if (ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ready_event), 0));
   const int nt = (int)ntris;
   std::string err;
@@ -301,7 +301,7 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
     return fail(c, FR_E_HIP, name + ": " + err);
   c->dev_box = c->geo->box;
   c->box_mirror_stale = true;
-  if (!given) HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // xyz has been read
+  if (!given) HIP_TRY(c, c->geo_read.record(c->stream));  // xyz has been read
   const uint32_t* reject = &c->geo->reject;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
   if (!gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, c->stream, err))
@@ -311,14 +311,13 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
   if (given) {
     if (!gpu_scatter_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), c->d_shade, reject, c->stream, err))
       return fail(c, FR_E_HIP, name + ": " + err);
-    HIP_TRY(c, hipEventRecord(c->ev_geo_read, c->stream));  // nrm has been read as well
+    HIP_TRY(c, c->geo_read.record(c->stream));  // nrm has been read as well
     c->nrm_mirror_stale = true;
   } else if (normals == FR_NORMALS_RECOMPUTE) {
     if (!gpu_recompute_normals_enqueue(c->nrm_work, c->d_pos, c->d_shade, reject, c->stream, err))
       return fail(c, FR_E_HIP, name + ": " + err);
     c->nrm_mirror_stale = true;
   }
-  c->geo_read_pending = true;
   return FR_OK;
 }
 
@@ -329,9 +328,9 @@ int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size
 
 int fr_geometry_consumed(fr_ctx* c, void* stream) {
   if (!c) return FR_E_INVALID;
-  if (!c->geo_read_pending) return FR_OK;
+  if (!c->geo_read.pending) return FR_OK;
   hipSetDevice(c->cfg.device);
-  HIP_TRY(c, hipStreamWaitEvent(static_cast<hipStream_t>(stream), c->ev_geo_read, 0));
+  HIP_TRY(c, c->geo_read.peek(static_cast<hipStream_t>(stream)));
   return FR_OK;
 }
 
@@ -573,7 +572,7 @@ extern "C" {
 
 int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
   if (!c || !o) return FR_E_INVALID;
-  if (c->geo_read_pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
+  if (c->geo_read.pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
     // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
     hipSetDevice(c->cfg.device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));

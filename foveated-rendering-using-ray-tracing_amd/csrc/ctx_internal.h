@@ -10,99 +10,10 @@
 
 #include "../../include/fovrt.h"
 #include "fr_device.h"
+#include "k_launch.h"
 #include "scene.h"
 
 #define FR_MAX_SHARD_RANKS 64  // ranks per view (an owner is one byte of the tile map)
-
-namespace fr {
-// (the two f3 arrays: the positions this launch traces and the ones the previous launch traced, for the motion
-// form; NULL for the plain one)
-void launch_gbuffer(const DevScene&, const FrameUniforms&, f4*, f4*, f4*, f4*, f4*, uint8_t*, DevStats*, const f3*,
-                    const f3*, hipStream_t);
-void launch_shade_paths(const DevScene&, const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*,
-                        const f4*, uint32_t*, f4*, unsigned long long*, DevStats*, f4*, uint32_t*, uint32_t, uint32_t,
-                        uint32_t, int, f4*, hipStream_t);
-int shade_max_blocks_per_cu();
-size_t shade_item_store_f4(int per_cu);
-void launch_sample_setup(const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*, const f4*,
-                         const unsigned long long*, f4*, uint32_t*, hipStream_t);
-void launch_shade_resolve(const FrameUniforms&, const uint32_t*, const uint32_t*, uint32_t, const f4*, const f4*,
-                          const f4*, unsigned long long*, f4*, f4*, uint32_t*, uint32_t, int, f4*, hipStream_t);
-size_t shade_counter_words();
-size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff, int per_cu);
-void launch_carry_history(const FrameUniforms&, const uint8_t*, const f4*, const f4*, f4*, f4*, unsigned long long*,
-                          hipStream_t);
-void launch_sampling(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, f4*, const f4*,
-                     const f4*, f4*, uint8_t*, const uint8_t*, unsigned long long*, uint32_t*, int, uint8_t*, uint32_t*,
-                     bool, uint32_t*, bool, const float*, hipStream_t);
-void launch_extra(const FrameUniforms&, const DevScene&, const f4*, const f4*, const f4*, const f4*, f4*, const float*,
-                  hipStream_t);
-size_t logpolar_inv_words(int W, int H);
-void launch_owner_counts(const FrameUniforms&, const uint32_t*, uint32_t*, hipStream_t);
-void launch_mask_words(const uint8_t*, const uint8_t*, int, int, unsigned long long*, uint32_t*, hipStream_t);
-void launch_compaction(int, int, const unsigned long long*, const uint32_t*, uint32_t*, uint32_t*, uint32_t*,
-                       uint32_t*, hipStream_t);
-size_t compaction_tiles(int W, int H);
-void launch_shard_pack(const FrameUniforms&, const f4*, f4*, hipStream_t);
-void launch_logpolar(const f4*, f4*, f4*, int, int, f2, hipStream_t);
-void launch_composite(const f4*, int, int, int, f4*, hipStream_t);
-void launch_shard_unpack(const FrameUniforms&, int, const f4*, f4*, hipStream_t);
-void launch_shard_pack_active(const uint32_t*, const uint32_t*, uint32_t, const f4*, f4*, uint32_t*, hipStream_t);
-// the history validity rings of a still-camera group (k_trace.hip): FR_VRING pixels inside each tile
-void launch_vring_pack(const f4*, int, int, int, const int32_t*, int, uint32_t*, hipStream_t);
-void launch_vring_unpack(const uint32_t*, int, int, int, const int32_t*, int, f4*, hipStream_t);
-void launch_shard_unpack_active(const FrameUniforms&, const f4*, const uint32_t*, uint32_t, uint32_t, const f4*, const f4*, f4*,
-                                f4*, hipStream_t);
-const u2* launch_jfa(const f4*, u2*, u2*, f4*, f4*, const float*, int, int, f4*, f4*, bool, int, hipStream_t);
-void launch_jfa_coord(const u2*, const f4*, f4*, int, int, hipStream_t);
-void launch_sibson(const f4*, const f4*, f4*, int, int, hipStream_t);
-void launch_sibson_runs(const f4*, const u2*, const f4*, f4*, f4*, f4*, uint32_t*, uint32_t*, f4*, int, int, bool, bool,
-                        int, bool, hipStream_t);
-int sibson_prefix_blocks(int W);
-size_t sibson_strip_words(int W, int H);
-size_t sibson_rowp_texels(int W, int H);
-struct BvhWork;
-bool gpu_build_bvh(BvhWork**, const f3*, int, BvhNode*, TriGeo*, int32_t*, int*, int*, int*, hipStream_t, std::string&);
-void bvh_work_free(BvhWork*);
-bool bvh_work_prepare(BvhWork**, int, hipStream_t, std::string&);
-bool bvh_builder_warm(BvhWork*, hipStream_t, std::string&);
-bool gpu_refit_bvh(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, hipStream_t, std::string&);
-bool gpu_refit_bvh_enqueue(BvhWork*, const f3*, int, BvhNode*, int, TriGeo*, const int32_t*, const uint32_t*, hipStream_t,
-                           std::string&);
-bool gpu_check_positions_enqueue(BvhWork*, const float*, int, hipStream_t, std::string&);
-bool gpu_take_over_positions(BvhWork*, const f3*, const f3*, int, f3*, const uint32_t*, GeoUpdateState*, int, f3, f3,
-                             hipStream_t, std::string&);
-bool gpu_bvh_cost(BvhWork*, const BvhNode*, int, float*, hipStream_t, std::string&);
-bool gpu_check_positions(BvhWork*, const float*, int, bool*, float*, hipStream_t, std::string&);
-// shading normals over moving geometry (k_normals.hip)
-struct NormalsWork;
-bool normals_work_create(NormalsWork**, const int32_t*, const int32_t*, const int32_t*, int, int, hipStream_t,
-                         std::string&);
-void normals_work_free(NormalsWork*);
-bool gpu_recompute_normals(NormalsWork*, const f3*, TriShade*, hipStream_t, std::string&);
-bool gpu_check_normals(NormalsWork*, const float*, bool*, hipStream_t, std::string&);
-bool gpu_scatter_normals(NormalsWork*, const float*, TriShade*, hipStream_t, std::string&);
-// their enqueue halves (no wait; the uint32_t*: the device verdict word of an enqueued update, or NULL)
-bool gpu_recompute_normals_enqueue(NormalsWork*, const f3*, TriShade*, const uint32_t*, hipStream_t, std::string&);
-bool gpu_check_normals_enqueue(NormalsWork*, const float*, uint32_t*, hipStream_t, std::string&);
-bool gpu_scatter_normals_enqueue(NormalsWork*, const float*, TriShade*, const uint32_t*, hipStream_t, std::string&);
-// model poses (k_pose.hip): a pose's kernel arguments (NULL, or why the pose is refused), the launch that writes the
-// posed rest arrays into the staging arrays, the capture of the rest arrays, and the bytes of one such array
-const char* pose_args(PoseArgs*, const float*, int, const int*);
-bool gpu_pose_enqueue(const PoseArgs&, const f3*, const f3*, f3*, f3*, int, hipStream_t, std::string&);
-bool gpu_pose_capture_enqueue(const f3*, const TriShade*, f3*, f3*, int, hipStream_t, std::string&);
-size_t pose_array_bytes(int);
-#ifdef FR_STAMPS
-void launch_trace_queries(const DevScene&, const f4*, uint32_t, f4*, uint32_t*, hipStream_t, int);
-void diag_record_queries(f4*, uint32_t, hipStream_t);
-uint32_t diag_recorded_queries(hipStream_t);
-void diag_sample_trace(uint32_t*, uint32_t, uint32_t*, uint32_t, hipStream_t);
-#endif
-void launch_pullpush(const f4*, f4*, f4*, f4*, f4*, int, int, hipStream_t);
-bool launch_atrous(const f4*, const f4*, const f4*, f4*, int, int, float, float, float, float, bool, int, hipStream_t);
-int pp_size(int W, int H);
-size_t pp_snap_count(int S);
-}  // namespace fr
 
 using fr::f2;
 using fr::f3;
@@ -129,48 +40,89 @@ enum Phys {
   P_COUNT
 };
 
+// An event with the flag that says a record of it may still be in flight. The owner creates and destroys `ev`
+// (hipEventDisableTiming); a reader that needs the event whatever the flag (a host poll, a query) takes `ev`.
+struct Fence {
+  hipEvent_t ev = nullptr;
+  bool pending = false;
+  hipError_t record(hipStream_t s) { pending = true; return hipEventRecord(ev, s); }
+  // s waits for the last record, if one is pending; the flag is cleared (consume: the next waiter has nothing to
+  // wait for) or kept (peek: others still wait for the same record)
+  hipError_t consume(hipStream_t s) {
+    const hipError_t e = peek(s);
+    pending = false;
+    return e;
+  }
+  hipError_t peek(hipStream_t s) const { return pending ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+};
+
 struct fr_ctx {
   fr_config cfg;
   std::string asset_dir;
   std::string err;
   int W = 0, H = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // reconstruction chain 2: pull-push -> A-Trous
-  hipStream_t stream3 = nullptr;  // reconstruction chain 1: JFA -> Sibson
-  hipStream_t stream4 = nullptr;  // entry 3's carry of the inactive pixels, beside the megakernel
-  hipStream_t stream5 = nullptr;  // front stages of a pipelined frame (entries 0-2), beside the previous megakernel
-  // Invariant for stream5: its front stages wait only for the slot events (ev_recon, ev_trace), not for
+  // The five streams, in creation order (all non-blocking, priority 0). DESIGN.md §5 has the table of who records and
+  // who waits for each fence and ordering event below.
+  hipStream_t stream = nullptr;         // the context stream: entry 3, stage calls, updates
+  hipStream_t atrous_stream = nullptr;  // reconstruction chain 2: pull-push -> A-Trous
+  hipStream_t sibson_stream = nullptr;  // reconstruction chain 1: JFA -> Sibson
+  hipStream_t carry_stream = nullptr;   // entry 3's carry of the inactive pixels, beside the megakernel
+  hipStream_t front_stream = nullptr;   // front stages of a pipelined frame (entries 0-2), beside the previous megakernel
+  // Invariant for front_stream: its front stages wait only for the slot fences (recon_done, trace_done), not for
   // earlier work on `stream`, although they overwrite shared buffers (gclass, DIFFUSE, EXTRA, depth,
   // ballots, counts, lp_cache). So every ABI call that enqueues on `stream` outside a pipelined frame
   // goes through join_recon, which sets stream_dirty, and the next pipelined frame's front stages then
-  // wait for `stream` once (frame_half). fr_update_geometry_enqueue sets stream_dirty itself without joining the
-  // reconstruction: its kernels touch positions, tree and normals, which only the trace half reads.
-  bool stream_dirty = true;
-  // Frame pipelining: frame N's reconstruction (stream3 + stream2) runs while later frames trace.
+  // wait for `stream` once (frame_half, ev_stream_join). fr_update_geometry_enqueue sets stream_dirty itself without
+  // joining the reconstruction: its kernels touch positions, tree and normals, which only the trace half reads.
+
+  // Frame pipelining: frame N's reconstruction (sibson_stream + atrous_stream) runs while later frames trace.
   // The buffers the reconstruction reads (POSITION, NORMAL, SHADING) rotate over `nslots` frame
   // slots (`slot` = the current frame's); a frame's front stages wait for the reconstruction that
-  // last read their slot (ev_recon). The front stages of a pipelined frame (G-buffer, sampling,
-  // compaction) run on stream5 while the previous frame's megakernel still runs on `stream`: they
+  // last read their slot (recon_done). The front stages of a pipelined frame (G-buffer, sampling,
+  // compaction) run on front_stream while the previous frame's megakernel still runs on `stream`: they
   // read nothing entry 3 writes. What entry 3's tail reads of them (WEIGHT, mask, active list, ray
   // count) rotates with the slot as well; the front of a frame waits for the trace half that last
-  // read its slot (ev_trace), and entry 3 of a frame waits for its own front (ev_front).
+  // read its slot (trace_done), and entry 3 of a frame waits for its own front (front_done).
   static constexpr int MAX_SLOTS = 3;
   int nslots = 3;
   int slot = 0;
-  bool recon_pending[MAX_SLOTS] = {};
-  bool front_pending = false;
-  bool trace_pending[MAX_SLOTS] = {};
-  hipEvent_t ev_front = nullptr, ev_trace[MAX_SLOTS] = {}, ev_recon[MAX_SLOTS] = {};
-  // latency mode: the end of the slot's JumpFlooding (or of its trace half when the chain is not run here)
-  hipEvent_t ev_jfa[MAX_SLOTS] = {};
-  bool jfa_pending[MAX_SLOTS] = {};
-  // latency mode's schedule: per slot, timing events at the front stages' start and end, the JumpFlooding's
-  // end and the reconstruction's end; the last completed frame's front and Sibson (JFA end -> end) times
-  hipEvent_t lat_ev[MAX_SLOTS][4] = {};
-  bool lat_rec[MAX_SLOTS] = {}, lat_arm = false;
-  float lat_front_ms = 0.0f, lat_sib_ms = 0.0f;
-  float lat_front_hist[8] = {};  // the last frames' front-stage spans: their minimum is the uncontended one
-  int lat_front_n = 0;
+  Fence front_done;             // front stream, after a pipelined frame's front stages
+  Fence trace_done[MAX_SLOTS];  // context stream, after the last reader of the slot's WEIGHT / mask / active list
+  Fence recon_done[MAX_SLOTS];  // sibson_stream, after both chains of the slot's reconstruction
+  // latency mode: the end of the slot's JumpFlooding (sibson_stream; the host polls it, or trace_done when the chain
+  // is not run here)
+  Fence jfa_done[MAX_SLOTS];
+  // Ordering inside a frame: plain events, each recorded and waited for unconditionally at one place (ctx_frame.cpp).
+  hipEvent_t ev_carry_fork = nullptr;   // `stream` records before entry 3's kernels; carry_stream waits
+  // carry_stream records after k_carry_history; `stream` waits before the resolve. Across frames: the front stream of
+  // the NEXT frame waits for it before its early sample setup (latency mode), which reads the carry's validity bits.
+  hipEvent_t ev_carry_done = nullptr;
+  hipEvent_t ev_recon_fork = nullptr;   // `stream` records after the trace half; sibson_stream and atrous_stream wait
+  hipEvent_t ev_chain2_done = nullptr;  // atrous_stream records after A-Trous; sibson_stream waits, then records recon_done
+  // `stream` records, the front stream waits, when stream_dirty: something was enqueued on `stream` outside a
+  // pipelined frame since the last one (the invariant above; no event of its own, so a plain flag)
+  hipEvent_t ev_stream_join = nullptr;
+  bool stream_dirty = true;
+  // Stage timing of a timed frame (fr_frame_timing): each event ends the stage it is named after, on the stream that
+  // ran it (`stream`; the chain events on their chain's stream). A timed frame records all of them, so untimed
+  // frames never read them. stage_begin / stage_end: the pair around one stage call (timed()).
+  struct StageEvents {
+    hipEvent_t begin, geometry, sampling, optimize, shading, end;
+    hipEvent_t paths_begin, paths_end;          // around k_shade_paths alone
+    hipEvent_t chain2_begin, pullpush, atrous;  // atrous_stream
+    hipEvent_t chain1_begin, jfa, sibson;       // sibson_stream
+    hipEvent_t stage_begin, stage_end;
+  } tev = {};
+  // Latency mode's schedule (wait_for_previous_frame, ctx_frame.cpp): per slot, timing events at the front stages'
+  // start and end, the JumpFlooding's end and the reconstruction's end (rec: all four were recorded, arm: this frame
+  // records them); the last completed frame's front and Sibson (JFA end -> end) times.
+  struct LatSchedule {
+    struct { hipEvent_t front_begin, front_end, jfa_end, recon_end; } ev[MAX_SLOTS] = {};
+    bool rec[MAX_SLOTS] = {}, arm = false;
+    float front_ms = 0.0f, sib_ms = 0.0f;
+    float front_hist[8] = {};  // the last frames' front-stage spans: their minimum is the uncontended one
+    int front_n = 0;
+  } lat;
   // Tile sharding (fr_set_shard_plan): tile -> (owner << 24 | index among the owner's tiles) on the
   // device (FrameUniforms::shard_map), and the owners on the host. With sharding on, the front stages
   // also count every rank's active pixels from the unfolded mask (bcount per 16x16 block ->
@@ -226,14 +178,14 @@ struct fr_ctx {
   // box), made by fr_create; h_geo: its pinned copy for fr_geometry_update_status. Once a context has enqueued an
   // update the box lives in geo->box (dev_box points there, the saliency stage reads it; extra.box: the box an owed
   // EXTRA's sampling launch saw, geo->box or geo->xbox) and scene.bbox_min / bbox_max may be behind
-  // (box_mirror_stale; fr_scene_export fetches it). ev_geo_read: recorded on the context
-  // stream after the last kernel that reads the caller's arrays of the last enqueued update (fr_geometry_consumed).
+  // (box_mirror_stale; fr_scene_export fetches it). geo_read: recorded on the context
+  // stream after the last kernel that reads the caller's arrays of the last enqueued update; the caller's stream
+  // waits for it (fr_geometry_consumed; never consumed: any number of streams may ask).
   // geo_rejected_seen: the rejected counts fr_geometry_update_status last reported (total, positions, normals).
   fr::GeoUpdateState* geo = nullptr;
   fr::GeoUpdateState* h_geo = nullptr;
   const float* dev_box = nullptr;
-  hipEvent_t ev_geo_read = nullptr;
-  bool geo_read_pending = false;
+  Fence geo_read;
   bool box_mirror_stale = false;
   unsigned long long geo_rejected_seen[3] = {};
   // Model poses (fr_model_pose_enable, fr_set_model_transforms). Four arrays of 9 floats per triangle, made by the
@@ -342,7 +294,6 @@ struct fr_ctx {
   bool light_pending = false;
   bool compacted = false;
   bool mask_dirty = false;
-  hipEvent_t ev[24] = {};  // 0-15 stage timing; 16 fork; 17 chain-2 join; 20-22 chain-1 timing
   bool time_kernels = false;  // fr_frame with timing: also time the path-trace kernel alone
   // Live timing of entry 3 inside pipelined (untimed) frames: a ring of event quadruples recorded on
   // the context stream around carry_history / k_shade_paths / resolve (fr_kernel_timing); a slot is
@@ -354,7 +305,7 @@ struct fr_ctx {
   uint32_t kt_frames = 0;
   double kt_stage_ms = 0.0, kt_kernel_ms = 0.0;
   // Frame clock of pipelined frames (fr_frame_clock): per frame, an event where its G-buffer may start
-  // (on the front stream, after the slot waits) and one after both reconstruction chains (stream3).
+  // (on the front stream, after the slot waits) and one after both reconstruction chains (sibson_stream).
   // latency = start -> end of one frame (gaze sample to finished image on the GPU), interval = end of
   // the previous frame -> end of this one. Harvested like kt_ev.
   static constexpr int FC_RING = 16;

@@ -27,10 +27,9 @@ extern "C" {
 
 int fr_shard_unpack_active_enqueue(fr_ctx* c, const void* slab, size_t slab_bytes, uint32_t capacity, uint32_t count) {
   if (int rc = unpack_active(c, slab, slab_bytes, capacity, count, false)) return rc;
-  // the unpack reads the slot's WEIGHT: the front stages of frame + nslots (stream5 waits for ev_trace[slot])
+  // the unpack reads the slot's WEIGHT: the front stages of frame + nslots (front_stream waits for trace_done[slot])
   // may overwrite it only after this launch
-  hipEventRecord(c->ev_trace[c->slot], c->stream);
-  c->trace_pending[c->slot] = true;
+  c->trace_done[c->slot].record(c->stream);
   return check_launch(c);
 }
 
@@ -114,7 +113,7 @@ int fr_set_shard_plan(fr_ctx* c, int rank, int count, int tile, const uint8_t* o
     }
   c->extra.settle(c);  // a sharded context's unpack calls write the images an owed EXTRA reads
   if (int rc = quiesce(c)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream5));
+  HIP_TRY(c, hipStreamSynchronize(c->front_stream));
   // the new map is complete before the old one goes: a failed allocation or copy leaves the previous
   // plan (map, owners, uniforms) in force
   uint32_t* new_map = nullptr;
@@ -154,7 +153,7 @@ int fr_set_front_local(fr_ctx* c, int on) {
   if (on && c->U.shard_count <= 1) return fail(c, FR_E_STATE, "fr_set_front_local: needs a shard plan with count > 1");
   if ((bool)on == c->front_local) return FR_OK;
   if (int rc = quiesce(c)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream5));
+  HIP_TRY(c, hipStreamSynchronize(c->front_stream));
   c->front_local = on != 0;
   c->compacted = false;
   return update_front_need(c);

@@ -38,8 +38,11 @@ struct GroupRank {
   // sparse slabs: [k] double buffers by frame parity; one receive slab per view rank (null for self)
   char* send[2] = {};
   std::vector<char*> recv[2];
-  hipEvent_t ev_packed = nullptr, ev_comm[2] = {}, ev_unpacked[2] = {}, ev_out = nullptr, ev_sent_out = nullptr;
-  bool comm_pending[2] = {}, unpacked_pending[2] = {};
+  hipEvent_t ev_packed = nullptr, ev_out = nullptr, ev_sent_out = nullptr;
+  // by frame parity like the slabs, and never consumed (several streams wait for one record; the next record of the
+  // parity replaces it). comm_done: on comm after a frame's transfers; the context streams that pack into or unpack
+  // from the slabs wait. unpacked: on the context stream after the unpacks; comm waits before frame + 2's transfers.
+  Fence comm_done[2], unpacked[2];
   uint32_t n[FR_GROUP_MAX_VIEW_RANKS] = {};  // this frame's active pixels of every view rank
   // history validity rings (still camera, k_vring_pack): the tile list grouped by owner (device), this
   // rank's packed ring bits and one receive slab per other view rank, double-buffered by frame parity
@@ -207,8 +210,8 @@ void free_rank(GroupRank& L) {
     for (char* p : L.recv[k]) if (p) hipFree(p);
     if (L.vsend[k]) hipFree(L.vsend[k]);
     for (uint32_t* p : L.vrecv[k]) if (p) hipFree(p);
-    if (L.ev_comm[k]) hipEventDestroy(L.ev_comm[k]);
-    if (L.ev_unpacked[k]) hipEventDestroy(L.ev_unpacked[k]);
+    if (L.comm_done[k].ev) hipEventDestroy(L.comm_done[k].ev);
+    if (L.unpacked[k].ev) hipEventDestroy(L.unpacked[k].ev);
   }
   if (L.ev_packed) hipEventDestroy(L.ev_packed);
   if (L.ev_out) hipEventDestroy(L.ev_out);
@@ -239,21 +242,19 @@ int exchange(fr_group* g) {
     hipSetDevice(L.c->cfg.device);
     // send[k] was last read by the transfers of frame - 2
     if (g->comm) {
-      if (L.comm_pending[k]) hipStreamWaitEvent(L.c->stream, L.ev_comm[k], 0);
+      L.comm_done[k].peek(L.c->stream);
     } else {
-      for (GroupRank& D : g->loc)
-        if (D.comm_pending[k]) hipStreamWaitEvent(L.c->stream, D.ev_comm[k], 0);
+      for (GroupRank& D : g->loc) D.comm_done[k].peek(L.c->stream);
     }
     f4* vals = (f4*)L.send[k];
     uint32_t* idx = (uint32_t*)(L.send[k] + (size_t)n * sizeof(f4));
     fr::launch_shard_pack_active(L.c->active, L.c->ray_count, n, L.c->shade_radiance, vals, idx, L.c->stream);
     if (int rc = fri::check_launch(L.c)) return gfail(rc, fr_last_error(L.c));
     hipEventRecord(L.ev_packed, L.c->stream);
-    // The slot's active list and ray count are released to the front stages of frame + nslots (stream5
-    // waits for ev_trace[slot]) only once this pack has read them: enqueue_shading recorded ev_trace
-    // before the pack was queued, and the pack may still wait for frame - 2's transfers (ev_comm).
-    hipEventRecord(L.c->ev_trace[L.c->slot], L.c->stream);
-    L.c->trace_pending[L.c->slot] = true;
+    // The slot's active list and ray count are released to the front stages of frame + nslots (front_stream
+    // waits for trace_done[slot]) only once this pack has read them: enqueue_shading recorded trace_done
+    // before the pack was queued, and the pack may still wait for frame - 2's transfers (comm_done).
+    L.c->trace_done[L.c->slot].record(L.c->stream);
     if (g->comm) hipStreamWaitEvent(L.comm, L.ev_packed, 0);
   }
   // the history validity rings of this frame's history (after the trace half: resolve and carry)
@@ -261,10 +262,9 @@ int exchange(fr_group* g) {
     if (!vring_sender(g, L.vrank)) continue;
     hipSetDevice(L.c->cfg.device);
     if (g->comm) {
-      if (L.comm_pending[k]) hipStreamWaitEvent(L.c->stream, L.ev_comm[k], 0);
+      L.comm_done[k].peek(L.c->stream);
     } else {
-      for (GroupRank& D : g->loc)
-        if (D.comm_pending[k]) hipStreamWaitEvent(L.c->stream, D.ev_comm[k], 0);
+      for (GroupRank& D : g->loc) D.comm_done[k].peek(L.c->stream);
     }
     fr::launch_vring_pack(L.c->img[L.c->hist_cache], g->W, g->H, g->cfg.tile, L.tiles_dev + g->tile_off[L.vrank],
                           g->tiles_per_vrank[L.vrank], L.vsend[k], L.c->stream);
@@ -274,9 +274,9 @@ int exchange(fr_group* g) {
   }
   // receive slabs of frame - 2 must have been unpacked
   for (GroupRank& L : g->loc)
-    if (L.unpacked_pending[k]) {
+    if (L.unpacked[k].pending) {
       hipSetDevice(L.c->cfg.device);
-      hipStreamWaitEvent(L.comm, L.ev_unpacked[k], 0);
+      L.unpacked[k].peek(L.comm);
     }
   std::vector<Xfer> xs;
   for (GroupRank& L : g->loc) {
@@ -311,22 +311,20 @@ int exchange(fr_group* g) {
   if (int rc = run_xfers(g, xs, true)) return rc;
   for (GroupRank& L : g->loc) {
     hipSetDevice(L.c->cfg.device);
-    hipEventRecord(L.ev_comm[k], L.comm);
-    L.comm_pending[k] = true;
+    L.comm_done[k].record(L.comm);
   }
   // a pure tracer writes the other ranks' validity rings into this frame's history (its next frame's seeds)
   for (GroupRank& L : g->loc) {
     if (!vring_receiver(g, L.vrank)) continue;
     hipSetDevice(L.c->cfg.device);
-    hipStreamWaitEvent(L.c->stream, L.ev_comm[k], 0);
+    L.comm_done[k].peek(L.c->stream);  // (recorded just above)
     for (int s = 0; s < g->G; s++)
       if (s != L.vrank && vring_sender(g, s))
         fr::launch_vring_unpack(L.vrecv[k][s], g->W, g->H, g->cfg.tile, L.tiles_dev + g->tile_off[s],
                                 g->tiles_per_vrank[s], L.c->img[L.c->hist_cache], L.c->stream);
     L.c->hvalid_fresh = false;  // (the history no longer matches the validity bits of this frame's carry)
     if (int rc = fri::check_launch(L.c)) return gfail(rc, fr_last_error(L.c));
-    hipEventRecord(L.ev_unpacked[k], L.c->stream);
-    L.unpacked_pending[k] = true;
+    L.unpacked[k].record(L.c->stream);
   }
   // scatter the received pixels into HISTORY_CACHE and SHADING (after this rank's own trace half)
   const uint32_t npix = (uint32_t)((size_t)g->W * g->H);
@@ -335,7 +333,7 @@ int exchange(fr_group* g) {
     for (int s = 0; s < g->G; s++) any |= receives(g, L.vrank, s) && L.n[s];
     if (!any) continue;
     hipSetDevice(L.c->cfg.device);
-    hipStreamWaitEvent(L.c->stream, L.ev_comm[k], 0);
+    L.comm_done[k].peek(L.c->stream);  // (recorded just above)
     for (int s = 0; s < g->G; s++) {
       if (!receives(g, L.vrank, s) || !L.n[s]) continue;
       const f4* vals = (const f4*)L.recv[k][s];
@@ -345,12 +343,10 @@ int exchange(fr_group* g) {
     }
     L.c->hvalid_fresh = false;
     if (int rc = fri::check_launch(L.c)) return gfail(rc, fr_last_error(L.c));
-    hipEventRecord(L.ev_unpacked[k], L.c->stream);
-    L.unpacked_pending[k] = true;
+    L.unpacked[k].record(L.c->stream);
     // the unpack reads the slot's WEIGHT (the history gather): the slot goes back to the front stages of
-    // frame + nslots (stream5 waits for ev_trace[slot]) only after it, as after the pack above
-    hipEventRecord(L.c->ev_trace[L.c->slot], L.c->stream);
-    L.c->trace_pending[L.c->slot] = true;
+    // frame + nslots (front_stream waits for trace_done[slot]) only after it, as after the pack above
+    L.c->trace_done[L.c->slot].record(L.c->stream);
   }
   return FR_OK;
 }
@@ -365,7 +361,7 @@ int composite(fr_group* g) {
   for (GroupRank& L : g->loc) {
     if (L.vrank != ov) continue;
     hipSetDevice(L.c->cfg.device);
-    hipStreamWaitEvent(L.comm, L.c->ev_recon[L.c->slot], 0);  // this frame's A-Trous is written
+    hipStreamWaitEvent(L.comm, L.c->recon_done[L.c->slot].ev, 0);  // this frame's A-Trous is written (whatever the flag)
     if (!g->comm) hipEventRecord(L.ev_packed, L.comm);
     const f4* src = L.c->img[L.c->atrous_out];
     if (L.rank == 0) {
@@ -382,7 +378,7 @@ int composite(fr_group* g) {
       if (src != 0) xs.push_back({src, 0, nullptr, root->comp_stack + (size_t)v * g->W * g->H, img});
     }
   if (int rc = run_xfers(g, xs, !g->comm)) return rc;
-  // the next frame's A-Trous (stream2) overwrites an output image only after it left: with RCCL the
+  // the next frame's A-Trous (atrous_stream) overwrites an output image only after it left: with RCCL the
   // send is on the output rank's comm stream, in-process the copy is on rank 0's
   if (g->comm) {
     for (GroupRank& L : g->loc) {
@@ -544,8 +540,8 @@ int fr_group_create(fr_ctx* const* ctxs, int n, void* rccl_comm, const fr_group_
     hipEventCreateWithFlags(&L.ev_sent_out, hipEventDisableTiming);
     const size_t T2 = (size_t)T * T;
     for (int k = 0; k < 2; k++) {
-      hipEventCreateWithFlags(&L.ev_comm[k], hipEventDisableTiming);
-      hipEventCreateWithFlags(&L.ev_unpacked[k], hipEventDisableTiming);
+      hipEventCreateWithFlags(&L.comm_done[k].ev, hipEventDisableTiming);
+      hipEventCreateWithFlags(&L.unpacked[k].ev, hipEventDisableTiming);
       L.recv[k].assign(G, nullptr);
       if (G == 1) continue;
       bool sends = false;

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 #include "fr_device.h"
+#include "k_launch.h"
 
 namespace fr {
 namespace {

@@ -1,0 +1,140 @@
+// k_launch.h — the host entry points of the kernel files (k_*.hip): launchers, workspaces and size helpers. Included
+// by the file that defines each of them and, through ctx_internal.h, by every file that calls them. A declaration
+// whose types drift from its definition does not build: another return type is an error in the .hip file, other
+// parameter types declare an overload that nothing defines, which the link refuses (-z defs). Parameter names are
+// the definitions'; two same-typed parameters in the wrong order are still for the reader to catch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "fr_device.h"
+
+namespace fr {
+// k_trace.hip
+// (cur_pos, prev_pos: the positions this launch traces and the ones the previous launch traced, for the motion form;
+// NULL for the plain one)
+void launch_gbuffer(const DevScene& sc, const FrameUniforms& U, f4* position, f4* normal, f4* depth, f4* diffuse,
+                    f4* weight, uint8_t* gclass, DevStats* stats, const f3* cur_pos, const f3* prev_pos,
+                    hipStream_t stream);
+void launch_shade_paths(const DevScene& sc, const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count,
+                        uint32_t max_active, const f4* weight, const f4* history_cache, uint32_t* chunk_ctr,
+                        f4* samples, unsigned long long* help, DevStats* stats, f4* aux, uint32_t* aux_seed,
+                        uint32_t chunk_refr, uint32_t xcd_bands, uint32_t handoff, int per_cu, f4* item_store,
+                        hipStream_t stream);
+int shade_max_blocks_per_cu();
+size_t shade_item_store_f4(int per_cu);
+void launch_sample_setup(const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count, uint32_t max_active,
+                         const f4* weight, const f4* history_cache, const unsigned long long* hvalid, f4* aux,
+                         uint32_t* aux_seed, hipStream_t stream);
+void launch_shade_resolve(const FrameUniforms& U, const uint32_t* active, const uint32_t* ray_count,
+                          uint32_t max_active, const f4* weight, const f4* history_cache, const f4* samples,
+                          unsigned long long* help, f4* history_buffer, f4* shading, uint32_t* chunk_ctr,
+                          uint32_t handoff, int per_cu, f4* radiance, hipStream_t stream);
+size_t shade_counter_words();
+size_t shade_fx_slots(uint32_t max_active, int spp, uint32_t handoff, int per_cu);
+void launch_carry_history(const FrameUniforms& U, const uint8_t* mask, const f4* weight, const f4* history_cache,
+                          f4* history_buffer, f4* shading, unsigned long long* hvalid, hipStream_t stream);
+void launch_shard_pack_active(const uint32_t* active, const uint32_t* ray_count, uint32_t capacity, const f4* radiance,
+                              f4* vals, uint32_t* idx, hipStream_t stream);
+void launch_shard_unpack_active(const FrameUniforms& U, const f4* vals, const uint32_t* idx, uint32_t n, uint32_t npix,
+                                const f4* weight, const f4* history_cache, f4* history_buffer, f4* shading,
+                                hipStream_t stream);
+// the history validity rings of a still-camera group: FR_VRING pixels inside each tile
+void launch_vring_pack(const f4* hist, int W, int H, int T, const int32_t* tiles, int ntiles, uint32_t* out,
+                       hipStream_t stream);
+void launch_vring_unpack(const uint32_t* in, int W, int H, int T, const int32_t* tiles, int ntiles, f4* hist,
+                         hipStream_t stream);
+#ifdef FR_STAMPS
+void launch_trace_queries(const DevScene& sc, const f4* queries, uint32_t n, f4* hits, uint32_t* ctr,
+                          hipStream_t stream, int kind);
+void diag_record_queries(f4* buf, uint32_t cap, hipStream_t stream);
+uint32_t diag_recorded_queries(hipStream_t stream);
+void diag_sample_trace(uint32_t* srec, uint32_t scap, uint32_t* wrec, uint32_t wcap, hipStream_t stream);
+#endif
+
+// k_front.hip
+void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* position, const f4* depth,
+                     const f4* depth_cache, f4* weight, const f4* normal, const f4* diffuse, f4* extra, uint8_t* mask,
+                     const uint8_t* gclass, unsigned long long* words, uint32_t* counts, int write_extra,
+                     uint8_t* lp_cache, uint32_t* lp_inv, bool lp_refresh, uint32_t* bcount, bool motion,
+                     const float* dev_box, hipStream_t stream);
+void launch_extra(const FrameUniforms& U, const DevScene& sc, const f4* depth, const f4* weight, const f4* normal,
+                  const f4* diffuse, f4* extra, const float* dev_box, hipStream_t stream);
+size_t logpolar_inv_words(int W, int H);
+void launch_owner_counts(const FrameUniforms& U, const uint32_t* bcount, uint32_t* owner_counts, hipStream_t stream);
+void launch_mask_words(const uint8_t* mask, const uint8_t* gclass, int W, int H, unsigned long long* words,
+                       uint32_t* counts, hipStream_t stream);
+void launch_compaction(int W, int H, const unsigned long long* words, const uint32_t* counts, uint32_t* local_prefix,
+                       uint32_t* tile_sum, uint32_t* ray_count, uint32_t* active, hipStream_t stream);
+size_t compaction_tiles(int W, int H);
+
+// k_post.hip
+void launch_shard_pack(const FrameUniforms& U, const f4* buf, f4* slab, hipStream_t stream);
+void launch_shard_unpack(const FrameUniforms& U, int rank, const f4* slab, f4* buf, hipStream_t stream);
+void launch_logpolar(const f4* in, f4* fwd, f4* inv, int W, int H, f2 gaze, hipStream_t stream);
+void launch_composite(const f4* views, int nviews, int W, int H, f4* out, hipStream_t stream);
+
+// k_jfa.hip, k_sibson.hip
+const u2* launch_jfa(const f4* in, u2* stateA, u2* stateB, f4* coord, f4* color, const float* ftab, int W, int H,
+                     f4* sibP, f4* sibT, bool outputs, int xcd, hipStream_t stream);
+void launch_jfa_coord(const u2* state, const f4* color, f4* coord, int W, int H, hipStream_t stream);
+void launch_sibson(const f4* coord, const f4* color, f4* out, int W, int H, hipStream_t stream);
+void launch_sibson_runs(const f4* coord, const u2* state, const f4* color, f4* P, f4* T, f4* G, uint32_t* wide,
+                        uint32_t* strips, f4* out, int W, int H, bool prefix_fresh, bool strip, int strip_mid,
+                        bool coord_owed, hipStream_t stream);
+int sibson_prefix_blocks(int W);
+size_t sibson_strip_words(int W, int H);
+size_t sibson_rowp_texels(int W, int H);
+
+// k_pullpush.hip, k_atrous.hip
+void launch_pullpush(const f4* in, f4* pull, f4* push, f4* snap, f4* out, int W, int H, hipStream_t stream);
+bool launch_atrous(const f4* pos, const f4* nrm, const f4* col, f4* out, int W, int H, float c_phi, float n_phi,
+                   float p_phi, float stepWidth, bool rows2, int xcd, hipStream_t stream);
+int pp_size(int W, int H);
+size_t pp_snap_count(int S);
+
+// k_bvh.hip
+struct BvhWork;
+bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim, int* num_nodes,
+                   int* max_stack, int* depth, hipStream_t s, std::string& err);
+void bvh_work_free(BvhWork* w);
+bool bvh_work_prepare(BvhWork** w, int n, hipStream_t s, std::string& err);
+bool bvh_builder_warm(BvhWork* w, hipStream_t s, std::string& err);
+bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
+                   hipStream_t s, std::string& err);
+bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
+                           const int32_t* prim, const uint32_t* reject, hipStream_t s, std::string& err);
+bool gpu_check_positions_enqueue(BvhWork* work, const float* xyz, int n, hipStream_t s, std::string& err);
+bool gpu_take_over_positions(BvhWork* work, const f3* xyz, const f3* cur, int n, f3* dst, const uint32_t* bad_nrm,
+                             GeoUpdateState* st, int flags, f3 seed_lo, f3 seed_hi, hipStream_t s, std::string& err);
+bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cost, hipStream_t s, std::string& err);
+bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, float box[6], hipStream_t s,
+                         std::string& err);
+
+// k_normals.hip: shading normals over moving geometry
+struct NormalsWork;
+bool normals_work_create(NormalsWork** out, const int32_t* corner_vertex, const int32_t* off, const int32_t* corners,
+                         int nt, int nv, hipStream_t s, std::string& err);
+void normals_work_free(NormalsWork* w);
+bool gpu_recompute_normals(NormalsWork* w, const f3* pos, TriShade* shade, hipStream_t s, std::string& err);
+bool gpu_check_normals(NormalsWork* w, const float* nrm, bool* finite, hipStream_t s, std::string& err);
+bool gpu_scatter_normals(NormalsWork* w, const float* nrm, TriShade* shade, hipStream_t s, std::string& err);
+// their enqueue halves (no wait; reject, flag: the device verdict word of an enqueued update, or NULL)
+bool gpu_recompute_normals_enqueue(NormalsWork* w, const f3* pos, TriShade* shade, const uint32_t* reject, hipStream_t s,
+                                   std::string& err);
+bool gpu_check_normals_enqueue(NormalsWork* w, const float* nrm, uint32_t* flag, hipStream_t s, std::string& err);
+bool gpu_scatter_normals_enqueue(NormalsWork* w, const float* nrm, TriShade* shade, const uint32_t* reject, hipStream_t s,
+                                 std::string& err);
+
+// k_pose.hip, model poses: a pose's kernel arguments (NULL, or why the pose is refused), the launch that writes the
+// posed rest arrays into the staging arrays, the capture of the rest arrays, and the bytes of one such array
+const char* pose_args(PoseArgs* a, const float* m, int nmodels, const int* first_tri);
+bool gpu_pose_enqueue(const PoseArgs& a, const f3* rest_pos, const f3* rest_nrm, f3* out_pos, f3* out_nrm, int nt,
+                      hipStream_t s, std::string& err);
+bool gpu_pose_capture_enqueue(const f3* pos, const TriShade* shade, f3* rest_pos, f3* rest_nrm, int nt, hipStream_t s,
+                              std::string& err);
+size_t pose_array_bytes(int nt);
+}  // namespace fr

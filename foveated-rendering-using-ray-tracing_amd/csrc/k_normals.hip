@@ -19,6 +19,7 @@
 #include <cfloat>
 #include <string>
 #include "fr_device.h"
+#include "k_launch.h"
 
 namespace fr {
 namespace {

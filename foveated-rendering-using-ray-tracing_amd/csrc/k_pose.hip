@@ -24,6 +24,7 @@
 #include <string>
 
 #include "fr_device.h"
+#include "k_launch.h"
 
 namespace fr {
 namespace {

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "fr_device.h"
+#include "k_launch.h"
 
 namespace fr {
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "fr_device.h"
+#include "k_launch.h"
 #include "k_image.h"
 
 namespace fr {

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "fr_device.h"
+#include "k_launch.h"
 
 namespace fr {
 
