@@ -166,6 +166,8 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   for (auto& f : c->jfa_done) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
   for (auto& e : c->ev_counts) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   hipEventCreateWithFlags(&c->geo_read.ev, hipEventDisableTiming);
+  for (auto& f : c->set_read) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->update_done.ev, hipEventDisableTiming);
   read_env_knobs(c);
 
   std::string err;
@@ -388,7 +390,7 @@ int fr_destroy(fr_ctx* c) {
   for (hipStream_t s : streams) if (s) hipStreamSynchronize(s);
   auto fr = [](void* p) { if (p) hipFree(p); };
   fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
-  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos);
+  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back);
   fr(c->pose_rest_pos); fr(c->pose_rest_nrm); fr(c->pose_stage_pos); fr(c->pose_stage_nrm);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   if (c->nrm_work) normals_work_free(c->nrm_work);
@@ -401,6 +403,8 @@ int fr_destroy(fr_ctx* c) {
   fr(c->geo);
   if (c->h_geo) hipHostFree(c->h_geo);
   if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
+  for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);
+  if (c->update_done.ev) hipEventDestroy(c->update_done.ev);
   for (auto e : c->ev_counts) if (e) hipEventDestroy(e);
   fr(c->gclass); fr(c->lp_cache); fr(c->lp_inv); fr(c->words); fr(c->counts); fr(c->offsets); fr(c->tiles); fr(c->shade_ctr); fr(c->samples); fr(c->sample_help); fr(c->aux_p[0]); fr(c->aux_p[1]); fr(c->aux_seed_p[0]); fr(c->aux_seed_p[1]); fr(c->hvalid); fr(c->item_store); fr(c->jfa_a); fr(c->jfa_b); fr(c->ftab);
   fr(c->pull); fr(c->push); fr(c->snap); fr(c->stats); fr(c->sib_prefix); fr(c->sib_blocks); fr(c->sib_wide); fr(c->sib_strips); fr(c->sib_rowp);

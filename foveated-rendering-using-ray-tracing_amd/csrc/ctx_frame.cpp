@@ -70,16 +70,20 @@ void fc_harvest(fr_ctx* c, int i) {
   c->fc_prev_end = e;
 }
 
+void join_update(fr_ctx* c) { c->update_done.consume(c->stream); }
+
 void join_recon(fr_ctx* c) {
   c->stream_dirty = true;  // the caller is about to enqueue on `stream` outside a pipelined frame
   for (Fence& f : c->recon_done) f.consume(c->stream);
   c->front_done.consume(c->stream);
+  join_update(c);
 }
 
 int quiesce(fr_ctx* c) {
   join_recon(c);
   hipSetDevice(c->cfg.device);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (Fence& f : c->set_read) f.pending = false;  // (recorded on `stream`: every reader of both sets has finished)
   return FR_OK;
 }
 }  // namespace fri
@@ -125,6 +129,8 @@ static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
   c->motion_frame = motion;
   c->moved = false;
   c->compacted = false;
+  // (a G-buffer on front_stream is ordered before an overlapped update by the stream itself)
+  if (c->overlap_on && fs == c->stream) c->set_read[c->set_cur].record(c->stream);
   return check_launch(c);
 }
 
@@ -218,6 +224,9 @@ int fri::enqueue_shading(fr_ctx* c) {
   if (kt) hipEventRecord(kt[3], c->stream);
   // this slot's WEIGHT / mask / active list are free for the front stages of frame + nslots after this
   c->trace_done[c->slot].record(c->stream);
+  // overlapped updates: the megakernel was the last reader of the scene's tree and normals; the update after the
+  // next one writes them (fr_set_geometry_overlap)
+  if (c->overlap_on) c->set_read[c->set_cur].record(c->stream);
   int rc = check_launch(c);
   // swapBuffer("history_cache", "history_buffer"); swapBuffer("depth_cache", "depth_buffer") (:226-227)
   std::swap(c->hist_cur, c->hist_cache);
@@ -427,7 +436,10 @@ int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
       c->fc_cur = -1;
     }
   } fc_guard{c};
-  if (t) hipEventRecord(T.begin, c->stream);
+  if (t) {
+    join_update(c);  // a timed frame's stages all run on `stream`: behind an overlapped update on front_stream
+    hipEventRecord(T.begin, c->stream);
+  }
   if (trace) {
     // untimed frames pipeline: the front stages go to front_stream and overlap the previous frame's
     // entry 3 (timed frames keep every stage on `stream`, one after the other)

@@ -1,6 +1,6 @@
 // ctx_geometry.cpp — the scene's geometry after fr_create: the tree (GPU rebuild, refit, SAH cost), position and
-// normal updates (synchronous and in stream order), the model table and poses by matrix, motion reprojection's switch,
-// and the scene export calls.
+// normal updates (synchronous; in stream order, in place or overlapped into a second set), the model table and poses
+// by matrix, the switches of motion reprojection and of overlapped updates, and the scene export calls.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -48,6 +48,7 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
     if (!alloc_spare()) {
       hipFree(c->spare_nodes); hipFree(c->spare_tri); hipFree(c->spare_prim);
       c->spare_nodes = nullptr; c->spare_tri = nullptr; c->spare_prim = nullptr;  // allocated again next time
+      c->overlap_on = false;  // (no second tree: updates are in place until fr_set_geometry_overlap makes one)
     }
   }
   c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim;
@@ -257,19 +258,37 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
   return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
 }
 
-// fr_update_geometry (device memory, refit) in stream order: every launch below goes on the context stream and
-// nothing here waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no synchronisation, no copy to
-// the host, no allocation). What the host learnt from the device in update_positions stays there: the verdict of
+// fr_update_geometry (device memory, refit) in stream order: every launch below goes on one stream and nothing
+// here waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no synchronisation, no copy to the
+// host, no allocation). What the host learnt from the device in update_positions stays there: the verdict of
 // the two checks is a device word that k_take_over publishes and every later kernel of the update reads, and the
 // scene box goes from the check's result into geo->box, where the saliency stage reads it from now on.
 // The three position arrays rotate here, at enqueue time and whatever the verdict, exactly as in update_positions;
 // their contents follow in stream order (k_take_over fills the array that becomes d_pos with the caller's
-// positions, or with the current ones when the update is rejected). That is safe because every reader and writer
+// positions, or with the current ones when the update is rejected).
+// In place (the default), the stream is the context stream. That is safe because every reader and writer
 // of the three arrays, the tree and the normals is ordered on the context stream: the front stages of a pipelined
 // frame run on front_stream, but entry 3 of that frame waits for them on the context stream (front_done) before this
 // update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
 // The reconstruction streams read none of it, so they are not joined.
-// (pose: fr_set_model_transforms_enqueue, whose k_pose produces xyz and nrm, the staging arrays, on the context stream)
+// Overlapped (fr_set_geometry_overlap), the stream is front_stream, and tree and normals are written out of place,
+// into the set no frame in flight reads, which becomes the scene's here (a swap, and dsc's pointers). The hazards:
+//  - the set written was the scene's until the previous update: its last reader on the context stream is a
+//    megakernel (or a G-buffer there), whose fence front_stream waits for (set_read); the G-buffers of pipelined
+//    frames, the only other readers of it and of the position arrays, are earlier work of front_stream itself;
+//  - the set read (the scene's) was written by the previous update, on front_stream, or by a synchronous call,
+//    which the host waited for;
+//  - the megakernel that reads the result waits for its own front stages (front_done), enqueued behind this update;
+//  - the scratch of the checks, the refit and the normals, geo (verdict, counters, box, xbox) and the pose staging
+//    arrays are shared with what the context stream runs outside a pipelined frame: all of that waits for the
+//    update (update_done, consumed by join_recon), and the update waits for it where the front stages would
+//    (stream_dirty: ev_stream_join). An owed EXTRA's k_extra, which reads geo->box or geo->xbox, is such work.
+//  - two or three updates before one G-buffer alternate the sets; each waits for its own set's fence, so the second
+//    one waits for the megakernel still reading the set it writes, and reads what the first wrote in stream order;
+//  - after a synchronous rebuild the other set holds another topology: nothing of it is kept (every node, triangle
+//    and leaf index is written);
+//  - a failed frame's front stages without their entry 3 are earlier work of front_stream.
+// (pose: fr_set_model_transforms_enqueue, whose k_pose produces xyz and nrm, the staging arrays, on the same stream)
 static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, const void* nrm, size_t ntris, int normals,
                           void* ready_event, const fr::PoseArgs* pose = nullptr) {
   if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
@@ -279,44 +298,75 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
                                          (pose ? "fr_set_model_transforms)" : "fr_update_geometry)"));
   if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
   hipSetDevice(c->cfg.device);
-  c->stream_dirty = true;  // the next pipelined frame's front stages (front_stream) start after this update
-  // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
-  c->front_done.consume(c->stream);
-  if (ready_event) HIP_TRY(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ready_event), 0));
+  const bool overlap = c->overlap_on;
+  const hipStream_t s = overlap ? c->front_stream : c->stream;
+  // whatever was enqueued of an overlapped update, the context stream's next work outside a frame waits for it
+  struct Done {
+    fr_ctx* c;
+    bool on;
+    ~Done() { if (on) c->update_done.record(c->front_stream); }
+  } done{c, overlap};
+  if (overlap) {
+    if (c->stream_dirty) {
+      hipEventRecord(c->ev_stream_join, c->stream);
+      hipStreamWaitEvent(s, c->ev_stream_join, 0);
+      c->stream_dirty = false;  // the next frame's front stages follow this update on front_stream
+    }
+    c->set_read[c->set_cur ^ 1].consume(s);
+  } else {
+    c->stream_dirty = true;  // the next pipelined frame's front stages (front_stream) start after this update
+    // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
+    c->front_done.consume(c->stream);
+  }
+  if (ready_event) HIP_TRY(c, hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready_event), 0));
   const int nt = (int)ntris;
   std::string err;
-  if (pose && !gpu_pose_enqueue(*pose, c->pose_rest_pos, c->pose_rest_nrm, c->pose_stage_pos, c->pose_stage_nrm, nt,
-                                c->stream, err))
+  if (pose && !gpu_pose_enqueue(*pose, c->pose_rest_pos, c->pose_rest_nrm, c->pose_stage_pos, c->pose_stage_nrm, nt, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
-  if (!gpu_check_positions_enqueue(c->bvh_work, static_cast<const float*>(xyz), nt, c->stream, err))
+  if (!gpu_check_positions_enqueue(c->bvh_work, static_cast<const float*>(xyz), nt, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   const bool given = normals == FR_NORMALS_GIVEN;
-  if (given && !gpu_check_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), &c->geo->bad_nrm, c->stream, err))
+  if (given && !gpu_check_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), &c->geo->bad_nrm, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   // the box: seeded from the host's at the first enqueue; an owed EXTRA keeps the one its sampling launch saw
   const int flags = (c->dev_box ? 0 : 1) | (extra_keeps_box(c) ? 2 : 0);  // (2: k_take_over makes the copy)
   if (!gpu_take_over_positions(c->bvh_work, static_cast<const f3*>(xyz), c->d_pos, nt, c->spare_pos,
                                given ? &c->geo->bad_nrm : nullptr, c->geo, flags, c->scene.bbox_min, c->scene.bbox_max,
-                               c->stream, err))
+                               s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   c->dev_box = c->geo->box;
   c->box_mirror_stale = true;
-  if (!given) HIP_TRY(c, c->geo_read.record(c->stream));  // xyz has been read
+  if (!given) HIP_TRY(c, c->geo_read.record(s));  // xyz has been read
   const uint32_t* reject = &c->geo->reject;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
-  if (!gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, c->stream, err))
+  if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim,
+                                          c->spare_nodes, c->spare_tri, c->spare_prim, reject, s, err)
+              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   rotate_positions(c);
   c->pos_mirror_stale = true;
-  if (given) {
-    if (!gpu_scatter_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), c->d_shade, reject, c->stream, err))
+  const bool recompute = normals == FR_NORMALS_RECOMPUTE;
+  if (overlap) {
+    // (FR_NORMALS_KEEP as well: the other set's normals are from before the previous update)
+    if (!gpu_normals_to_enqueue(c->nrm_work, given ? static_cast<const float*>(nrm) : nullptr,
+                                recompute ? c->d_pos : nullptr, c->d_shade, c->shade_back, reject, s, err))
       return fail(c, FR_E_HIP, name + ": " + err);
-    HIP_TRY(c, c->geo_read.record(c->stream));  // nrm has been read as well
-    c->nrm_mirror_stale = true;
-  } else if (normals == FR_NORMALS_RECOMPUTE) {
-    if (!gpu_recompute_normals_enqueue(c->nrm_work, c->d_pos, c->d_shade, reject, c->stream, err))
+  } else if (given) {
+    if (!gpu_scatter_normals_enqueue(c->nrm_work, static_cast<const float*>(nrm), c->d_shade, reject, s, err))
       return fail(c, FR_E_HIP, name + ": " + err);
-    c->nrm_mirror_stale = true;
+  } else if (recompute) {
+    if (!gpu_recompute_normals_enqueue(c->nrm_work, c->d_pos, c->d_shade, reject, s, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+  }
+  if (given) HIP_TRY(c, c->geo_read.record(s));  // nrm has been read as well
+  if (given || recompute) c->nrm_mirror_stale = true;
+  if (overlap) {
+    std::swap(c->d_nodes, c->spare_nodes);
+    std::swap(c->d_tri, c->spare_tri);
+    std::swap(c->d_prim, c->spare_prim);
+    std::swap(c->d_shade, c->shade_back);
+    c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim; c->dsc.shade = c->d_shade;
+    c->set_cur ^= 1;
   }
   return FR_OK;
 }
@@ -477,6 +527,52 @@ int fr_set_motion_reprojection(fr_ctx* c, int on) {
   return FR_OK;
 }
 
+// The second set of fr_set_geometry_overlap: the GPU builder's spare tree arrays (fr_create made them, with room for
+// any device-built tree; a host-built tree of more nodes than that gets bigger ones, once) and a second TriShade
+// array, copied from d_shade. On a quiet context. Either everything is made or nothing is kept.
+static int make_second_set(fr_ctx* c, const std::string& name) {
+  const size_t nt = (size_t)c->scene.num_tris(), cap = std::max<size_t>(nt, 1), nn = (size_t)tree_nodes(c->bvh);
+  const bool first = !c->shade_back;
+  const bool tree = !c->spare_nodes || (first && nn > cap);
+  BvhNode* nodes = nullptr;
+  TriGeo* tri = nullptr;
+  int32_t* prim = nullptr;
+  TriShade* shade = nullptr;
+  bool ok = true;
+  if (tree)
+    ok = hipMalloc((void**)&nodes, std::max(cap, nn) * sizeof(BvhNode)) == hipSuccess &&
+         hipMalloc((void**)&tri, cap * sizeof(TriGeo)) == hipSuccess &&
+         hipMalloc((void**)&prim, cap * sizeof(int32_t)) == hipSuccess;
+  if (ok && first)
+    ok = dalloc(&shade, cap) == hipSuccess &&
+         hipMemcpyAsync(shade, c->d_shade, nt * sizeof(TriShade), hipMemcpyDeviceToDevice, c->stream) == hipSuccess &&
+         hipStreamSynchronize(c->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)nodes, (void*)tri, (void*)prim, (void*)shade})
+      if (p) hipFree(p);
+    return fail(c, FR_E_NOMEM, name + ": device allocation (second tree and normals) failed");
+  }
+  if (tree) {
+    for (void* p : {(void*)c->spare_nodes, (void*)c->spare_tri, (void*)c->spare_prim})
+      if (p) hipFree(p);
+    c->spare_nodes = nodes; c->spare_tri = tri; c->spare_prim = prim;
+  }
+  if (first) c->shade_back = shade;
+  return FR_OK;
+}
+
+int fr_set_geometry_overlap(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_geometry_overlap";
+  if (on != 0 && on != 1) return fail(c, FR_E_INVALID, name + ": on is 0 or 1");
+  if (int rc = quiesce(c)) return rc;
+  if (on)
+    if (int rc = make_second_set(c, name)) return rc;
+  c->overlap_on = on != 0;
+  return FR_OK;
+}
+
 int fr_set_normals(fr_ctx* c, const void* nrm, size_t ntris, int where) {
   if (!c) return FR_E_INVALID;
   const std::string name = "fr_set_normals";
@@ -533,6 +629,15 @@ int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size
   return FR_OK;
 }
 
+// Test hook (not part of include/fovrt.h): the device addresses of the tree and the normals in use (a frame enqueued
+// now reads them there). No wait.
+int fr__scene_addresses(fr_ctx* c, const void** nodes, const void** shade) {
+  if (!c || !nodes || !shade) return FR_E_INVALID;
+  *nodes = c->d_nodes;
+  *shade = c->d_shade;
+  return FR_OK;
+}
+
 }  // extern "C"
 
 struct fr_scene {
@@ -574,7 +679,9 @@ int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
   if (!c || !o) return FR_E_INVALID;
   if (c->geo_read.pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
     // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
+    // (nor for front_stream, where an overlapped update runs: the context stream waits for that one first)
     hipSetDevice(c->cfg.device);
+    join_update(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (c->pos_mirror_stale) {  // positions last came from device memory (fr_update_positions): fetch them now

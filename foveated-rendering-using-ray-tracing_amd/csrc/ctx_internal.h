@@ -67,7 +67,8 @@ struct fr_ctx {
   hipStream_t atrous_stream = nullptr;  // reconstruction chain 2: pull-push -> A-Trous
   hipStream_t sibson_stream = nullptr;  // reconstruction chain 1: JFA -> Sibson
   hipStream_t carry_stream = nullptr;   // entry 3's carry of the inactive pixels, beside the megakernel
-  hipStream_t front_stream = nullptr;   // front stages of a pipelined frame (entries 0-2), beside the previous megakernel
+  // front stages of a pipelined frame (entries 0-2), beside the previous megakernel; overlapped updates between them
+  hipStream_t front_stream = nullptr;
   // Invariant for front_stream: its front stages wait only for the slot fences (recon_done, trace_done), not for
   // earlier work on `stream`, although they overwrite shared buffers (gclass, DIFFUSE, EXTRA, depth,
   // ballots, counts, lp_cache). So every ABI call that enqueues on `stream` outside a pipelined frame
@@ -195,6 +196,19 @@ struct fr_ctx {
   f3 *pose_rest_pos = nullptr, *pose_rest_nrm = nullptr, *pose_stage_pos = nullptr, *pose_stage_nrm = nullptr;
   bool pose_on = false;
   std::vector<float> pose_m;
+  // Overlapped updates (fr_set_geometry_overlap). While overlap_on, an enqueued update runs on front_stream and writes
+  // the set no frame in flight reads: the spare tree arrays above and shade_back (made by the first on = 1, a copy of
+  // d_shade), which then become the scene's (a swap with d_nodes / d_tri / d_prim / d_shade and a refresh of dsc;
+  // frames already enqueued keep the dsc they were given). set_cur: which of the two sets is the scene's.
+  // set_read[i]: recorded on the context stream after the last reader of set i there (entry 3; a G-buffer on the
+  // context stream); front_stream waits for the other set's before the update's first write. update_done: recorded on
+  // front_stream after the update's last kernel; the context stream waits for it before anything it runs outside a
+  // pipelined frame (join_update, in join_recon), and a pipelined frame's front stages follow it on front_stream.
+  bool overlap_on = false;
+  TriShade* shade_back = nullptr;
+  int set_cur = 0;
+  Fence set_read[2];
+  Fence update_done;
   int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
   // the smooth-vertex weld of the scene as fr_create built it (host), and on the device with the scratch of
@@ -328,8 +342,11 @@ namespace fri {
 int fail(fr_ctx* c, int code, const std::string& msg);  // sets the error text (of fr_create when c is NULL)
 int check_launch(fr_ctx* c);
 // The context stream waits for every reconstruction still in flight (before any call that reads or
-// writes what the reconstruction uses, or hands buffers to the caller).
+// writes what the reconstruction uses, or hands buffers to the caller). Calls join_update.
 void join_recon(fr_ctx* c);
+// The context stream waits for an overlapped update still in flight on front_stream (fr_set_geometry_overlap): it
+// shares the update scratch, the staging arrays and geo with everything the context stream runs outside a frame.
+void join_update(fr_ctx* c);
 int quiesce(fr_ctx* c);  // join_recon, then the host waits for the context stream
 // one frame half on the context; trace / recon as fr_trace_frame / fr_reconstruct_frame (recon runs the
 // chains in c->recon_chains)

@@ -398,6 +398,108 @@ __global__ void k_refit_up(BvhNode* nodes, int nn, const f3* __restrict__ pos, c
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Refit out of place (fr_set_geometry_overlap): the same three kernels reading one tree (src) and writing another
+// (dst), which no frame in flight reads. dst is two updates old, or a replaced tree of another topology, so nothing
+// of it is kept: every node is written whole (the new boxes around src's child / count; an empty slot's boxes are
+// src's), tri[j] is rebuilt and prim copied. The accepted result is the in-place refit's, byte for byte. A rejected
+// update (*reject != 0, one uniform load per kernel) cannot write nothing here: the same launches then copy src's
+// nodes and triangles verbatim. 16-B loads and stores throughout (a node is eight of them, a TriGeo three).
+// ---------------------------------------------------------------------------------------------
+__global__ void k_refit_tris_to(const f3* __restrict__ pos, const int32_t* __restrict__ prim,
+                                const TriGeo* __restrict__ src, int n, TriGeo* __restrict__ dst,
+                                int32_t* __restrict__ prim_dst, const uint32_t* __restrict__ reject) {
+  const uint32_t rej = *reject;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int p = prim[j];
+  prim_dst[j] = p;
+  if (rej) {
+    const TriGeo g = src[j];
+    dst[j].a = g.a; dst[j].b = g.b; dst[j].c = g.c;
+  } else {
+    store_tri_geo(pos, p, &dst[j]);
+  }
+}
+
+// k_refit_links over src. Rejected: the copy of the nodes instead, one 16-B word per lane, consecutive lanes
+// consecutive words (the grid's nn lanes take eight words each).
+__global__ void k_refit_links_to(const BvhNode* __restrict__ src, int nn, int* __restrict__ parent,
+                                 uint32_t* __restrict__ arrivals, BvhNode* __restrict__ dst,
+                                 const uint32_t* __restrict__ reject) {
+  if (*reject) {
+    const f4* s4 = reinterpret_cast<const f4*>(src);
+    f4* d4 = reinterpret_cast<f4*>(dst);
+    const size_t n4 = (size_t)nn * 8, first = (size_t)blockIdx.x * blockDim.x * 8 + threadIdx.x;
+    for (int k = 0; k < 8; k++) {
+      const size_t q = first + (size_t)k * blockDim.x;
+      if (q < n4) d4[q] = s4[q];
+    }
+    return;
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  arrivals[i] = 0u;
+  if (i == 0) parent[0] = -1;
+  for (int k = 0; k < 4; k++)
+    if (src[i].count[k] == 0) parent[src[i].child[k]] = i;
+}
+
+// k_refit_up's walk over src's topology; the thread that finishes a node stores it whole into dst.
+__global__ void k_refit_up_to(const BvhNode* __restrict__ src, BvhNode* __restrict__ dst, int nn,
+                              const f3* __restrict__ pos, const int32_t* __restrict__ prim,
+                              const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi,
+                              const uint32_t* __restrict__ reject) {
+  if (*reject) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn) return;
+  int node = i;
+  {
+    const int* cnt = src[i].count;
+    if (cnt[0] == 0 || cnt[1] == 0 || cnt[2] == 0 || cnt[3] == 0) return;
+  }
+  for (;;) {
+    BvhNode nd = src[node];
+    float* LX = &nd.lox.x; float* HX = &nd.hix.x;
+    float* LY = &nd.loy.x; float* HY = &nd.hiy.x;
+    float* LZ = &nd.loz.x; float* HZ = &nd.hiz.x;
+    f3 nlo3 = mk3(INFINITY), nhi3 = mk3(-INFINITY);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int cnt = nd.count[k], ch = nd.child[k];
+      if (cnt < 0) continue;  // an empty slot keeps src's +inf / -inf / child 0
+      f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+      if (cnt == 0) {
+        lo = xyz(load_agent(nlo + ch));
+        hi = xyz(load_agent(nhi + ch));
+      } else {
+        for (int j = 0; j < cnt; j++) {
+          const int p = prim[ch + j];
+          for (int v = 0; v < 3; v++) {
+            const f3 q = pos[3 * p + v];
+            lo = mk3(fminf(lo.x, q.x), fminf(lo.y, q.y), fminf(lo.z, q.z));
+            hi = mk3(fmaxf(hi.x, q.x), fmaxf(hi.y, q.y), fmaxf(hi.z, q.z));
+          }
+        }
+      }
+      LX[k] = inflate_lo_d(lo.x); HX[k] = inflate_hi_d(hi.x);
+      LY[k] = inflate_lo_d(lo.y); HY[k] = inflate_hi_d(hi.y);
+      LZ[k] = inflate_lo_d(lo.z); HZ[k] = inflate_hi_d(hi.z);
+      nlo3 = mk3(fminf(nlo3.x, lo.x), fminf(nlo3.y, lo.y), fminf(nlo3.z, lo.z));
+      nhi3 = mk3(fmaxf(nhi3.x, hi.x), fmaxf(nhi3.y, hi.y), fmaxf(nhi3.z, hi.z));
+    }
+    dst[node] = nd;
+    const int up = parent[node];
+    if (up < 0) return;
+    store_agent(nlo + node, nlo3);
+    store_agent(nhi + node, nhi3);
+    const int* pc = src[up].count;
+    const uint32_t inner = (uint32_t)(pc[0] == 0) + (uint32_t)(pc[1] == 0) + (uint32_t)(pc[2] == 0) + (uint32_t)(pc[3] == 0);
+    if (__hip_atomic_fetch_add(&arrivals[up], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u != inner) return;
+    node = up;
+  }
+}
+
 // SAH cost terms: part[i] = sum over node i's non-empty slots of area(stored box) * (1 for an inner slot, count
 // for a leaf slot); *root_area = the area of the union of node 0's slot boxes.
 __global__ void k_cost_terms(const BvhNode* __restrict__ nodes, int nn, float* __restrict__ part,
@@ -672,6 +774,34 @@ bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, 
     hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals, reject);
     hipLaunchKernelGGL(up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo, w.nhi,
                        reject);
+  }
+  if (hipGetLastError() != hipSuccess) {
+    err = "GPU BVH refit: launch failure";
+    return false;
+  }
+  return true;
+}
+
+// The refit of an enqueued update out of place (k_refit_*_to): from the tree in use (src_*) over `pos` into the
+// arrays no frame in flight reads (dst_*, room for num_nodes nodes and n triangles), whole. reject: the device
+// verdict word, never NULL. The same scratch, the same three launches, no wait.
+bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
+                              const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
+                              int32_t* dst_prim, const uint32_t* reject, hipStream_t s, std::string& err) {
+  if (!work || !reject || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
+    err = "GPU BVH refit: no workspace for this tree";
+    return false;
+  }
+  BvhWork& w = *work;
+  const int B = 256;
+  hipLaunchKernelGGL(k_refit_tris_to, dim3((n + B - 1) / B), dim3(B), 0, s, pos, src_prim, src_tri, n, dst_tri, dst_prim,
+                     reject);
+  if (num_nodes > 0) {
+    const int GN = (num_nodes + B - 1) / B;
+    hipLaunchKernelGGL(k_refit_links_to, dim3(GN), dim3(B), 0, s, src_nodes, num_nodes, w.parent, w.arrivals, dst_nodes,
+                       reject);
+    hipLaunchKernelGGL(k_refit_up_to, dim3(GN), dim3(B), 0, s, src_nodes, dst_nodes, num_nodes, pos, src_prim, w.parent,
+                       w.arrivals, w.nlo, w.nhi, reject);
   }
   if (hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: launch failure";

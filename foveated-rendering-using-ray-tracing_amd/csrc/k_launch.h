@@ -107,6 +107,10 @@ bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_
                    hipStream_t s, std::string& err);
 bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
                            const int32_t* prim, const uint32_t* reject, hipStream_t s, std::string& err);
+// the refit of an enqueued update out of place: from the tree in use into another set of arrays, whole
+bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
+                              const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
+                              int32_t* dst_prim, const uint32_t* reject, hipStream_t s, std::string& err);
 bool gpu_check_positions_enqueue(BvhWork* work, const float* xyz, int n, hipStream_t s, std::string& err);
 bool gpu_take_over_positions(BvhWork* work, const f3* xyz, const f3* cur, int n, f3* dst, const uint32_t* bad_nrm,
                              GeoUpdateState* st, int flags, f3 seed_lo, f3 seed_hi, hipStream_t s, std::string& err);
@@ -128,6 +132,10 @@ bool gpu_recompute_normals_enqueue(NormalsWork* w, const f3* pos, TriShade* shad
 bool gpu_check_normals_enqueue(NormalsWork* w, const float* nrm, uint32_t* flag, hipStream_t s, std::string& err);
 bool gpu_scatter_normals_enqueue(NormalsWork* w, const float* nrm, TriShade* shade, const uint32_t* reject, hipStream_t s,
                                  std::string& err);
+// the normals of an enqueued update out of place: src's records into dst with the given normals (nrm), the
+// recomputed ones (pos), or src's own (both NULL)
+bool gpu_normals_to_enqueue(NormalsWork* w, const float* nrm, const f3* pos, const TriShade* src, TriShade* dst,
+                            const uint32_t* reject, hipStream_t s, std::string& err);
 
 // k_pose.hip, model poses: a pose's kernel arguments (NULL, or why the pose is refused), the launch that writes the
 // posed rest arrays into the staging arrays, the capture of the rest arrays, and the bytes of one such array

@@ -103,6 +103,44 @@ __global__ void k_scatter_given(const int32_t* __restrict__ corner_vertex, int n
   }
 }
 
+// The normals of an enqueued update out of place (fr_set_geometry_overlap): src's TriShade records into dst, which
+// is two updates old, with the new normals on the way. One lane per 16-B word of a record (n0, n1, n2, t), so
+// consecutive lanes load and store consecutive words; words 0..2 are corner k's (normal, texture coordinate), whose
+// .xyz take k_scatter_given's or k_scatter_recomputed's value where those kernels write, and src's where they do not.
+// NRM_COPY (FR_NORMALS_KEEP), and every rejected update (*reject != 0, one uniform load): the plain copy. Writing
+// nothing is no option: dst would bring back the normals from before the previous update.
+enum { NRM_COPY, NRM_GIVEN, NRM_RECOMPUTED };
+template <int MODE>
+__global__ void k_normals_to(const TriShade* __restrict__ src, TriShade* __restrict__ dst,
+                             const int32_t* __restrict__ corner_vertex, int nt, const float* __restrict__ nrm,
+                             const f4* __restrict__ vnrm, const f3* __restrict__ face,
+                             const uint32_t* __restrict__ reject) {
+  const bool copy = MODE == NRM_COPY || *reject != 0u;
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= 4 * (size_t)nt) return;
+  f4 w = reinterpret_cast<const f4*>(src)[q];
+  const int k = (int)(q & 3);
+  if (!copy && k < 3) {
+    const size_t t = q >> 2, c = 3 * t + k;
+    const int v = corner_vertex[c];
+    if (v >= 0) {
+      if (MODE == NRM_GIVEN) {
+        store_xyz(&w, mk3(nrm[3 * c], nrm[3 * c + 1], nrm[3 * c + 2]));
+      } else {
+        const f4 n = vnrm[v];
+        if (n.w != 0.0f) {
+          store_xyz(&w, xyz(n));
+        } else {
+          const f3 f = face[t];
+          const float d = dot(f, f);
+          if (normalisable(d)) store_xyz(&w, f * (1.0f / sqrtf(d)));
+        }
+      }
+    }
+  }
+  reinterpret_cast<f4*>(dst)[q] = w;
+}
+
 template <typename T>
 hipError_t alloc(T** p, size_t n) {
   return hipMalloc((void**)p, (n > 0 ? n : 1) * sizeof(T));
@@ -235,6 +273,28 @@ bool gpu_scatter_normals_enqueue(NormalsWork* w, const float* nrm, TriShade* sha
     hipLaunchKernelGGL(sg, dim3(blocks(w->nt)), dim3(kBlock), 0, s, w->corner_vertex, w->nt, nrm, shade, reject);
   }
   return launched("normals scatter", err);
+}
+
+// The normals of an enqueued update out of place (k_normals_to): src's records into dst with the caller's normals
+// (nrm: device, 9 floats per triangle), the recomputed ones (pos: the positions now in place), or src's own (both
+// NULL). reject: the device verdict word, never NULL. No wait.
+bool gpu_normals_to_enqueue(NormalsWork* w, const float* nrm, const f3* pos, const TriShade* src, TriShade* dst,
+                            const uint32_t* reject, hipStream_t s, std::string& err) {
+  if (!w || !reject) { err = "normals: no workspace"; return false; }
+  const int G = blocks(4 * (size_t)w->nt);
+  const int32_t* cv = w->corner_vertex;
+  if (w->nv == 0 || (!nrm && !pos)) {
+    hipLaunchKernelGGL(k_normals_to<NRM_COPY>, dim3(G), dim3(kBlock), 0, s, src, dst, cv, w->nt, nrm, w->vnrm, w->face, reject);
+  } else if (nrm) {
+    hipLaunchKernelGGL(k_normals_to<NRM_GIVEN>, dim3(G), dim3(kBlock), 0, s, src, dst, cv, w->nt, nrm, w->vnrm, w->face, reject);
+  } else {
+    hipLaunchKernelGGL(k_face_cross<true>, dim3(blocks(w->nt)), dim3(kBlock), 0, s, pos, w->nt, w->face, reject);
+    hipLaunchKernelGGL(k_vertex_normals<true>, dim3(blocks(w->nv)), dim3(kBlock), 0, s, w->off, w->corners, w->nv, w->face,
+                       w->vnrm, reject);
+    hipLaunchKernelGGL(k_normals_to<NRM_RECOMPUTED>, dim3(G), dim3(kBlock), 0, s, src, dst, cv, w->nt, nrm, w->vnrm, w->face,
+                       reject);
+  }
+  return launched("normals (out of place)", err);
 }
 
 bool gpu_scatter_normals(NormalsWork* w, const float* nrm, TriShade* shade, hipStream_t s, std::string& err) {

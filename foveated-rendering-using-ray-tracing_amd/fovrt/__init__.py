@@ -180,6 +180,7 @@ _SIGS = {
     "fr_update_geometry": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int],
     "fr_update_geometry_enqueue": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "fr_geometry_consumed": [C.c_void_p, C.c_void_p],
+    "fr_set_geometry_overlap": [C.c_void_p, C.c_int],
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_model_count": [C.c_void_p, C.POINTER(C.c_int)],
     "fr_model_info": [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -691,6 +692,12 @@ class PathTracer:
         the device for the last enqueued update's reads of the caller's arrays. Does not block the host."""
         s = getattr(stream, "cuda_stream", stream)
         self._check(_lib.fr_geometry_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
+
+    def set_geometry_overlap(self, on=True):
+        """fr_set_geometry_overlap: enqueued updates and enqueued poses refit into a second tree and write second
+        normals on the front stages' stream, beside the previous frame's path trace (off by default; the first on
+        allocates 64 B per triangle). Waits for the context's pending work."""
+        self._check(_lib.fr_set_geometry_overlap(self._ctx, int(bool(on))))
 
     def geometry_update_status(self):
         """(applied, rejected): enqueued updates by their verdict on the device since the context was created.

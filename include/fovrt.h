@@ -469,13 +469,30 @@ int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* 
  * box (the depth term of the saliency mask) stays in device memory from a context's first enqueued update on;
  * fr_scene_export fetches it, with positions and normals, when asked. The next pipelined frame's front stages
  * start after the update, so they no longer overlap the previous frame's path trace (the tree is refitted in
- * place). Synchronous updates, fr_refit_bvh, fr_set_normals, fr_recompute_normals, fr_snapshot and fr_restore
- * keep their behaviour after enqueued updates (they wait for pending work as always).
- * Not covered: groups and sharded contexts, a rebuild without synchronisation, host-memory arrays, a second tree
- * that would let the front stages overlap the previous path trace again. */
+ * place; fr_set_geometry_overlap below gives the overlap back). Synchronous updates, fr_refit_bvh, fr_set_normals,
+ * fr_recompute_normals, fr_snapshot and fr_restore keep their behaviour after enqueued updates (they wait for
+ * pending work as always).
+ * Not covered: groups and sharded contexts, a rebuild without synchronisation, host-memory arrays. */
 int fr_update_geometry_enqueue(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntris, int normals,
                                void* ready_event);
 int fr_geometry_consumed(fr_ctx* ctx, void* stream);
+/* Enqueued updates beside the path trace (off by default). In place, an enqueued update sits on the context stream
+ * between the path trace of the frame before it, which still reads tree and normals, and the front stages of the
+ * frame after it. With overlap on, fr_update_geometry_enqueue and fr_set_model_transforms_enqueue refit into a
+ * second tree and write a second array of shading records, which no frame in flight reads, on the stream of the
+ * front stages; those arrays become the scene's when the call returns (frames already enqueued keep the ones they
+ * were given), and the next frame's G-buffer, sampling and compaction follow the update beside the previous path
+ * trace. Every word of the two calls' contracts holds: the checks, the verdict on the device (a rejected update
+ * leaves the scene as it was, bit for bit), the counters, ready_event, fr_geometry_consumed,
+ * fr_geometry_update_status, motion reprojection, the scene box, and bytes equal to the synchronous update's.
+ * Every other call behaves as before and orders itself behind a pending update.
+ * The first on = 1 makes the second set: the tree arrays fr_create made for fr_rebuild_bvh serve as the second
+ * tree (a host-built tree of more nodes than triangles gets bigger ones), and 64 B per triangle are allocated and
+ * copied for the shading records (FR_E_NOMEM: nothing is kept and the setting stays off). on = 0 returns to
+ * updates in place and frees nothing. No update allocates. The call waits for the context's pending work.
+ * FR_E_INVALID for a NULL context or on outside {0, 1}. With overlap off nothing differs from a context that never
+ * made the call. Not covered: groups and sharded contexts (their enqueued updates stay FR_E_UNSUPPORTED). */
+int fr_set_geometry_overlap(fr_ctx* ctx, int on);
 int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected);
 /* The scene's models, posed by matrix on the device. A scene is assembled from rigid models (ground, box, bunny,
  * earth, vokselia_spawn: PathTracer::load_obj's meshes with their transforms baked in), each a contiguous range of
@@ -518,6 +535,8 @@ int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected
  * A finite pose can still overflow the positions. That is caught where fr_update_geometry catches an array that
  * is not finite: the synchronous call returns FR_E_INVALID, the enqueued one is rejected on the device and
  * counted by fr_geometry_update_status; both leave the scene untouched.
+ * With fr_set_geometry_overlap on, the enqueued form poses, refits and writes the normals beside the previous
+ * frame's path trace.
  * Not covered: per-model visibility or materials, instancing, a two-level tree, changed triangle counts, groups
  * in stream order. */
 #define FR_MAX_MODELS 16

@@ -186,6 +186,11 @@ class PathTracer {
   void geometry_consumed(void* stream = nullptr) {  // stream: a hipStream_t (nullptr: the null stream); no host wait
     check(fr_geometry_consumed(ctx(), stream), ctx_, "geometry_consumed");
   }
+  // enqueued updates (and enqueued poses) refit into a second tree and second normals beside the previous frame's
+  // path trace (fr_set_geometry_overlap; off by default, 64 B per triangle at the first on; waits for pending work)
+  void set_geometry_overlap(bool on) {
+    check(fr_set_geometry_overlap(ctx(), on ? 1 : 0), ctx_, "set_geometry_overlap");
+  }
   // enqueued updates applied / rejected on the device since the context was created (waits for pending work)
   void geometry_update_status(uint64_t* applied, uint64_t* rejected) {
     check(fr_geometry_update_status(ctx(), applied, rejected), ctx_, "geometry_update_status");
