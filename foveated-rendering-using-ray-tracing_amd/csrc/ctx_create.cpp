@@ -176,7 +176,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     c->err = "scene: " + err;
     return bail(FR_E_IO);
   }
-  if (cfg.bvh_builder < 0 || cfg.bvh_builder > 1) { c->err = "bad bvh_builder"; return bail(FR_E_INVALID); }
+  if (cfg.bvh_builder < 0 || cfg.bvh_builder > 2) { c->err = "bad bvh_builder"; return bail(FR_E_INVALID); }
   if (cfg.bvh_builder == 0) {
     build_bvh(c->scene, c->bvh);
     if (c->bvh.max_stack > FR_BVH_STACK) {
@@ -236,6 +236,12 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     c->tree_full_cap = c->bvh.nodes.size() <= cap;
     std::string werr;
     if (nt >= 3 && !bvh_work_prepare(&c->bvh_work, nt, c->stream, werr)) { c->err = werr; return bail(FR_E_NOMEM); }
+    // the device SAH builder's scratch, on its contexts alone (the others' footprint does not move); the build
+    // below is also that module's first launch
+    if (cfg.bvh_builder == 2 && nt >= 3 && !sah_work_create(&c->sah_work, nt, c->stream, werr)) {
+      c->err = werr;
+      return bail(FR_E_NOMEM);
+    }
   }
   if (cfg.bvh_builder == 0) {
     if (hipMemcpy(c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice) != hipSuccess ||
@@ -393,6 +399,7 @@ int fr_destroy(fr_ctx* c) {
   fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back);
   fr(c->pose_rest_pos); fr(c->pose_rest_nrm); fr(c->pose_stage_pos); fr(c->pose_stage_nrm);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
+  if (c->sah_work) sah_work_free(c->sah_work);
   if (c->nrm_work) normals_work_free(c->nrm_work);
   for (auto p : c->d_tex) fr(p);
   fr(c->d_mats); fr(c->d_texs);

@@ -27,10 +27,14 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   }
   int nn = 0, max_stack = 0, depth = 0;
   std::string err;
-  if (!gpu_build_bvh(&c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri, c->spare_prim, &nn, &max_stack, &depth,
-                     c->stream, err)) {
+  // the context's builder: the LBVH, or on a bvh_builder 2 context the binned SAH of k_bvh_sah.hip
+  bool unsupported = false;
+  if (c->cfg.bvh_builder == 2 ? !gpu_build_bvh_sah(c->sah_work, c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri,
+                                                   c->spare_prim, &nn, &max_stack, &depth, &unsupported, c->stream, err)
+                              : !gpu_build_bvh(&c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri, c->spare_prim, &nn,
+                                               &max_stack, &depth, c->stream, err)) {
     c->err = err;
-    return FR_E_HIP;
+    return unsupported ? FR_E_UNSUPPORTED : FR_E_HIP;
   }
   if (max_stack > FR_BVH_STACK) {
     c->err = "GPU BVH needs a traversal stack deeper than FR_BVH_STACK";
@@ -765,6 +769,30 @@ int fr__scene_bvh(fr_scene* sc, const void** nodes, int* num_nodes, const void**
   *prim = sc->bvh.tri_prim.data();
   *num_leaf_tris = (int)sc->bvh.tri_prim.size();
   return FR_OK;
+}
+
+// Test hook (not part of include/fovrt.h): replaces the positions of an fr_scene (xyz: ntris x 9 floats, finite;
+// ntris the scene's) and its box, and builds its tree over them with the host builder, as fr_scene_create did over
+// the preset's. The host builder's tree for any geometry, without a device: the reference of the device SAH
+// builder. Returns a negative status, or the number of splits that took the median fallback although the node's
+// centroids differ on the split axis (the one case in which the device builder fails instead; 0 on geometry of
+// ordinary size). Pointers fr__scene_bvh and fr_scene_get_arrays gave before the call are stale after it.
+int fr__scene_rebuild_over(fr_scene* sc, const float* xyz, size_t ntris) {
+  if (!sc || !xyz || ntris != (size_t)sc->scene.num_tris()) return FR_E_INVALID;
+  for (size_t i = 0; i < ntris * 9; i++)
+    if (!std::isfinite(xyz[i])) return FR_E_INVALID;
+  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
+  for (size_t v = 0; v < ntris * 3; v++) {
+    const f3 p = mk3(xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2]);
+    sc->scene.pos[v] = p;
+    lo = mk3(fminf(lo.x, p.x), fminf(lo.y, p.y), fminf(lo.z, p.z));
+    hi = mk3(fmaxf(hi.x, p.x), fmaxf(hi.y, p.y), fmaxf(hi.z, p.z));
+  }
+  sc->scene.bbox_min = lo;
+  sc->scene.bbox_max = hi;
+  int medians = 0;
+  build_bvh(sc->scene, sc->bvh, &medians);
+  return medians;
 }
 
 int fr_scene_destroy(fr_scene* sc) {

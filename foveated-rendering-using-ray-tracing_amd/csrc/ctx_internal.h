@@ -211,6 +211,7 @@ struct fr_ctx {
   Fence update_done;
   int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
+  fr::SahWork* sah_work = nullptr;  // the device SAH builder's scratch (k_bvh_sah.hip): bvh_builder 2 contexts only
   // the smooth-vertex weld of the scene as fr_create built it (host), and on the device with the scratch of
   // a normal recompute (k_normals.hip); fixed for the life of the context
   fr::NormalGroups groups;

@@ -204,10 +204,24 @@ struct BinTree {
   FR_DEV f4 hi(int e) const { return e >= n - 1 ? bhi[ids[e - (n - 1)]] : nhi[e]; }
 };
 
+// The same questions of a MarkedTree (k_launch.h; the device SAH builder's): a leaf is marked, not recognised by
+// its size, and holds any number of triangles.
+struct MarkedBinTree {
+  const int2* child;
+  const int2* range;
+  const f4 *nlo, *nhi;
+  FR_DEV bool is_leaf(int e) const { return child[e].x < 0; }
+  FR_DEV int first(int e) const { return range[e].x; }
+  FR_DEV int size(int e) const { return range[e].y - range[e].x; }
+  FR_DEV f4 lo(int e) const { return nlo[e]; }
+  FR_DEV f4 hi(int e) const { return nhi[e]; }
+};
+
 // One level of the collapse: every item becomes a four-wide node; its inner children are allocated
 // contiguously and become the next level's items. Leaf entries keep their sorted-order range for
-// now (k_emit_leaves relays them out).
-__global__ void k_collapse(BinTree T, const CollapseItem* __restrict__ cur, const uint32_t* __restrict__ ncur,
+// now (k_emit_leaves relays them out). Tree: BinTree (the LBVH) or MarkedBinTree.
+template <class Tree>
+__global__ void k_collapse(Tree T, const CollapseItem* __restrict__ cur, const uint32_t* __restrict__ ncur,
                            CollapseItem* __restrict__ next, uint32_t* __restrict__ nnext, uint32_t* __restrict__ node_ctr,
                            BvhNode* __restrict__ nodes, uint32_t* __restrict__ max_stack, uint32_t* __restrict__ levels) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -662,6 +676,11 @@ __global__ void k_build_init(uint32_t* __restrict__ cb, CollapseItem* __restrict
   if (t == 0) qa[0] = CollapseItem{0, 0, 0};
 }
 
+template <class Tree, class Phase>
+static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes, TriGeo* tri,
+                              int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err,
+                              Phase&& phase);
+
 // Builds the four-wide BVH of n triangles (pos: 3 vertices per triangle, device) into the caller's
 // nodes / tri / prim (device, n entries each) with the workspace *work (created or grown here, kept
 // by the caller). Returns false with err set on failure. num_nodes, max_stack and depth (levels of
@@ -714,6 +733,39 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
                      w.arrivals);
   phase("karras");
   BinTree T{n, w.child, w.range, w.nlo, w.nhi, w.blo, w.bhi, w.ids_s};
+  return collapse_and_emit(w, T, w.ids_s, pos, n, nodes, tri, prim, num_nodes, max_stack, depth, s, err, phase);
+}
+
+BvhWorkView bvh_work_view(BvhWork* w) { return BvhWorkView{w->blo, w->bhi, w->cb}; }
+
+bool gpu_prim_boxes_enqueue(BvhWork* work, const f3* pos, int n, hipStream_t s, std::string& err) {
+  if (!work || n < 1 || n > work->cap) { err = "GPU BVH builder: no workspace for these triangles"; return false; }
+  BvhWork& w = *work;
+  hipLaunchKernelGGL(k_build_init, dim3(1), dim3(64), 0, s, w.cb, w.qa, w.ctr);
+  const int B = 256, G = (n + B - 1) / B;
+  hipLaunchKernelGGL(k_prim_boxes, dim3(std::min(G, 2048)), dim3(B), 0, s, pos, n, w.blo, w.bhi, w.cb);
+  if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
+  return true;
+}
+
+bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes,
+                         TriGeo* tri, int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s,
+                         std::string& err) {
+  if (!work || n < 3 || n > work->cap) { err = "GPU BVH builder: no workspace for these triangles"; return false; }
+  // (qa[0], ctr: k_build_init ran in gpu_prim_boxes_enqueue, and nothing since has touched them)
+  return collapse_and_emit(*work, MarkedBinTree{T.child, T.range, T.lo, T.hi}, ids, pos, n, nodes, tri, prim, num_nodes,
+                           max_stack, depth, s, err, [](const char*) {});
+}
+
+// The four-wide part of a build: the collapse of the binary tree T, whose leaves own ranges of ids, then the leaf
+// scan and the triangle relayout. The collapse runs its levels in batches of launches that skip themselves once
+// the level queue is empty, with one host read per batch.
+template <class Tree, class Phase>
+static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes, TriGeo* tri,
+                              int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err,
+                              Phase&& phase) {
+  const int B = 256, G = (n + B - 1) / B;
+  size_t tb = w.tmp_bytes;
   // (qa[0] = the root item and ctr = {1, 0, 1, 0, 0}: k_build_init)
   const int kBatch = 8;
   int launched = 0;
@@ -722,7 +774,7 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
     for (int b = 0; b < kBatch; b++) {
       hipMemsetAsync(w.ctr + 3, 0, sizeof(uint32_t), s);
       // a level holds at most n items (one per inner node of the binary tree)
-      hipLaunchKernelGGL(k_collapse, dim3(G), dim3(B), 0, s, T, qa, w.ctr + 2, qb, w.ctr + 3, w.ctr, nodes, w.ctr + 1,
+      hipLaunchKernelGGL(k_collapse<Tree>, dim3(G), dim3(B), 0, s, T, qa, w.ctr + 2, qb, w.ctr + 3, w.ctr, nodes, w.ctr + 1,
                          w.ctr + 4);
       hipMemcpyAsync(w.ctr + 2, w.ctr + 3, sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
       std::swap(qa, qb);
@@ -742,7 +794,7 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
   tb = w.tmp_bytes;
   hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, nn, s);
   phase("scan");
-  hipLaunchKernelGGL(k_emit_leaves, dim3(GN), dim3(B), 0, s, nodes, nn, w.off, w.ids_s, pos, tri, prim);
+  hipLaunchKernelGGL(k_emit_leaves, dim3(GN), dim3(B), 0, s, nodes, nn, w.off, ids, pos, tri, prim);
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH builder: kernel failure";
     return false;

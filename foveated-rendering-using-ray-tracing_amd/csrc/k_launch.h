@@ -118,6 +118,37 @@ bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cos
 bool gpu_check_positions(BvhWork* work, const float* xyz, int n, bool* finite, float box[6], hipStream_t s,
                          std::string& err);
 
+// What another builder (k_bvh_sah.hip) shares with this one: the workspace's primitive boxes (blo / bhi, one per
+// triangle), the centroid bounds k_prim_boxes leaves in cb[0..5] (order-mapped min / max), and the four-wide part.
+struct BvhWorkView {
+  const f4 *blo, *bhi;
+  const uint32_t* cb;
+};
+BvhWorkView bvh_work_view(BvhWork* w);
+// k_build_init and k_prim_boxes over pos (no wait)
+bool gpu_prim_boxes_enqueue(BvhWork* work, const f3* pos, int n, hipStream_t s, std::string& err);
+// A binary tree whose leaves are marked (child[e].x < 0) and own ids[range[e].x, range[e].y): any number of
+// triangles, at any depth. lo / hi: the raw box of every node.
+struct MarkedTree {
+  const int2* child;
+  const int2* range;
+  const f4 *lo, *hi;
+};
+// The four-wide part of gpu_build_bvh over such a tree (root: node 0, not a leaf): collapse, leaf scan, triangle
+// relayout, with the same kernels. Waits for the result.
+bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes,
+                         TriGeo* tri, int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s,
+                         std::string& err);
+
+// k_bvh_sah.hip: the device binned-SAH builder (fr_config.bvh_builder = 2), whose tree is the host builder's
+struct SahWork;
+bool sah_work_create(SahWork** out, int n, hipStream_t s, std::string& err);
+void sah_work_free(SahWork* w);
+size_t sah_work_bytes(int n);
+// gpu_build_bvh's contract. *unsupported: the build met a node without a finite SAH candidate (see fovrt.h)
+bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim,
+                       int* num_nodes, int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err);
+
 // k_normals.hip: shading normals over moving geometry
 struct NormalsWork;
 bool normals_work_create(NormalsWork** out, const int32_t* corner_vertex, const int32_t* off, const int32_t* corners,

@@ -656,6 +656,7 @@ struct Builder {
   Bvh& out;
   static constexpr int kMaxBins = 64, kMaxDepth = 30;
   int kLeaf = 2, kBins = 16;  // leaf size and SAH bins (FOVRT_BVH_LEAF / FOVRT_BVH_BINS override, for tuning)
+  int median_with_extent = 0;  // splits that fell back to the median although the centroids differ (ex > 0)
   int kSplit = 0;             // FOVRT_BVH_SPLIT: 0 binned on the widest centroid axis; 1 binned on all three
                               // axes; 2 exact sweep over the sorted centroids of all three axes
   Builder(const HostScene& sc, Bvh& o) : s(sc), out(o) {
@@ -769,6 +770,7 @@ struct Builder {
       }
     }
     if (mid <= b || mid >= e) {  // degenerate: median split on the axis
+      if (ex > 0.0f) median_with_extent++;
       mid = b + n / 2;
       std::nth_element(ids.begin() + b, ids.begin() + mid, ids.begin() + e,
                        [&](int x, int y) { return key(x) < key(y) || (key(x) == key(y) && x < y); });
@@ -899,9 +901,10 @@ struct Builder {
 };
 }  // namespace
 
-void build_bvh(const HostScene& s, Bvh& out) {
+void build_bvh(const HostScene& s, Bvh& out, int* median_with_extent) {
   Builder b(s, out);
   b.run();
+  if (median_with_extent) *median_with_extent = b.median_with_extent;
 }
 
 void build_normal_groups(const HostScene& s, NormalGroups& out) {

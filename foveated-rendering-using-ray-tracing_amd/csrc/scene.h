@@ -71,7 +71,9 @@ bool load_png(const std::string& path, HostTexture& tex, std::string& err);
 
 // Binned-SAH binary BVH over the soup collapsed into four-wide nodes; conservative (inflated)
 // child boxes.
-void build_bvh(const HostScene& s, Bvh& out);
+// (median_with_extent, may be NULL: how many splits took the median fallback over centroids that differ on the split
+// axis, the one case in which the device SAH builder, k_bvh_sah.hip, fails instead of following)
+void build_bvh(const HostScene& s, Bvh& out, int* median_with_extent = nullptr);
 
 // Camera presets (FR/main.cpp:189-209): eye and look-at target.
 void preset_camera(int preset, f3& eye, f3& target);

@@ -359,7 +359,7 @@ class Config:
     texture_mode: int = 0
     detail: int = 0
     mesh_mode: int = 0  # 0: .obj meshes where present, else procedural; 1: procedural; 2: .obj required
-    bvh_builder: int = 0  # 0: host binned SAH; 1: GPU LBVH (k_bvh.hip)
+    bvh_builder: int = 0  # 0: host binned SAH; 1: GPU LBVH (k_bvh.hip); 2: GPU binned SAH, the host's tree (k_bvh_sah.hip)
     sibson_mode: int = 0  # 0: run form (prefix sums, ~1e-6 of the per-tap sum); 1: per tap, bit-exact
     asset_dir: str = DEFAULT_ASSET_DIR
 

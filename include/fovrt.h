@@ -70,8 +70,41 @@ typedef struct fr_config {
   int detail;                 /* procedural mesh detail (0 = preset default) */
   int mesh_mode;              /* 0: the reference's .obj meshes where present under asset_dir, procedural
                                * stand-ins otherwise; 1: procedural only; 2: .obj required (FR_E_IO) */
-  int bvh_builder;            /* 0: host binned SAH (default); 1: GPU LBVH (k_bvh.hip), the builder of
-                               * fr_rebuild_bvh / fr_set_positions; both give identical frames */
+  int bvh_builder;            /* 0: host binned SAH (default); 1: GPU LBVH (k_bvh.hip); 2: GPU binned SAH
+                               * (k_bvh_sah.hip). The context's builder makes fr_create's tree and every later
+                               * one (fr_rebuild_bvh, fr_set_positions, FR_BVH_REBUILD of fr_update_positions /
+                               * fr_update_geometry / fr_set_model_transforms); a builder-0 context rebuilds with
+                               * the LBVH. All three give identical frames.
+                               *
+                               * The tree of builder 2 is the tree of builder 0: one right answer, the rule
+                               *   inputs    a triangle's box is the min / max of its vertices, its centroid
+                               *             (lo + hi) * 0.5f;
+                               *   leaves    a node of <= 2 triangles, or at depth >= 30 (the root: depth 0);
+                               *   axis      over the node's centroid box, ext = hi - lo:
+                               *             ext.x > ext.y ? (ext.x > ext.z ? 0 : 2) : (ext.y > ext.z ? 1 : 2);
+                               *   bins      with ex = ext[axis] > 0, bin = (int)((key - lo) / ex * 16) clamped
+                               *             to [0, 15]; a bin keeps its triangle count and the union of boxes;
+                               *   split     for k = 1..15, l = union of bins < k, r = of bins >= k, skipped
+                               *             when a side is empty; cost = l.area() * nl + r.area() * nr in fp32,
+                               *             every operation rounded on its own (no fused multiply-add),
+                               *             area = 2 * (dx*dy + dy*dz + dz*dx), 0 when dx < 0; the first k of
+                               *             strictly smaller cost wins; left: the triangles of bins < k;
+                               *   ex == 0   (all centroids equal) left: the n / 2 lowest primitive indices;
+                               *   boxes     a child's box is the union of its triangles' boxes;
+                               *   4-wide    the collapse, stack need, slot inflation and leaf layout of every
+                               *             builder here.
+                               * Equal: the hierarchy, every stored slot box bit for bit, every leaf's triangle
+                               * set, the node count, bvh_depth, bvh_max_stack. Free: the index a node takes among
+                               * the nodes of its level, and the order of the triangles inside one leaf. (Mins
+                               * and maxes of +0 and -0 depend on the order; nothing stored does.)
+                               * Not the host's: a node with ex > 0 none of whose candidates has a finite cost
+                               * (coordinates around 1e19 and beyond) gets the median by (key, index) on the
+                               * host; the device build fails with FR_E_UNSUPPORTED and leaves positions, tree
+                               * and scene box as they were. The host's FOVRT_BVH_LEAF / _BINS / _SPLIT tuning
+                               * variables do not reach the device: equality is with the host at its defaults.
+                               * Scenes of fewer than 3 triangles behave as with builder 1. Scratch: 143 bytes
+                               * per triangle, made by fr_create on builder-2 contexts only; a rebuild
+                               * allocates nothing. */
   int sibson_mode;            /* 0 (default): run form, each row of a pixel's disc summed from per-row prefix
                                * sums (same taps as sibsonFS.glsl:30-44, rounding-level differences, ~1e-6);
                                * 1: per tap in the shader's order (bit-exact against the oracle) */

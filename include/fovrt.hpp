@@ -154,7 +154,7 @@ class PathTracer {
     check(fr_gaze_target(ctx(), g.data()), ctx_, "gaze_target");
     return g;
   }
-  float rebuild_bvh() {  // GPU LBVH over the current triangles (fr_rebuild_bvh), wall ms
+  float rebuild_bvh() {  // the context's GPU builder (LBVH; binned SAH with bvh_builder 2) over the current triangles, wall ms
     float ms = 0.0f;
     check(fr_rebuild_bvh(ctx(), &ms), ctx_, "rebuild_bvh");
     return ms;
