@@ -173,6 +173,7 @@ int fr_snapshot(fr_ctx* c, void* host, size_t bytes) {
   if (!c) return FR_E_INVALID;
   const size_t need = snap_total(c);
   if (!host || bytes < need) return fail(c, FR_E_INVALID, "snapshot: buffer smaller than fr_snapshot_bytes");
+  if (int rc = tree_numbers(c)) return rc;  // (behind an enqueued rebuild: the host's copy of the tree's numbers)
   join_recon(c);
   hipSetDevice(c->cfg.device);
   SnapHeader h{};

@@ -209,6 +209,11 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
+  // the record of enqueued rebuilds (fr_rebuild_bvh_enqueue allocates nothing either)
+  if (dalloc(&c->rb, 1) != hipSuccess || hipHostMalloc((void**)&c->h_rb, sizeof(fr::RebuildState)) != hipSuccess) {
+    c->err = "device allocation (scene) failed";
+    return bail(FR_E_NOMEM);
+  }
   {  // the weld and the recompute's scratch exist from the start: an update of the normals allocates nothing
     build_normal_groups(s, c->groups);
     std::string werr;
@@ -409,6 +414,8 @@ int fr_destroy(fr_ctx* c) {
   if (c->h_counts) hipHostFree(c->h_counts);
   fr(c->geo);
   if (c->h_geo) hipHostFree(c->h_geo);
+  fr(c->rb);
+  if (c->h_rb) hipHostFree(c->h_rb);
   if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
   for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);
   if (c->update_done.ev) hipEventDestroy(c->update_done.ev);

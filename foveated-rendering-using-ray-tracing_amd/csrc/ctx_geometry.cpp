@@ -61,6 +61,26 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   b.gpu_nodes = nn;
   b.host_nodes = 0;
   c->bvh = std::move(b);
+  c->tree_on_device = false;  // (the host has just seen this tree's numbers)
+  return FR_OK;
+}
+
+// The numbers of the tree an enqueued rebuild left, from the pinned copy of the record (the caller has waited).
+static void take_tree_numbers(fr_ctx* c) {
+  const fr::TreeDesc& d = c->h_rb->tree[c->desc_cur];
+  c->bvh.gpu_nodes = (int)d.nodes;
+  c->bvh.max_stack = (int)d.max_stack;
+  c->bvh.max_depth = (int)d.depth;
+  c->tree_on_device = false;
+}
+
+int fri::tree_numbers(fr_ctx* c) {
+  if (!c->tree_on_device) return FR_OK;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(c->h_rb, c->rb, sizeof(fr::RebuildState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  take_tree_numbers(c);
   return FR_OK;
 }
 
@@ -71,6 +91,7 @@ static int tree_nodes(const Bvh& b) {
 // Refit of the tree in use (either builder's) over `pos` (device), in place (k_bvh.hip). The caller has joined
 // and synchronised the context stream.
 static int gpu_refit(fr_ctx* c, const f3* pos) {
+  if (int rc = tree_numbers(c)) return rc;
   std::string err;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
   if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->d_nodes, nn, c->d_tri, c->d_prim, c->stream, err)) {
@@ -99,6 +120,7 @@ int fr_refit_bvh(fr_ctx* c, float* ms) { return host_timed(c, ms, [&] { return g
 int fr_bvh_sah_cost(fr_ctx* c, float* cost) {
   if (!c || !cost) return FR_E_INVALID;
   if (c->bvh.root_count > 0) { *cost = (float)c->bvh.root_count; return FR_OK; }  // one leaf: its triangles
+  if (int rc = tree_numbers(c)) return rc;
   join_recon(c);
   hipSetDevice(c->cfg.device);
   std::string err;
@@ -293,6 +315,23 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 //    and leaf index is written);
 //  - a failed frame's front stages without their entry 3 are earlier work of front_stream.
 // (pose: fr_set_model_transforms_enqueue, whose k_pose produces xyz and nrm, the staging arrays, on the same stream)
+// An enqueued rebuild (fr_rebuild_bvh_enqueue, enqueue_rebuild below) runs on the same stream under the same rules,
+// and in both modes builds out of place, into the spare tree arrays, which the host makes the scene's at enqueue time:
+//  - in place (context stream): the spare arrays' last readers are frames enqueued before the rebuild that retired
+//    them; their entry 3 is earlier work of the context stream and waited for their front stages (front_done, consumed
+//    here as above), and later front stages wait for the context stream (stream_dirty). Shading records and set_cur
+//    stay: only the tree's pointers change, as in fr_rebuild_bvh;
+//  - overlapped (front_stream): the set written is the one the fences above guard (set_read of the other set,
+//    ev_stream_join), its shading records are brought along by gpu_normals_to_enqueue's copy, and tree and records
+//    swap together with set_cur, so an update that follows finds the parity it assumes;
+//  - the builders' scratch (bvh_work: boxes, codes, binary tree, queues, counters, the scan's; sah_work) and rb
+//    (verdict, level counters, the trees' numbers) are shared with the checks, the refit, the cost and the
+//    synchronous builders: all of it runs on the update's stream, and synchronous users wait through update_done
+//    (join_recon) before they touch it;
+//  - the tree's numbers: a refit enqueued behind the rebuild reads the node count from rb->tree[desc_cur] in stream
+//    order (nodes_dev); a host reader waits and fetches them (tree_numbers); a frame needs none of them;
+//  - a build that fails on the device reads the tree in use (the source of its last kernel's copy), which the
+//    previous update or rebuild wrote earlier on this stream.
 static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, const void* nrm, size_t ntris, int normals,
                           void* ready_event, const fr::PoseArgs* pose = nullptr) {
   if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
@@ -343,9 +382,12 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
   if (!given) HIP_TRY(c, c->geo_read.record(s));  // xyz has been read
   const uint32_t* reject = &c->geo->reject;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  // (behind an enqueued rebuild the host's count is stale: the refit takes the tree's from its device record)
+  const uint32_t* nn_dev = c->tree_on_device ? &c->rb->tree[c->desc_cur].nodes : nullptr;
   if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim,
-                                          c->spare_nodes, c->spare_tri, c->spare_prim, reject, s, err)
-              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, s, err))
+                                          c->spare_nodes, c->spare_tri, c->spare_prim, reject, nn_dev, s, err)
+              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, nn_dev,
+                                       s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   rotate_positions(c);
   c->pos_mirror_stale = true;
@@ -406,6 +448,101 @@ int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) 
   c->geo_rejected_seen[0] = g.rejected;
   c->geo_rejected_seen[1] = g.rejected_pos;
   c->geo_rejected_seen[2] = g.rejected_nrm;
+  return FR_OK;
+}
+
+// fr_rebuild_bvh in stream order: the context's builder on its fixed launch schedule (gpu_build_bvh_enqueue,
+// gpu_build_bvh_sah_enqueue), on the stream enqueue_update would use and behind the same fences; see the notes above
+// it. The build goes into the spare tree arrays, which become the scene's here, whatever the verdict (a failed build
+// ends with the tree in use copied over them, whole). Nothing waits, nothing is copied to the host, nothing is
+// allocated: the new tree's numbers are the device record's until a host reader asks (tree_numbers).
+static int enqueue_rebuild(fr_ctx* c, const std::string& name) {
+  if (c->group_refs > 0 || c->U.shard_count > 1)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_rebuild_bvh)");
+  const int nt = c->scene.num_tris();
+  if (nt < 3) return fail(c, FR_E_HIP, name + ": GPU BVH builder needs at least 3 triangles");
+  const bool sah = c->cfg.bvh_builder == 2;
+  if (!c->tree_full_cap || !c->spare_nodes || (!c->tree_on_device && c->bvh.gpu_nodes < 0) || !c->bvh_work || !c->rb ||
+      !c->geo || (sah && !c->sah_work) || (c->overlap_on && !c->shade_back))
+    return fail(c, FR_E_STATE, name + ": the tree in use is not yet a device-built one with a spare set beside it "
+                                      "(call fr_rebuild_bvh once first; this call allocates nothing)");
+  hipSetDevice(c->cfg.device);
+  const bool overlap = c->overlap_on;
+  const hipStream_t s = overlap ? c->front_stream : c->stream;
+  struct Done {
+    fr_ctx* c;
+    bool on;
+    ~Done() { if (on) c->update_done.record(c->front_stream); }
+  } done{c, overlap};
+  if (overlap) {
+    if (c->stream_dirty) {
+      hipEventRecord(c->ev_stream_join, c->stream);
+      hipStreamWaitEvent(s, c->ev_stream_join, 0);
+      c->stream_dirty = false;
+    }
+    c->set_read[c->set_cur ^ 1].consume(s);
+  } else {
+    c->stream_dirty = true;
+    c->front_done.consume(c->stream);
+  }
+  fr::RebuildTarget t{};
+  t.rs = c->rb;
+  t.nodes = c->spare_nodes; t.tri = c->spare_tri; t.prim = c->spare_prim;
+  t.desc = &c->rb->tree[c->desc_cur ^ 1];
+  t.src_nodes = c->d_nodes; t.src_tri = c->d_tri; t.src_prim = c->d_prim;
+  t.src_host_nodes = c->tree_on_device ? -1 : tree_nodes(c->bvh);
+  t.src_host_desc = fr::TreeDesc{(uint32_t)std::max(t.src_host_nodes, 0), (uint32_t)c->bvh.max_stack,
+                                 (uint32_t)c->bvh.max_depth, 0u};
+  t.src_desc = &c->rb->tree[c->desc_cur];
+  std::string err;
+  if (sah ? !gpu_build_bvh_sah_enqueue(c->sah_work, c->bvh_work, c->d_pos, nt, t, s, err)
+          : !gpu_build_bvh_enqueue(c->bvh_work, c->d_pos, nt, t, s, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  // (overlapped: the other set's shading records are an update old; the tree's verdict does not touch them)
+  if (overlap && !gpu_normals_to_enqueue(c->nrm_work, nullptr, nullptr, c->d_shade, c->shade_back, &c->geo->reject, s, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
+  std::swap(c->d_nodes, c->spare_nodes);
+  std::swap(c->d_tri, c->spare_tri);
+  std::swap(c->d_prim, c->spare_prim);
+  c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim;
+  if (overlap) {
+    std::swap(c->d_shade, c->shade_back);
+    c->dsc.shade = c->d_shade;
+    c->set_cur ^= 1;
+  }
+  c->desc_cur ^= 1;
+  c->bvh.root_count = 0;
+  c->tree_on_device = true;
+  return FR_OK;
+}
+
+int fr_rebuild_bvh_enqueue(fr_ctx* c) {
+  if (!c) return FR_E_INVALID;
+  return enqueue_rebuild(c, "fr_rebuild_bvh_enqueue");
+}
+
+int fr_bvh_rebuild_status(fr_ctx* c, uint64_t* built, uint64_t* failed) {
+  if (!c) return FR_E_INVALID;
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(c->h_rb, c->rb, sizeof(fr::RebuildState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->tree_on_device) take_tree_numbers(c);
+  const fr::RebuildState& r = *c->h_rb;
+  if (built) *built = r.built;
+  if (failed) *failed = r.failed;
+  if (r.failed > c->rb_failed_seen[0]) {
+    std::string why;
+    auto add = [&](bool on, const char* text) { if (on) why += (why.empty() ? "" : "; ") + std::string(text); };
+    add(r.failed_sah > c->rb_failed_seen[1], "GPU SAH builder: a node has no finite SAH candidate (coordinates too large)");
+    add(r.failed_stack > c->rb_failed_seen[2], "GPU BVH needs a traversal stack deeper than FR_BVH_STACK");
+    add(r.failed_collapse > c->rb_failed_seen[3], "GPU BVH builder: collapse did not terminate");
+    c->err = "fr_rebuild_bvh_enqueue: " + why + " (build failed on the device, the scene keeps its tree)";
+  }
+  c->rb_failed_seen[0] = r.failed;
+  c->rb_failed_seen[1] = r.failed_sah;
+  c->rb_failed_seen[2] = r.failed_stack;
+  c->rb_failed_seen[3] = r.failed_collapse;
   return FR_OK;
 }
 
@@ -535,6 +672,7 @@ int fr_set_motion_reprojection(fr_ctx* c, int on) {
 // any device-built tree; a host-built tree of more nodes than that gets bigger ones, once) and a second TriShade
 // array, copied from d_shade. On a quiet context. Either everything is made or nothing is kept.
 static int make_second_set(fr_ctx* c, const std::string& name) {
+  if (int rc = tree_numbers(c)) return rc;
   const size_t nt = (size_t)c->scene.num_tris(), cap = std::max<size_t>(nt, 1), nn = (size_t)tree_nodes(c->bvh);
   const bool first = !c->shade_back;
   const bool tree = !c->spare_nodes || (first && nn > cap);
@@ -621,6 +759,7 @@ int fr_normal_groups(fr_ctx* c, int32_t* corner_vertex, size_t ncorners, int* nv
 int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size_t tri_bytes, int32_t* prim,
                  size_t prim_bytes) {
   if (!c || !nodes || !tri_geo || !prim) return FR_E_INVALID;
+  if (int rc = tree_numbers(c)) return rc;
   const Bvh& b = c->bvh;
   const size_t nn = (size_t)tree_nodes(b);
   const size_t nt = (size_t)c->scene.num_tris();
@@ -681,6 +820,7 @@ extern "C" {
 
 int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
   if (!c || !o) return FR_E_INVALID;
+  if (int rc = tree_numbers(c)) return rc;
   if (c->geo_read.pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
     // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
     // (nor for front_stream, where an overlapped update runs: the context stream waits for that one first)

@@ -189,6 +189,18 @@ struct fr_ctx {
   Fence geo_read;
   bool box_mirror_stale = false;
   unsigned long long geo_rejected_seen[3] = {};
+  // Enqueued rebuilds (fr_rebuild_bvh_enqueue). rb: their record on the device (verdict, counters, the numbers of
+  // the two trees, the collapse's level counters), made by fr_create; h_rb: its pinned copy for fr_bvh_rebuild_status
+  // and tree_numbers. tree_on_device: the tree in use was built by an enqueued rebuild the host has not looked at
+  // since: its node count, stack need and depth are rb->tree[desc_cur], and bvh.gpu_nodes / max_stack / max_depth are
+  // behind (beside pos_mirror_stale / box_mirror_stale: tree_numbers refreshes them, after a wait, for every host
+  // reader; enqueued refits take the count from the device meanwhile). rb_failed_seen: the failed counts
+  // fr_bvh_rebuild_status last reported (total, SAH, stack, collapse).
+  fr::RebuildState* rb = nullptr;
+  fr::RebuildState* h_rb = nullptr;
+  bool tree_on_device = false;
+  int desc_cur = 0;
+  unsigned long long rb_failed_seen[4] = {};
   // Model poses (fr_model_pose_enable, fr_set_model_transforms). Four arrays of 9 floats per triangle, made by the
   // first enable: the rest geometry a pose is relative to (positions, and d_shade's normals expanded) and the
   // staging arrays k_pose writes and the update path then reads as a caller's device arrays. All four are read
@@ -357,6 +369,10 @@ int P_pos(const fr_ctx* c), P_shd(const fr_ctx* c), P_wgt(const fr_ctx* c);  // 
 int resolve(fr_ctx* c, int id, int* phys);  // buffer id -> physical image, with the lazy outputs it names written
 void kt_harvest(fr_ctx* c, int i), fc_harvest(fr_ctx* c, int i);  // one ring entry of fr_kernel_timing / fr_frame_clock
 int gpu_rebuild(fr_ctx* c, const f3* pos);  // ctx_geometry.cpp
+// The host's numbers of the tree in use (bvh.gpu_nodes / max_stack / max_depth) made current: while tree_on_device
+// they are fetched from the device, behind the context's pending work (a wait). Every host reader of them goes
+// through this first. (ctx_geometry.cpp)
+int tree_numbers(fr_ctx* c);
 }  // namespace fri
 
 #define HIP_TRY(ctx, expr)                                                                                      \

@@ -104,6 +104,24 @@ struct GeoUpdateState {
   float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
 };
 
+// Device-side record of enqueued rebuilds (fr_rebuild_bvh_enqueue), one per context. The numbers of a tree the host
+// has not seen live in tree[]: the build writes the record that is not the current tree's, which then becomes it.
+struct TreeDesc {
+  uint32_t nodes, max_stack, depth, pad;
+};
+#define FR_REBUILD_FAIL_SAH 1u       // a builder-2 node without a finite SAH candidate
+#define FR_REBUILD_FAIL_STACK 2u     // the tree needs a traversal stack deeper than FR_BVH_STACK
+#define FR_REBUILD_FAIL_COLLAPSE 4u  // the collapse's level queue was not empty after the launches provided
+#define FR_REBUILD_LEVELS 64         // collapse launches of the LBVH form (the SAH form: 30)
+struct RebuildState {
+  unsigned long long built, failed;                            // builds since fr_create, by verdict
+  unsigned long long failed_sah, failed_stack, failed_collapse;  // failed ones by cause (more than one may count)
+  TreeDesc tree[2];
+  uint32_t fail;        // verdict of the build in flight (FR_REBUILD_FAIL_* bits), written by k_rebuild_verdict
+  uint32_t emit_nodes;  // the nodes whose leaves are emitted: the built tree's, or 0 after a failed build
+  uint32_t level[FR_REBUILD_LEVELS + 1];  // items of each collapse level; the last: left over after the last launch
+};
+
 // A pose of the scene's models (fr_set_model_transforms), passed to k_pose by value: everything the kernel needs
 // travels in its kernel arguments (1.4 KB), so a pose costs no copy to the device and keeps nothing alive.
 #define FR_POSE_MAX_MODELS 16  // FR_MAX_MODELS of include/fovrt.h

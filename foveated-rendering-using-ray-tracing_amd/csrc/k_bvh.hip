@@ -21,6 +21,9 @@
 // the check of positions handed over in device memory (gpu_check_positions). Each has an enqueue half that
 // launches and returns; an update enqueued in stream order (fr_update_geometry_enqueue) uses those alone, with
 // the refit's gated kernels and the take-over of the positions by verdict (gpu_take_over_positions).
+// The build has an enqueue form as well (fr_rebuild_bvh_enqueue: gpu_build_bvh_enqueue, gpu_collapse_marked_enqueue): a
+// fixed launch schedule whose verdict and numbers stay in device memory (RebuildState), and the refit has forms
+// that take the node count of such a tree from there.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -220,10 +223,14 @@ struct MarkedBinTree {
 // One level of the collapse: every item becomes a four-wide node; its inner children are allocated
 // contiguously and become the next level's items. Leaf entries keep their sorted-order range for
 // now (k_emit_leaves relays them out). Tree: BinTree (the LBVH) or MarkedBinTree.
-template <class Tree>
+// GATED: the form of an enqueued build, whose binary tree may have failed on the device (*stop != 0: its root may
+// then be a leaf, which the collapse does not handle) and writes nothing then. The plain instances never read it.
+template <class Tree, bool GATED = false>
 __global__ void k_collapse(Tree T, const CollapseItem* __restrict__ cur, const uint32_t* __restrict__ ncur,
                            CollapseItem* __restrict__ next, uint32_t* __restrict__ nnext, uint32_t* __restrict__ node_ctr,
-                           BvhNode* __restrict__ nodes, uint32_t* __restrict__ max_stack, uint32_t* __restrict__ levels) {
+                           BvhNode* __restrict__ nodes, uint32_t* __restrict__ max_stack, uint32_t* __restrict__ levels,
+                           const uint32_t* __restrict__ stop) {
+  if (GATED && *stop) return;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t nc = *ncur;
   if (i == 0 && nc) atomicAdd(levels, 1u);
@@ -283,9 +290,15 @@ __global__ void k_collapse(Tree T, const CollapseItem* __restrict__ cur, const u
   nodes[it.slot] = nd;
 }
 
-__global__ void k_leaf_counts(const BvhNode* __restrict__ nodes, int nn, uint32_t* __restrict__ cnt) {
+// DEVN (here and below): the form of an enqueued build or update, whose node count is in device memory (*nn_dev,
+// one uniform load); the grid then covers the capacity `nn` (one node per triangle). The plain instances never
+// read the pointer. k_leaf_counts<true> writes every entry of the capacity (0 past the tree: the scan runs over all).
+template <bool DEVN>
+__global__ void k_leaf_counts(const BvhNode* __restrict__ nodes, int nn, uint32_t* __restrict__ cnt,
+                              const uint32_t* __restrict__ nn_dev) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
+  if (DEVN && i >= (int)*nn_dev) { cnt[i] = 0u; return; }
   uint32_t s = 0;
   for (int k = 0; k < 4; k++) s += nodes[i].count[k] > 0 ? (uint32_t)nodes[i].count[k] : 0u;
   cnt[i] = s;
@@ -302,9 +315,11 @@ FR_DEV void store_tri_geo(const f3* __restrict__ pos, int p, TriGeo* __restrict_
 }
 
 // Leaf children of node i -> one contiguous range starting at off[i].
+template <bool DEVN>
 __global__ void k_emit_leaves(BvhNode* __restrict__ nodes, int nn, const uint32_t* __restrict__ off,
                               const int32_t* __restrict__ ids, const f3* __restrict__ pos, TriGeo* __restrict__ tri,
-                              int32_t* __restrict__ prim) {
+                              int32_t* __restrict__ prim, const uint32_t* __restrict__ nn_dev) {
+  if (DEVN) nn = min(nn, (int)*nn_dev);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   uint32_t o = off[i];
@@ -337,10 +352,12 @@ __global__ void k_refit_tris(const f3* __restrict__ pos, const int32_t* __restri
 }
 
 // Parent links (node, not slot) from the nodes themselves, and the arrival counters back to zero.
-template <bool GATED>
+template <bool GATED, bool DEVN = false>
 __global__ void k_refit_links(const BvhNode* __restrict__ nodes, int nn, int* __restrict__ parent,
-                              uint32_t* __restrict__ arrivals, const uint32_t* __restrict__ reject) {
+                              uint32_t* __restrict__ arrivals, const uint32_t* __restrict__ reject,
+                              const uint32_t* __restrict__ nn_dev) {
   if (GATED && *reject) return;
+  if (DEVN) nn = min(nn, (int)*nn_dev);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   arrivals[i] = 0u;
@@ -360,11 +377,12 @@ FR_DEV void store_agent(f4* p, f3 v) {
 // thread that finishes a node arrives at its parent, and the last of the parent's inner children to arrive
 // (which then sees every child's raw box) goes on with the parent. nlo / nhi hold the raw (uninflated) box of
 // each node; a slot stores inflate(raw). Nobody waits: a walk that is not the last arrival ends.
-template <bool GATED>
+template <bool GATED, bool DEVN = false>
 __global__ void k_refit_up(BvhNode* nodes, int nn, const f3* __restrict__ pos, const int32_t* __restrict__ prim,
                            const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi,
-                           const uint32_t* __restrict__ reject) {
+                           const uint32_t* __restrict__ reject, const uint32_t* __restrict__ nn_dev) {
   if (GATED && *reject) return;
+  if (DEVN) nn = min(nn, (int)*nn_dev);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   int node = i;
@@ -438,9 +456,11 @@ __global__ void k_refit_tris_to(const f3* __restrict__ pos, const int32_t* __res
 
 // k_refit_links over src. Rejected: the copy of the nodes instead, one 16-B word per lane, consecutive lanes
 // consecutive words (the grid's nn lanes take eight words each).
+template <bool DEVN>
 __global__ void k_refit_links_to(const BvhNode* __restrict__ src, int nn, int* __restrict__ parent,
                                  uint32_t* __restrict__ arrivals, BvhNode* __restrict__ dst,
-                                 const uint32_t* __restrict__ reject) {
+                                 const uint32_t* __restrict__ reject, const uint32_t* __restrict__ nn_dev) {
+  if (DEVN) nn = min(nn, (int)*nn_dev);
   if (*reject) {
     const f4* s4 = reinterpret_cast<const f4*>(src);
     f4* d4 = reinterpret_cast<f4*>(dst);
@@ -460,11 +480,13 @@ __global__ void k_refit_links_to(const BvhNode* __restrict__ src, int nn, int* _
 }
 
 // k_refit_up's walk over src's topology; the thread that finishes a node stores it whole into dst.
+template <bool DEVN>
 __global__ void k_refit_up_to(const BvhNode* __restrict__ src, BvhNode* __restrict__ dst, int nn,
                               const f3* __restrict__ pos, const int32_t* __restrict__ prim,
                               const int* __restrict__ parent, uint32_t* __restrict__ arrivals, f4* nlo, f4* nhi,
-                              const uint32_t* __restrict__ reject) {
+                              const uint32_t* __restrict__ reject, const uint32_t* __restrict__ nn_dev) {
   if (*reject) return;
+  if (DEVN) nn = min(nn, (int)*nn_dev);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
   int node = i;
@@ -775,7 +797,7 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
       hipMemsetAsync(w.ctr + 3, 0, sizeof(uint32_t), s);
       // a level holds at most n items (one per inner node of the binary tree)
       hipLaunchKernelGGL(k_collapse<Tree>, dim3(G), dim3(B), 0, s, T, qa, w.ctr + 2, qb, w.ctr + 3, w.ctr, nodes, w.ctr + 1,
-                         w.ctr + 4);
+                         w.ctr + 4, nullptr);
       hipMemcpyAsync(w.ctr + 2, w.ctr + 3, sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
       std::swap(qa, qb);
     }
@@ -790,11 +812,11 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
   *max_stack = (int)w.host[1];
   *depth = (int)w.host[4] - 1;
   const int nn = *num_nodes, GN = (nn + B - 1) / B;
-  hipLaunchKernelGGL(k_leaf_counts, dim3(GN), dim3(B), 0, s, nodes, nn, w.cnt);
+  hipLaunchKernelGGL(k_leaf_counts<false>, dim3(GN), dim3(B), 0, s, nodes, nn, w.cnt, nullptr);
   tb = w.tmp_bytes;
   hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, nn, s);
   phase("scan");
-  hipLaunchKernelGGL(k_emit_leaves, dim3(GN), dim3(B), 0, s, nodes, nn, w.off, ids, pos, tri, prim);
+  hipLaunchKernelGGL(k_emit_leaves<false>, dim3(GN), dim3(B), 0, s, nodes, nn, w.off, ids, pos, tri, prim, nullptr);
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH builder: kernel failure";
     return false;
@@ -803,29 +825,161 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The enqueue form of a build (fr_rebuild_bvh_enqueue): the same kernels on a fixed launch schedule, nothing read
+// back. What the host loop learnt from the counters stays on the device, in the context's RebuildState.
+// ---------------------------------------------------------------------------------------------
+// The level counters of the collapse: level L's launch reads level[L] and counts its inner children into
+// level[L + 1], so no counter is reset or copied between launches.
+__global__ void k_rebuild_begin(RebuildState* __restrict__ rs) {
+  for (int t = threadIdx.x; t <= FR_REBUILD_LEVELS; t += blockDim.x) rs->level[t] = t == 0 ? 1u : 0u;
+}
+
+// The verdict, one lane, after the last collapse launch. sah_fail: the SAH builder's failure word (NULL: the LBVH);
+// ctr: node_ctr, max_stack, -, -, levels (k_build_init, k_collapse); levels: the collapse launches made. The built
+// tree's numbers go to *out; rs->emit_nodes gates the leaf kernels.
+__global__ void k_rebuild_verdict(RebuildState* __restrict__ rs, const uint32_t* __restrict__ sah_fail,
+                                  const uint32_t* __restrict__ ctr, int levels, TreeDesc* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint32_t f = 0u;
+  if (sah_fail && *sah_fail) f |= FR_REBUILD_FAIL_SAH;
+  if (!f && ctr[1] > (uint32_t)FR_BVH_STACK) f |= FR_REBUILD_FAIL_STACK;
+  if (!f && rs->level[levels] != 0u) f |= FR_REBUILD_FAIL_COLLAPSE;
+  rs->fail = f;
+  rs->emit_nodes = f ? 0u : ctr[0];
+  if (!f) *out = TreeDesc{ctr[0], ctr[1], ctr[4] - 1u, 0u};
+}
+
+// The last kernel of an enqueued build. A failed build (rs->fail) has partly written the destination: the tree in
+// use (src_*) is copied over it, whole, with its record (host_desc when the host knows that tree's numbers,
+// host_nodes >= 0; *src_desc when it has not seen that tree either): 16-B words, consecutive lanes consecutive
+// words, a grid-stride loop. Lane 0 of block 0 counts the verdict.
+__global__ void k_rebuild_keep(RebuildState* __restrict__ rs, const BvhNode* __restrict__ src_nodes,
+                               const TriGeo* __restrict__ src_tri, const int32_t* __restrict__ src_prim, int host_nodes,
+                               TreeDesc host_desc, const TreeDesc* __restrict__ src_desc, int n,
+                               BvhNode* __restrict__ dst_nodes, TriGeo* __restrict__ dst_tri,
+                               int32_t* __restrict__ dst_prim, TreeDesc* __restrict__ dst_desc) {
+  const uint32_t f = rs->fail;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!f) {
+    if (lead) rs->built++;
+    return;
+  }
+  const TreeDesc d = host_nodes >= 0 ? host_desc : *src_desc;
+  const size_t nn = min((size_t)d.nodes, (size_t)n);
+  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const f4* s4 = reinterpret_cast<const f4*>(src_nodes);
+  f4* d4 = reinterpret_cast<f4*>(dst_nodes);
+  for (size_t q = first; q < nn * 8; q += stride) d4[q] = s4[q];
+  s4 = reinterpret_cast<const f4*>(src_tri);
+  d4 = reinterpret_cast<f4*>(dst_tri);
+  for (size_t q = first; q < (size_t)n * 3; q += stride) d4[q] = s4[q];
+  for (size_t q = first; q < (size_t)n; q += stride) dst_prim[q] = src_prim[q];
+  if (lead) {
+    *dst_desc = d;
+    rs->failed++;
+    if (f & FR_REBUILD_FAIL_SAH) rs->failed_sah++;
+    if (f & FR_REBUILD_FAIL_STACK) rs->failed_stack++;
+    if (f & FR_REBUILD_FAIL_COLLAPSE) rs->failed_collapse++;
+  }
+}
+
+static_assert(sizeof(BvhNode) == 8 * sizeof(f4) && sizeof(TriGeo) == 3 * sizeof(f4), "k_rebuild_keep copies 16-B words");
+
+// collapse_and_emit without the host: `levels` collapse launches (level L holds at most min(4^L, n) items), the
+// verdict, the leaf kernels over the capacity with the node count from the device, and the keep kernel.
+// (qa[0] = the root item and ctr = {1, 0, 1, 0, 0}: k_build_init.) sah_fail: see k_rebuild_verdict; it also gates
+// the collapse, whose binary tree's root is a leaf after a failure there.
+template <class Tree>
+static bool collapse_and_emit_enqueue(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, int levels,
+                                      const uint32_t* sah_fail, const RebuildTarget& t, hipStream_t s, std::string& err) {
+  const int B = 256, G = (n + B - 1) / B;
+  RebuildState* rs = t.rs;
+  CollapseItem *qa = w.qa, *qb = w.qb;
+  auto collapse = sah_fail ? k_collapse<Tree, true> : k_collapse<Tree, false>;
+  for (int L = 0; L < levels; L++) {
+    const long long items = L < 15 ? std::min<long long>(1ll << (2 * L), n) : n;
+    const int GL = (int)((items + B - 1) / B);
+    hipLaunchKernelGGL(collapse, dim3(GL), dim3(B), 0, s, T, qa, rs->level + L, qb, rs->level + L + 1, w.ctr, t.nodes,
+                       w.ctr + 1, w.ctr + 4, sah_fail);
+    std::swap(qa, qb);
+  }
+  hipLaunchKernelGGL(k_rebuild_verdict, dim3(1), dim3(64), 0, s, rs, sah_fail, w.ctr, levels, t.desc);
+  hipLaunchKernelGGL(k_leaf_counts<true>, dim3(G), dim3(B), 0, s, t.nodes, n, w.cnt, &rs->emit_nodes);
+  size_t tb = w.tmp_bytes;
+  hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, n, s);
+  hipLaunchKernelGGL(k_emit_leaves<true>, dim3(G), dim3(B), 0, s, t.nodes, n, w.off, ids, pos, t.tri, t.prim,
+                     &rs->emit_nodes);
+  const int GK = (int)std::min<long long>(((long long)n * 8 + B - 1) / B, 2048);
+  hipLaunchKernelGGL(k_rebuild_keep, dim3(GK), dim3(B), 0, s, rs, t.src_nodes, t.src_tri, t.src_prim, t.src_host_nodes,
+                     t.src_host_desc, t.src_desc, n, t.nodes, t.tri, t.prim, t.desc);
+  if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
+  return true;
+}
+
+bool gpu_collapse_marked_enqueue(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, int levels,
+                                 const uint32_t* sah_fail, const RebuildTarget& t, hipStream_t s, std::string& err) {
+  if (!work || n < 3 || n > work->cap || levels < 1 || levels > FR_REBUILD_LEVELS || !sah_fail) {
+    err = "GPU BVH builder: no workspace for these triangles";
+    return false;
+  }
+  return collapse_and_emit_enqueue(*work, MarkedBinTree{T.child, T.range, T.lo, T.hi}, ids, pos, n, levels, sah_fail, t, s,
+                                   err);
+}
+
+bool gpu_rebuild_begin_enqueue(RebuildState* rs, hipStream_t s, std::string& err) {
+  hipLaunchKernelGGL(k_rebuild_begin, dim3(1), dim3(128), 0, s, rs);
+  if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
+  return true;
+}
+
+// gpu_build_bvh in stream order: the same launches up to the binary tree (they never read anything back), then
+// collapse_and_emit_enqueue with today's bound of 64 collapse launches. The workspace must exist (fr_create's).
+bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s, std::string& err) {
+  if (!work || n < 3 || n > work->cap) { err = "GPU BVH builder: no workspace for these triangles"; return false; }
+  BvhWork& w = *work;
+  if (!gpu_rebuild_begin_enqueue(t.rs, s, err)) return false;
+  hipLaunchKernelGGL(k_build_init, dim3(1), dim3(64), 0, s, w.cb, w.qa, w.ctr);
+  const int B = 256, G = (n + B - 1) / B;
+  hipLaunchKernelGGL(k_prim_boxes, dim3(std::min(G, 2048)), dim3(B), 0, s, pos, n, w.blo, w.bhi, w.cb);
+  hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, s, w.blo, w.bhi, n, w.cb, w.codes, w.ids);
+  size_t tb = w.tmp_bytes;
+  hipcub::DeviceRadixSort::SortPairs(w.tmp, tb, w.codes, w.codes_s, w.ids, w.ids_s, n, 0, 30, s);
+  hipLaunchKernelGGL(k_karras, dim3(G), dim3(B), 0, s, w.codes_s, n, w.child, w.parent, w.range);
+  hipMemsetAsync(w.arrivals, 0, (size_t)n * sizeof(uint32_t), s);
+  hipLaunchKernelGGL(k_boxes_up, dim3(G), dim3(B), 0, s, n, w.ids_s, w.blo, w.bhi, w.parent, w.child, w.nlo, w.nhi,
+                     w.arrivals);
+  BinTree T{n, w.child, w.range, w.nlo, w.nhi, w.blo, w.bhi, w.ids_s};
+  return collapse_and_emit_enqueue(w, T, w.ids_s, pos, n, FR_REBUILD_LEVELS, nullptr, t, s, err);
+}
+
 // Refits the four-wide tree nodes[0, num_nodes) (either builder's) over new positions, in place: every slot box
 // and tri[j] for every leaf-order j are rewritten, child / count / prim are not. num_nodes == 0 (the whole scene
 // is one leaf): tri only. Three launches whatever the depth, no allocation; the scratch is *work's nlo / nhi
 // (raw node boxes), parent and arrivals, which hold one entry per triangle (a tree has at most as many nodes).
 // gpu_refit_bvh_enqueue launches them and returns (reject: NULL, or the device verdict word of an enqueued update,
 // which selects the gated kernels); gpu_refit_bvh also waits for them.
+// nodes_dev (the enqueue forms; NULL: num_nodes is the tree's): the tree's node count in device memory, for a tree
+// the host has not seen (fr_rebuild_bvh_enqueue). num_nodes is ignored then and the grids cover the capacity, n.
 bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
-                           const int32_t* prim, const uint32_t* reject, hipStream_t s, std::string& err) {
-  if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
+                           const int32_t* prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+                           std::string& err) {
+  if (nodes_dev) num_nodes = n;
+  if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap || (nodes_dev && !reject)) {
     err = "GPU BVH refit: no workspace for this tree";
     return false;
   }
   BvhWork& w = *work;
   const int B = 256;
   auto tris = reject ? k_refit_tris<true> : k_refit_tris<false>;
-  auto links = reject ? k_refit_links<true> : k_refit_links<false>;
-  auto up = reject ? k_refit_up<true> : k_refit_up<false>;
+  auto links = nodes_dev ? k_refit_links<true, true> : reject ? k_refit_links<true> : k_refit_links<false>;
+  auto up = nodes_dev ? k_refit_up<true, true> : reject ? k_refit_up<true> : k_refit_up<false>;
   hipLaunchKernelGGL(tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, prim, n, tri, reject);
   if (num_nodes > 0) {
     const int GN = (num_nodes + B - 1) / B;
-    hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals, reject);
+    hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals, reject, nodes_dev);
     hipLaunchKernelGGL(up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo, w.nhi,
-                       reject);
+                       reject, nodes_dev);
   }
   if (hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: launch failure";
@@ -839,7 +993,9 @@ bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, 
 // verdict word, never NULL. The same scratch, the same three launches, no wait.
 bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
                               const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
-                              int32_t* dst_prim, const uint32_t* reject, hipStream_t s, std::string& err) {
+                              int32_t* dst_prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+                              std::string& err) {
+  if (nodes_dev) num_nodes = n;
   if (!work || !reject || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
     err = "GPU BVH refit: no workspace for this tree";
     return false;
@@ -850,10 +1006,10 @@ bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode
                      reject);
   if (num_nodes > 0) {
     const int GN = (num_nodes + B - 1) / B;
-    hipLaunchKernelGGL(k_refit_links_to, dim3(GN), dim3(B), 0, s, src_nodes, num_nodes, w.parent, w.arrivals, dst_nodes,
-                       reject);
-    hipLaunchKernelGGL(k_refit_up_to, dim3(GN), dim3(B), 0, s, src_nodes, dst_nodes, num_nodes, pos, src_prim, w.parent,
-                       w.arrivals, w.nlo, w.nhi, reject);
+    hipLaunchKernelGGL(nodes_dev ? k_refit_links_to<true> : k_refit_links_to<false>, dim3(GN), dim3(B), 0, s, src_nodes,
+                       num_nodes, w.parent, w.arrivals, dst_nodes, reject, nodes_dev);
+    hipLaunchKernelGGL(nodes_dev ? k_refit_up_to<true> : k_refit_up_to<false>, dim3(GN), dim3(B), 0, s, src_nodes,
+                       dst_nodes, num_nodes, pos, src_prim, w.parent, w.arrivals, w.nlo, w.nhi, reject, nodes_dev);
   }
   if (hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: launch failure";
@@ -864,7 +1020,7 @@ bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode
 
 bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
                    hipStream_t s, std::string& err) {
-  if (!gpu_refit_bvh_enqueue(work, pos, n, nodes, num_nodes, tri, prim, nullptr, s, err)) return false;
+  if (!gpu_refit_bvh_enqueue(work, pos, n, nodes, num_nodes, tri, prim, nullptr, nullptr, s, err)) return false;
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: kernel failure";
     return false;

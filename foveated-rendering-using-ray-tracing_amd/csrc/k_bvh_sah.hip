@@ -19,6 +19,8 @@
 //     centroid bounds.
 // A child's box is the union of the bins on its side: the union of its triangles' boxes.
 // The four-wide part is k_bvh.hip's (gpu_collapse_marked): collapse, leaf scan, triangle relayout.
+// gpu_build_bvh_sah reads the counters back once per eight levels and stops when a level made no node;
+// gpu_build_bvh_sah_enqueue (fr_rebuild_bvh_enqueue) launches every level and reads nothing back.
 //
 // Not the host's: a node with ex > 0 none of whose candidates has a finite cost (coordinates around 1e19) fails
 // the build (the host falls back to a median there), and the host's FOVRT_BVH_* tuning variables are not read.
@@ -364,6 +366,7 @@ __global__ void k_sah_select(SahDev D, int depth, uint32_t* __restrict__ slots, 
 
 // Large nodes: bin -> "goes left", the scan's input (0 everywhere else).
 __global__ void k_sah_flags(SahDev D, const uint32_t* __restrict__ slots) {
+  if (D.ctr[C_BIG_CUR] == 0u) return;  // (nobody reads the scan of such a level)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= D.n) return;
   uint32_t f = 0u;
@@ -554,6 +557,46 @@ bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode
   }
   return gpu_collapse_marked(work, MarkedTree{w.kid, w.rng, w.nlo, w.nhi}, w.ids, pos, n, nodes, tri, prim, num_nodes,
                              max_stack, depth, s, err);
+}
+
+// The build in stream order: every level of the depth bound is launched, with the large nodes' kernels whenever the
+// scene can have a large node at all. Each kernel reads its level's range and C_BIG_CUR from ctr, so a level past the
+// last one, or one without large nodes, finds nothing. C_FAIL stays on the device: it gates the collapse and feeds
+// the verdict (k_bvh.hip).
+bool gpu_build_bvh_sah_enqueue(SahWork* sw, BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s,
+                               std::string& err) {
+  if (n < 3) { err = "GPU BVH builder needs at least 3 triangles"; return false; }
+  if (!sw || !work || n > sw->cap) { err = "GPU SAH builder: no workspace for these triangles"; return false; }
+  if (!gpu_rebuild_begin_enqueue(t.rs, s, err) || !gpu_prim_boxes_enqueue(work, pos, n, s, err)) return false;
+  const BvhWorkView v = bvh_work_view(work);
+  SahWork& w = *sw;
+  SahDev D{n, 2 * n, (int)slot_cap_of(n), v.blo, v.bhi, w.ids, w.node_of, w.flag, w.scan, w.tmp_id, w.tmp_dst,
+           w.rng, w.kid, w.nlo, w.nhi, w.bslot, w.ctr};
+  const int B = 256, G = (n + B - 1) / B;
+  hipLaunchKernelGGL(k_sah_ids, dim3(G), dim3(B), 0, s, w.ids, w.node_of, n);
+  hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, s, D, v.cb, w.slots[0]);
+  const bool big = n > kSmall;
+  for (int level = 0; level < kMaxDepth; level++) {
+    uint32_t *cur = w.slots[level & 1], *next = w.slots[(level + 1) & 1];
+    hipLaunchKernelGGL(k_sah_level, dim3(1), dim3(64), 0, s, w.ctr);
+    const long long cap_nodes = std::min<long long>(1ll << level, n);
+    const int GS = (int)std::min<long long>((cap_nodes + 3) / 4, 4096);
+    hipLaunchKernelGGL(k_sah_small, dim3(GS), dim3(B), 0, s, D, level);
+    // (splits are uneven, so no level is known on the host to be free of large nodes: each of these leaves at once
+    // on the device when C_BIG_CUR is 0)
+    if (!big) continue;
+    hipLaunchKernelGGL(k_sah_bin, dim3(G), dim3(B), 0, s, D, cur);
+    const int GN = (int)std::min<long long>((cap_nodes + B - 1) / B, 1024);
+    hipLaunchKernelGGL(k_sah_select, dim3(GN), dim3(B), 0, s, D, level, cur, next);
+    hipLaunchKernelGGL(k_sah_flags, dim3(G), dim3(B), 0, s, D, cur);
+    size_t tb = w.tmp_bytes;
+    hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.flag, w.scan, n, s);
+    hipLaunchKernelGGL(k_sah_move_read, dim3(G), dim3(B), 0, s, D, cur, next);
+    hipLaunchKernelGGL(k_sah_move_write, dim3(G), dim3(B), 0, s, D);
+  }
+  if (hipGetLastError() != hipSuccess) { err = "GPU SAH builder: launch failure"; return false; }
+  return gpu_collapse_marked_enqueue(work, MarkedTree{w.kid, w.rng, w.nlo, w.nhi}, w.ids, pos, n, kMaxDepth,
+                                     w.ctr + C_FAIL, t, s, err);
 }
 
 }  // namespace fr

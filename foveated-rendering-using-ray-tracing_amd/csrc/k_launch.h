@@ -105,12 +105,15 @@ bool bvh_work_prepare(BvhWork** w, int n, hipStream_t s, std::string& err);
 bool bvh_builder_warm(BvhWork* w, hipStream_t s, std::string& err);
 bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
                    hipStream_t s, std::string& err);
+// (nodes_dev, here and below: NULL, or the node count in device memory of a tree the host has not seen)
 bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
-                           const int32_t* prim, const uint32_t* reject, hipStream_t s, std::string& err);
+                           const int32_t* prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+                           std::string& err);
 // the refit of an enqueued update out of place: from the tree in use into another set of arrays, whole
 bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
                               const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
-                              int32_t* dst_prim, const uint32_t* reject, hipStream_t s, std::string& err);
+                              int32_t* dst_prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+                              std::string& err);
 bool gpu_check_positions_enqueue(BvhWork* work, const float* xyz, int n, hipStream_t s, std::string& err);
 bool gpu_take_over_positions(BvhWork* work, const f3* xyz, const f3* cur, int n, f3* dst, const uint32_t* bad_nrm,
                              GeoUpdateState* st, int flags, f3 seed_lo, f3 seed_hi, hipStream_t s, std::string& err);
@@ -140,6 +143,30 @@ bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids,
                          TriGeo* tri, int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s,
                          std::string& err);
 
+// A build in stream order (fr_rebuild_bvh_enqueue): where it goes (nodes / tri / prim, n entries each, and the
+// record of its numbers), the context's record of such builds, and the tree in use, which a build that fails on the
+// device copies over the destination (src_host_nodes >= 0: the host knows its numbers, src_host_desc; else src_desc).
+struct RebuildTarget {
+  RebuildState* rs;
+  BvhNode* nodes;
+  TriGeo* tri;
+  int32_t* prim;
+  TreeDesc* desc;
+  const BvhNode* src_nodes;
+  const TriGeo* src_tri;
+  const int32_t* src_prim;
+  int src_host_nodes;
+  TreeDesc src_host_desc;
+  const TreeDesc* src_desc;
+};
+// gpu_build_bvh / gpu_collapse_marked on a fixed launch schedule: no wait, no read-back, no allocation. The verdict
+// and the tree's numbers stay on the device (t.rs, t.desc). levels: the collapse launches (the binary tree's depth
+// bounds them); sah_fail: the device word that says the binary tree failed.
+bool gpu_rebuild_begin_enqueue(RebuildState* rs, hipStream_t s, std::string& err);
+bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s, std::string& err);
+bool gpu_collapse_marked_enqueue(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, int levels,
+                                 const uint32_t* sah_fail, const RebuildTarget& t, hipStream_t s, std::string& err);
+
 // k_bvh_sah.hip: the device binned-SAH builder (fr_config.bvh_builder = 2), whose tree is the host builder's
 struct SahWork;
 bool sah_work_create(SahWork** out, int n, hipStream_t s, std::string& err);
@@ -148,6 +175,9 @@ size_t sah_work_bytes(int n);
 // gpu_build_bvh's contract. *unsupported: the build met a node without a finite SAH candidate (see fovrt.h)
 bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim,
                        int* num_nodes, int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err);
+// the same build in stream order: all 30 levels are launched (those past the last find nothing), see RebuildTarget
+bool gpu_build_bvh_sah_enqueue(SahWork* sw, BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s,
+                               std::string& err);
 
 // k_normals.hip: shading normals over moving geometry
 struct NormalsWork;

@@ -182,6 +182,8 @@ _SIGS = {
     "fr_geometry_consumed": [C.c_void_p, C.c_void_p],
     "fr_set_geometry_overlap": [C.c_void_p, C.c_int],
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "fr_rebuild_bvh_enqueue": [C.c_void_p],
+    "fr_bvh_rebuild_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_model_count": [C.c_void_p, C.POINTER(C.c_int)],
     "fr_model_info": [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fr_scene_model_count": [C.c_void_p, C.POINTER(C.c_int)],
@@ -705,6 +707,19 @@ class PathTracer:
         a, r = C.c_uint64(), C.c_uint64()
         self._check(_lib.fr_geometry_update_status(self._ctx, C.byref(a), C.byref(r)))
         return a.value, r.value
+
+    def rebuild_bvh_enqueue(self):
+        """fr_rebuild_bvh_enqueue: rebuild_bvh() in stream order, without waiting for the GPU, with the context's
+        builder over the current positions; compose it with update_geometry_enqueue or an enqueued pose. A build
+        that fails on the device keeps the tree in use: bvh_rebuild_status()."""
+        self._check(_lib.fr_rebuild_bvh_enqueue(self._ctx))
+
+    def bvh_rebuild_status(self):
+        """(built, failed): enqueued rebuilds by their verdict on the device since the context was created.
+        Waits for the context's pending work; after a new failure last_error() names the cause."""
+        b, f = C.c_uint64(), C.c_uint64()
+        self._check(_lib.fr_bvh_rebuild_status(self._ctx, C.byref(b), C.byref(f)))
+        return b.value, f.value
 
     def models(self):
         """[(name, first_tri, ntris)]: the scene's models, contiguous triangle ranges in scene order."""

@@ -419,6 +419,41 @@ const char* fr_group_last_error(void);  /* the failure of the calling thread's l
  * shading normals, texture coordinates and materials are kept. */
 int fr_rebuild_bvh(fr_ctx* ctx, float* ms);
 int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
+/* fr_rebuild_bvh without host synchronisation: the tree is rebuilt over the current positions with the context's
+ * builder (the LBVH on bvh_builder 0 and 1 contexts, the binned SAH on bvh_builder 2 ones), enqueued behind the
+ * context's pending work; the call returns without waiting for the GPU. It synchronises no stream and no event,
+ * copies nothing to the host that it waits for and allocates nothing; the builder runs a fixed schedule of
+ * launches (every level its depth bound allows; those past the last find nothing to do). The update calls have no
+ * rebuild form in stream order: a caller composes fr_update_geometry_enqueue or fr_set_model_transforms_enqueue
+ * (which refit) with this call when it wants a new tree.
+ * Equality: after a successful enqueued rebuild the tree, fr_scene_export's bvh_nodes / bvh_depth / bvh_max_stack,
+ * fr_bvh_sah_cost and every later frame are what fr_rebuild_bvh called at the same point of the stream order
+ * leaves (the tree is free only where bvh_builder says it is: node numbering within a level, order inside a leaf;
+ * on a bvh_builder 2 context it is the host builder's tree over those positions). Positions, normals, scene box and
+ * motion-reprojection state are untouched: like fr_rebuild_bvh the call is no position update.
+ * Where it runs: on the context stream, or with fr_set_geometry_overlap on, on the stream of the front stages,
+ * beside the previous frame's path trace. In both modes the build goes into the spare tree arrays, which become the
+ * scene's when the call returns (overlapped: with the second array of shading records, brought up to date); frames
+ * already enqueued keep the arrays they were given. Calls after it do not wait either: a later enqueued update or
+ * pose refits the new tree, a later fr_frame(..., NULL) traces it, a later fr_rebuild_bvh_enqueue replaces it, none
+ * of them with host knowledge of its node count.
+ * Failure on the device: a bvh_builder 2 node with no finite SAH candidate (coordinates around 1e19), a tree whose
+ * stack need exceeds FR_BVH_STACK, or a collapse that did not finish in the launches provided. The scene then
+ * keeps the tree it had, bit for bit (a last kernel, gated on the verdict, copies the tree in use over the partly
+ * written arrays, whole): the tree's numbers and every later frame are as if the call had not been made. Counters
+ * on the device record each verdict: fr_bvh_rebuild_status waits for the context's pending work, as
+ * fr_geometry_update_status does, and returns how many enqueued rebuilds built a tree and how many failed since
+ * fr_create (either pointer may be NULL); when the failed count grew since its last call, fr_last_error says why.
+ * Refused at once, nothing enqueued, scene untouched: a NULL context (FR_E_INVALID); a rank of a group or a
+ * sharded context (FR_E_UNSUPPORTED); a scene of fewer than 3 triangles (fr_rebuild_bvh's answer); a context whose
+ * tree in use is not yet a device-built one with a spare set beside it (FR_E_STATE: a bvh_builder 0 context
+ * before its first fr_rebuild_bvh or FR_BVH_REBUILD update, which make the arrays; this call never allocates).
+ * Every other call behaves as before and orders itself behind a pending rebuild; the synchronous ones
+ * (fr_refit_bvh, fr_bvh_sah_cost, fr_scene_export, fr_snapshot, the synchronous updates) wait as they already do
+ * and then learn the tree's numbers from the device. A context that never makes the call differs in nothing.
+ * Not covered: groups and sharded contexts; a rebuild the device itself triggers from the tree's SAH cost. */
+int fr_rebuild_bvh_enqueue(fr_ctx* ctx);
+int fr_bvh_rebuild_status(fr_ctx* ctx, uint64_t* built, uint64_t* failed);
 /* Moving geometry without giving up the tree. fr_refit_bvh keeps the topology of the tree in use (whichever
  * builder made it: the host SAH tree too) and recomputes every slot box bottom-up and every leaf triangle
  * from the current positions, in place; node count, depth and stack need do not change; *ms = its wall time.
@@ -473,7 +508,7 @@ int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* 
 /* fr_update_geometry (device memory, refit) without host synchronisation: a caller who deforms the mesh before
  * every frame keeps the frame pipeline full. xyz is device memory the context's device can read, 9 floats per
  * triangle; nrm the same kind of array, required for FR_NORMALS_GIVEN and ignored otherwise. The tree is always
- * refitted (FR_BVH_REFIT; a rebuild keeps its synchronous call). The update is enqueued on the context stream
+ * refitted (FR_BVH_REFIT; compose it with fr_rebuild_bvh_enqueue for a rebuild). The update is enqueued on the context stream
  * after the work already there and the call returns without waiting for the GPU: it synchronises no stream and no
  * event, copies nothing to the host and allocates nothing (what it needs is made by fr_create).
  * ready_event: a hipEvent_t the caller recorded after producing the arrays (the update's first read waits for it
@@ -505,7 +540,8 @@ int fr_normal_groups(fr_ctx* ctx, int32_t* corner_vertex, size_t ncorners, int* 
  * place; fr_set_geometry_overlap below gives the overlap back). Synchronous updates, fr_refit_bvh, fr_set_normals,
  * fr_recompute_normals, fr_snapshot and fr_restore keep their behaviour after enqueued updates (they wait for
  * pending work as always).
- * Not covered: groups and sharded contexts, a rebuild without synchronisation, host-memory arrays. */
+ * Not covered: groups and sharded contexts, host-memory arrays (a rebuild without synchronisation is
+ * fr_rebuild_bvh_enqueue). */
 int fr_update_geometry_enqueue(fr_ctx* ctx, const void* xyz, const void* nrm, size_t ntris, int normals,
                                void* ready_event);
 int fr_geometry_consumed(fr_ctx* ctx, void* stream);

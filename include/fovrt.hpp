@@ -195,6 +195,12 @@ class PathTracer {
   void geometry_update_status(uint64_t* applied, uint64_t* rejected) {
     check(fr_geometry_update_status(ctx(), applied, rejected), ctx_, "geometry_update_status");
   }
+  // fr_rebuild_bvh_enqueue: rebuild_bvh in stream order, without waiting for the GPU (compose it with an enqueued
+  // update or pose). A build that fails on the device keeps the tree in use: bvh_rebuild_status counts it.
+  void rebuild_bvh_enqueue() { check(fr_rebuild_bvh_enqueue(ctx()), ctx_, "rebuild_bvh_enqueue"); }
+  void bvh_rebuild_status(uint64_t* built, uint64_t* failed) {
+    check(fr_bvh_rebuild_status(ctx(), built, failed), ctx_, "bvh_rebuild_status");
+  }
   // The scene's models (load_obj's meshes, FR/PathTracer.cpp:604-772): contiguous triangle ranges in scene order.
   struct Model {
     std::string name;
