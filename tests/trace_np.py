@@ -548,14 +548,14 @@ def _round_u32(x):
 def gbuffer_np(sc, cam, W, H, frame):
     """Entry 0 (g_buffer_trace_camera.cu:84-151, g_diffuse.cu:67-144, gradientbg.cu:45-51)."""
     out = {k: np.zeros((H, W, 4), np.float32) for k in ("position", "normal", "depth", "diffuse", "weight")}
-    inv_vp, prev_vp = list(cam.inv_vp[:]), list(cam.prev_vp[:])
+    from trace_cases import camera_rays_np  # the camera ray's arithmetic, shared with the off-preset cases
+    prev_vp = list(cam.prev_vp[:])
     eye = v3(*cam.eye[:])
     screen = (f(W), f(H))
+    rays = camera_rays_np(cam, W, H)[1]
     for y in range(H):
         for x in range(W):
-            ndc = (fma(f(f(x) / screen[0]), f(2), f(-1)), fma(f(f(y) / screen[1]), f(2), f(-1)))
-            tmp = mat_vec(inv_vp, (ndc[0], ndc[1], f(-1), f(1)))
-            d = normalize(sub(div_w(tmp), eye))
+            d = tuple(rays[y, x])
             h = sc.closest(eye, d, EPS)
             if h is None:  # g_miss: result 0, radiance 0, reproject_uv -1; origin / normal / depth stay 0
                 out["position"][y, x] = (0, 0, 0, 1)
