@@ -62,6 +62,7 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   b.host_nodes = 0;
   c->bvh = std::move(b);
   c->tree_on_device = false;  // (the host has just seen this tree's numbers)
+  c->base_stale = true;       // (a conditional rebuild adopts this tree's cost first)
   return FR_OK;
 }
 
@@ -111,6 +112,8 @@ static int host_timed(fr_ctx* c, float* ms, F body) {
   if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
+
+static int policy_after_update(fr_ctx* c);  // (fr_set_rebuild_policy, below the enqueued rebuild)
 
 extern "C" {
 
@@ -419,7 +422,8 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
 
 int fr_update_geometry_enqueue(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris, int normals, void* ready_event) {
   if (!c) return FR_E_INVALID;
-  return enqueue_update(c, "fr_update_geometry_enqueue", xyz, nrm, ntris, normals, ready_event);
+  if (int rc = enqueue_update(c, "fr_update_geometry_enqueue", xyz, nrm, ntris, normals, ready_event)) return rc;
+  return policy_after_update(c);
 }
 
 int fr_geometry_consumed(fr_ctx* c, void* stream) {
@@ -451,12 +455,8 @@ int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) 
   return FR_OK;
 }
 
-// fr_rebuild_bvh in stream order: the context's builder on its fixed launch schedule (gpu_build_bvh_enqueue,
-// gpu_build_bvh_sah_enqueue), on the stream enqueue_update would use and behind the same fences; see the notes above
-// it. The build goes into the spare tree arrays, which become the scene's here, whatever the verdict (a failed build
-// ends with the tree in use copied over them, whole). Nothing waits, nothing is copied to the host, nothing is
-// allocated: the new tree's numbers are the device record's until a host reader asks (tree_numbers).
-static int enqueue_rebuild(fr_ctx* c, const std::string& name) {
+// What both enqueued rebuilds and fr_set_rebuild_policy refuse before anything is enqueued.
+static int check_rebuild_state(fr_ctx* c, const std::string& name) {
   if (c->group_refs > 0 || c->U.shard_count > 1)
     return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_rebuild_bvh)");
   const int nt = c->scene.num_tris();
@@ -466,6 +466,26 @@ static int enqueue_rebuild(fr_ctx* c, const std::string& name) {
       !c->geo || (sah && !c->sah_work) || (c->overlap_on && !c->shade_back))
     return fail(c, FR_E_STATE, name + ": the tree in use is not yet a device-built one with a spare set beside it "
                                       "(call fr_rebuild_bvh once first; this call allocates nothing)");
+  return FR_OK;
+}
+static int check_ratio(fr_ctx* c, const std::string& name, float ratio) {
+  if (!std::isfinite(ratio) || ratio < 1.0f) return fail(c, FR_E_INVALID, name + ": ratio must be finite and at least 1");
+  return FR_OK;
+}
+
+// fr_rebuild_bvh in stream order: the context's builder on its fixed launch schedule (gpu_build_bvh_enqueue,
+// gpu_build_bvh_sah_enqueue), on the stream enqueue_update would use and behind the same fences; see the notes above
+// it. The build goes into the spare tree arrays, which become the scene's here, whatever the verdict (a failed build
+// ends with the tree in use copied over them, whole). Nothing waits, nothing is copied to the host, nothing is
+// allocated: the new tree's numbers are the device record's until a host reader asks (tree_numbers).
+// ratio: NULL, or the condition of fr_rebuild_bvh_enqueue_if (checked by the caller). The conditional form puts the
+// decision ahead of the schedule and the new tree's cost behind it, on the same stream: the cost's scratch is the
+// builders' (bvh_work's codes, counters and hipCUB storage), which the checks and the refit of an update enqueued
+// earlier have finished with in stream order, and which the build's first kernels only write after the decision.
+static int enqueue_rebuild(fr_ctx* c, const std::string& name, const float* ratio = nullptr) {
+  if (int rc = check_rebuild_state(c, name)) return rc;
+  const int nt = c->scene.num_tris();
+  const bool sah = c->cfg.bvh_builder == 2;
   hipSetDevice(c->cfg.device);
   const bool overlap = c->overlap_on;
   const hipStream_t s = overlap ? c->front_stream : c->stream;
@@ -494,10 +514,16 @@ static int enqueue_rebuild(fr_ctx* c, const std::string& name) {
   t.src_host_desc = fr::TreeDesc{(uint32_t)std::max(t.src_host_nodes, 0), (uint32_t)c->bvh.max_stack,
                                  (uint32_t)c->bvh.max_depth, 0u};
   t.src_desc = &c->rb->tree[c->desc_cur];
+  t.conditional = ratio ? 1 : 0;
   std::string err;
+  if (ratio && !gpu_rebuild_decide_enqueue(c->bvh_work, c->rb, c->d_nodes, std::max(t.src_host_nodes, 0), nt,
+                                           c->tree_on_device ? &t.src_desc->nodes : nullptr, *ratio, c->base_stale, s, err))
+    return fail(c, FR_E_HIP, name + ": " + err);
   if (sah ? !gpu_build_bvh_sah_enqueue(c->sah_work, c->bvh_work, c->d_pos, nt, t, s, err)
           : !gpu_build_bvh_enqueue(c->bvh_work, c->d_pos, nt, t, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
+  if (ratio && !gpu_rebuild_rebase_enqueue(c->bvh_work, t, nt, s, err)) return fail(c, FR_E_HIP, name + ": " + err);
+  c->base_stale = !ratio;  // (the unconditional build installs a tree whose cost nobody has evaluated)
   // (overlapped: the other set's shading records are an update old; the tree's verdict does not touch them)
   if (overlap && !gpu_normals_to_enqueue(c->nrm_work, nullptr, nullptr, c->d_shade, c->shade_back, &c->geo->reject, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
@@ -521,13 +547,64 @@ int fr_rebuild_bvh_enqueue(fr_ctx* c) {
   return enqueue_rebuild(c, "fr_rebuild_bvh_enqueue");
 }
 
-int fr_bvh_rebuild_status(fr_ctx* c, uint64_t* built, uint64_t* failed) {
+int fr_rebuild_bvh_enqueue_if(fr_ctx* c, float ratio) {
   if (!c) return FR_E_INVALID;
+  const std::string name = "fr_rebuild_bvh_enqueue_if";
+  if (int rc = check_rebuild_state(c, name)) return rc;
+  if (int rc = check_ratio(c, name, ratio)) return rc;
+  return enqueue_rebuild(c, name, &ratio);
+}
+
+int fr_set_rebuild_policy(fr_ctx* c, float ratio, int period) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_rebuild_policy";
+  if (period < 0) return fail(c, FR_E_INVALID, name + ": period is negative");
+  if (period > 0) {
+    if (int rc = check_rebuild_state(c, name)) return rc;
+    if (int rc = check_ratio(c, name, ratio)) return rc;
+  }
+  c->policy_ratio = ratio;
+  c->policy_period = period;
+  c->policy_count = 0;
+  return FR_OK;
+}
+
+}  // extern "C"
+
+// The policy's part of an enqueue call that has accepted its update or pose: every policy_period-th of them is
+// followed by the conditional rebuild, as a caller would make it by hand.
+static int policy_after_update(fr_ctx* c) {
+  if (c->policy_period <= 0 || ++c->policy_count % c->policy_period != 0) return FR_OK;
+  c->policy_count = 0;
+  return enqueue_rebuild(c, "fr_set_rebuild_policy (the update is enqueued; the rebuild it owes)", &c->policy_ratio);
+}
+
+// The record of enqueued rebuilds, behind the context's pending work, in its pinned copy (a wait).
+static int fetch_rebuild_record(fr_ctx* c) {
   join_recon(c);
   hipSetDevice(c->cfg.device);
   HIP_TRY(c, hipMemcpyAsync(c->h_rb, c->rb, sizeof(fr::RebuildState), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->tree_on_device) take_tree_numbers(c);
+  return FR_OK;
+}
+
+extern "C" {
+
+int fr_bvh_rebuild_policy_status(fr_ctx* c, uint64_t* evaluated, uint64_t* skipped, float* last_cost, float* base_cost) {
+  if (!c) return FR_E_INVALID;
+  if (int rc = fetch_rebuild_record(c)) return rc;
+  const fr::RebuildState& r = *c->h_rb;
+  if (evaluated) *evaluated = r.cond_built + r.cond_failed + r.skipped;
+  if (skipped) *skipped = r.skipped;
+  if (last_cost) *last_cost = r.last_cost;
+  if (base_cost) *base_cost = r.base_cost;
+  return FR_OK;
+}
+
+int fr_bvh_rebuild_status(fr_ctx* c, uint64_t* built, uint64_t* failed) {
+  if (!c) return FR_E_INVALID;
+  if (int rc = fetch_rebuild_record(c)) return rc;
   const fr::RebuildState& r = *c->h_rb;
   if (built) *built = r.built;
   if (failed) *failed = r.failed;
@@ -640,7 +717,7 @@ int fr_set_model_transforms_enqueue(fr_ctx* c, const float* m, size_t nmodels) {
                               FR_NORMALS_GIVEN, nullptr, &args))
     return rc;
   c->pose_m.assign(m, m + 12 * nmodels);
-  return FR_OK;
+  return policy_after_update(c);
 }
 
 int fr_model_transforms(fr_ctx* c, float* m, size_t nmodels) {

@@ -201,6 +201,15 @@ struct fr_ctx {
   bool tree_on_device = false;
   int desc_cur = 0;
   unsigned long long rb_failed_seen[4] = {};
+  // Conditional rebuilds (fr_rebuild_bvh_enqueue_if). base_stale: rb->base_cost is not the cost of the tree in use when
+  // it was built or adopted, because that tree came by another route (fr_create, gpu_rebuild, the unconditional
+  // enqueued rebuild); the next conditional call hands the flag to its deciding kernel, which adopts the tree's cost.
+  // The policy (fr_set_rebuild_policy): after every policy_period-th update or pose accepted by the enqueue calls
+  // (policy_count, since the policy was set) the context makes the conditional call itself; period 0: off.
+  bool base_stale = true;
+  float policy_ratio = 0.0f;
+  int policy_period = 0;
+  int policy_count = 0;
   // Model poses (fr_model_pose_enable, fr_set_model_transforms). Four arrays of 9 floats per triangle, made by the
   // first enable: the rest geometry a pose is relative to (positions, and d_shade's normals expanded) and the
   // staging arrays k_pose writes and the update path then reads as a caller's device arrays. All four are read

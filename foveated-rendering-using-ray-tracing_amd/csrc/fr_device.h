@@ -104,22 +104,31 @@ struct GeoUpdateState {
   float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
 };
 
-// Device-side record of enqueued rebuilds (fr_rebuild_bvh_enqueue), one per context. The numbers of a tree the host
-// has not seen live in tree[]: the build writes the record that is not the current tree's, which then becomes it.
+// Device-side record of enqueued rebuilds (fr_rebuild_bvh_enqueue, fr_rebuild_bvh_enqueue_if), one per context. The
+// numbers of a tree the host has not seen live in tree[]: the build writes the record that is not the current
+// tree's, which then becomes it.
 struct TreeDesc {
   uint32_t nodes, max_stack, depth, pad;
 };
 #define FR_REBUILD_FAIL_SAH 1u       // a builder-2 node without a finite SAH candidate
 #define FR_REBUILD_FAIL_STACK 2u     // the tree needs a traversal stack deeper than FR_BVH_STACK
 #define FR_REBUILD_FAIL_COLLAPSE 4u  // the collapse's level queue was not empty after the launches provided
+#define FR_REBUILD_SKIP 8u           // a conditional build the device declined (k_rebuild_decide): it writes nothing
 #define FR_REBUILD_LEVELS 64         // collapse launches of the LBVH form (the SAH form: 30)
 struct RebuildState {
   unsigned long long built, failed;                            // builds since fr_create, by verdict
   unsigned long long failed_sah, failed_stack, failed_collapse;  // failed ones by cause (more than one may count)
   TreeDesc tree[2];
-  uint32_t fail;        // verdict of the build in flight (FR_REBUILD_FAIL_* bits), written by k_rebuild_verdict
-  uint32_t emit_nodes;  // the nodes whose leaves are emitted: the built tree's, or 0 after a failed build
+  // verdict of the build in flight: FR_REBUILD_SKIP or 0 from k_rebuild_decide (a conditional build; every kernel of
+  // the schedule up to k_rebuild_verdict reads it there, since the builders reset their own counters), then the
+  // FR_REBUILD_FAIL_* bits from k_rebuild_verdict, which keeps a skip
+  uint32_t fail;
+  uint32_t emit_nodes;  // the nodes whose leaves are emitted: the built tree's, or 0 after a failed or skipped build
   uint32_t level[FR_REBUILD_LEVELS + 1];  // items of each collapse level; the last: left over after the last launch
+  // conditional builds (fr_rebuild_bvh_enqueue_if) by verdict; built and failed above count them as well
+  unsigned long long cond_built, cond_failed, skipped;
+  float base_cost;  // the SAH cost a conditional build compares with: the tree's when it was adopted or built
+  float last_cost;  // the SAH cost evaluated last (the tree in use; after a build, the new tree's)
 };
 
 // A pose of the scene's models (fr_set_model_transforms), passed to k_pose by value: everything the kernel needs

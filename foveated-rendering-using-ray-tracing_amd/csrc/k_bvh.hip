@@ -23,7 +23,9 @@
 // the refit's gated kernels and the take-over of the positions by verdict (gpu_take_over_positions).
 // The build has an enqueue form as well (fr_rebuild_bvh_enqueue: gpu_build_bvh_enqueue, gpu_collapse_marked_enqueue): a
 // fixed launch schedule whose verdict and numbers stay in device memory (RebuildState), and the refit has forms
-// that take the node count of such a tree from there.
+// that take the node count of such a tree from there. A conditional build (fr_rebuild_bvh_enqueue_if) puts the cost
+// and a one-lane decision ahead of that schedule (gpu_rebuild_decide_enqueue) and the new tree's cost behind it
+// (gpu_rebuild_rebase_enqueue); a build the device declines runs the schedule over an empty level 0.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -537,11 +539,21 @@ __global__ void k_refit_up_to(const BvhNode* __restrict__ src, BvhNode* __restri
 }
 
 // SAH cost terms: part[i] = sum over node i's non-empty slots of area(stored box) * (1 for an inner slot, count
-// for a leaf slot); *root_area = the area of the union of node 0's slot boxes.
+// for a leaf slot); *root_area = the area of the union of node 0's slot boxes. DEVN: every entry of the capacity is
+// written (0 past the tree, and a root area of 0 for a tree without a node: the sum runs over all). GATE (the cost
+// of a tree a conditional build has just made): NULL, or the build's verdict word; nothing is read of a destination
+// that a failed or skipped build left (the terms are 0 then, and k_rebuild_rebase does not look at the sum).
+template <bool DEVN>
 __global__ void k_cost_terms(const BvhNode* __restrict__ nodes, int nn, float* __restrict__ part,
-                             float* __restrict__ root_area) {
+                             float* __restrict__ root_area, const uint32_t* __restrict__ nn_dev,
+                             const uint32_t* __restrict__ gate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nn) return;
+  if (DEVN && (i >= (int)*nn_dev || (gate && *gate))) {
+    part[i] = 0.0f;
+    if (i == 0) *root_area = 0.0f;
+    return;
+  }
   const BvhNode nd = nodes[i];
   const float* LX = &nd.lox.x; const float* HX = &nd.hix.x;
   const float* LY = &nd.loy.x; const float* HY = &nd.hiy.x;
@@ -831,16 +843,56 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
 // ---------------------------------------------------------------------------------------------
 // The level counters of the collapse: level L's launch reads level[L] and counts its inner children into
 // level[L + 1], so no counter is reset or copied between launches.
-__global__ void k_rebuild_begin(RebuildState* __restrict__ rs) {
-  for (int t = threadIdx.x; t <= FR_REBUILD_LEVELS; t += blockDim.x) rs->level[t] = t == 0 ? 1u : 0u;
+// conditional (here and below): the build is fr_rebuild_bvh_enqueue_if's and rs->fail holds k_rebuild_decide's word;
+// a skipped build starts from an empty level 0, so every collapse launch finds nothing. An unconditional build never
+// reads the word a previous build left there.
+__global__ void k_rebuild_begin(RebuildState* __restrict__ rs, int conditional) {
+  const uint32_t root = conditional && (rs->fail & FR_REBUILD_SKIP) ? 0u : 1u;
+  for (int t = threadIdx.x; t <= FR_REBUILD_LEVELS; t += blockDim.x) rs->level[t] = t == 0 ? root : 0u;
+}
+
+// The decision of a conditional build (fr_rebuild_bvh_enqueue_if; include/fovrt.h states the rule), one lane, after
+// the cost terms of the tree in use and their sum (sums[0]; sums[1]: the root's area). nodes: the tree's node count
+// (host_nodes when the host knows it, >= 0; else *nn_dev). The word it leaves in rs->fail is FR_REBUILD_SKIP or 0.
+__global__ void k_rebuild_decide(RebuildState* __restrict__ rs, const float* __restrict__ sums, int host_nodes,
+                                 const uint32_t* __restrict__ nn_dev, float ratio, int base_stale) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  rs->fail = FR_REBUILD_SKIP;
+  const uint32_t nodes = host_nodes >= 0 ? (uint32_t)host_nodes : *nn_dev;
+  if (nodes == 0u) return;
+  const float sum = sums[0], root = sums[1];
+  if (!(root > 0.0f)) return;
+  const float cost = (float)(1.0 + (double)sum / (double)root);  // gpu_bvh_cost's
+  if (!isfinite(cost)) return;
+  rs->last_cost = cost;
+  // (a baseline of 0 was never adopted: an earlier evaluation of this tree found nothing to score)
+  if (base_stale || !(rs->base_cost > 0.0f)) { rs->base_cost = cost; return; }
+  if (cost > ratio * rs->base_cost) rs->fail = 0u;
+}
+
+// After a conditional build, one lane: the cost of a tree it built (the terms' sum as above, over the new tree) is
+// the baseline from now on. A failed or skipped build leaves the baseline alone.
+__global__ void k_rebuild_rebase(RebuildState* __restrict__ rs, const float* __restrict__ sums) {
+  if (threadIdx.x != 0 || blockIdx.x != 0 || rs->fail) return;
+  const float sum = sums[0], root = sums[1];
+  if (!(root > 0.0f)) return;
+  const float cost = (float)(1.0 + (double)sum / (double)root);
+  if (!isfinite(cost)) return;
+  rs->base_cost = rs->last_cost = cost;
 }
 
 // The verdict, one lane, after the last collapse launch. sah_fail: the SAH builder's failure word (NULL: the LBVH);
 // ctr: node_ctr, max_stack, -, -, levels (k_build_init, k_collapse); levels: the collapse launches made. The built
-// tree's numbers go to *out; rs->emit_nodes gates the leaf kernels.
+// tree's numbers go to *out; rs->emit_nodes gates the leaf kernels. A skipped build keeps its word and emits nothing.
 __global__ void k_rebuild_verdict(RebuildState* __restrict__ rs, const uint32_t* __restrict__ sah_fail,
-                                  const uint32_t* __restrict__ ctr, int levels, TreeDesc* __restrict__ out) {
+                                  const uint32_t* __restrict__ ctr, int levels, TreeDesc* __restrict__ out,
+                                  int conditional) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (conditional && (rs->fail & FR_REBUILD_SKIP)) {
+    rs->fail = FR_REBUILD_SKIP;
+    rs->emit_nodes = 0u;
+    return;
+  }
   uint32_t f = 0u;
   if (sah_fail && *sah_fail) f |= FR_REBUILD_FAIL_SAH;
   if (!f && ctr[1] > (uint32_t)FR_BVH_STACK) f |= FR_REBUILD_FAIL_STACK;
@@ -853,16 +905,20 @@ __global__ void k_rebuild_verdict(RebuildState* __restrict__ rs, const uint32_t*
 // The last kernel of an enqueued build. A failed build (rs->fail) has partly written the destination: the tree in
 // use (src_*) is copied over it, whole, with its record (host_desc when the host knows that tree's numbers,
 // host_nodes >= 0; *src_desc when it has not seen that tree either): 16-B words, consecutive lanes consecutive
-// words, a grid-stride loop. Lane 0 of block 0 counts the verdict.
+// words, a grid-stride loop. A skipped build wrote nothing there, and the destination becomes the scene's all the
+// same: the same copy. Lane 0 of block 0 counts the verdict (a skip in `skipped`, not in `failed`).
 __global__ void k_rebuild_keep(RebuildState* __restrict__ rs, const BvhNode* __restrict__ src_nodes,
                                const TriGeo* __restrict__ src_tri, const int32_t* __restrict__ src_prim, int host_nodes,
                                TreeDesc host_desc, const TreeDesc* __restrict__ src_desc, int n,
                                BvhNode* __restrict__ dst_nodes, TriGeo* __restrict__ dst_tri,
-                               int32_t* __restrict__ dst_prim, TreeDesc* __restrict__ dst_desc) {
+                               int32_t* __restrict__ dst_prim, TreeDesc* __restrict__ dst_desc, int conditional) {
   const uint32_t f = rs->fail;
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   if (!f) {
-    if (lead) rs->built++;
+    if (lead) {
+      rs->built++;
+      if (conditional) rs->cond_built++;
+    }
     return;
   }
   const TreeDesc d = host_nodes >= 0 ? host_desc : *src_desc;
@@ -877,7 +933,9 @@ __global__ void k_rebuild_keep(RebuildState* __restrict__ rs, const BvhNode* __r
   for (size_t q = first; q < (size_t)n; q += stride) dst_prim[q] = src_prim[q];
   if (lead) {
     *dst_desc = d;
+    if (f & FR_REBUILD_SKIP) { rs->skipped++; return; }
     rs->failed++;
+    if (conditional) rs->cond_failed++;
     if (f & FR_REBUILD_FAIL_SAH) rs->failed_sah++;
     if (f & FR_REBUILD_FAIL_STACK) rs->failed_stack++;
     if (f & FR_REBUILD_FAIL_COLLAPSE) rs->failed_collapse++;
@@ -904,7 +962,7 @@ static bool collapse_and_emit_enqueue(BvhWork& w, Tree T, const int32_t* ids, co
                        w.ctr + 1, w.ctr + 4, sah_fail);
     std::swap(qa, qb);
   }
-  hipLaunchKernelGGL(k_rebuild_verdict, dim3(1), dim3(64), 0, s, rs, sah_fail, w.ctr, levels, t.desc);
+  hipLaunchKernelGGL(k_rebuild_verdict, dim3(1), dim3(64), 0, s, rs, sah_fail, w.ctr, levels, t.desc, t.conditional);
   hipLaunchKernelGGL(k_leaf_counts<true>, dim3(G), dim3(B), 0, s, t.nodes, n, w.cnt, &rs->emit_nodes);
   size_t tb = w.tmp_bytes;
   hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, n, s);
@@ -912,7 +970,7 @@ static bool collapse_and_emit_enqueue(BvhWork& w, Tree T, const int32_t* ids, co
                      &rs->emit_nodes);
   const int GK = (int)std::min<long long>(((long long)n * 8 + B - 1) / B, 2048);
   hipLaunchKernelGGL(k_rebuild_keep, dim3(GK), dim3(B), 0, s, rs, t.src_nodes, t.src_tri, t.src_prim, t.src_host_nodes,
-                     t.src_host_desc, t.src_desc, n, t.nodes, t.tri, t.prim, t.desc);
+                     t.src_host_desc, t.src_desc, n, t.nodes, t.tri, t.prim, t.desc, t.conditional);
   if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
   return true;
 }
@@ -927,8 +985,8 @@ bool gpu_collapse_marked_enqueue(BvhWork* work, const MarkedTree& T, const int32
                                    err);
 }
 
-bool gpu_rebuild_begin_enqueue(RebuildState* rs, hipStream_t s, std::string& err) {
-  hipLaunchKernelGGL(k_rebuild_begin, dim3(1), dim3(128), 0, s, rs);
+bool gpu_rebuild_begin_enqueue(RebuildState* rs, int conditional, hipStream_t s, std::string& err) {
+  hipLaunchKernelGGL(k_rebuild_begin, dim3(1), dim3(128), 0, s, rs, conditional);
   if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
   return true;
 }
@@ -938,7 +996,7 @@ bool gpu_rebuild_begin_enqueue(RebuildState* rs, hipStream_t s, std::string& err
 bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s, std::string& err) {
   if (!work || n < 3 || n > work->cap) { err = "GPU BVH builder: no workspace for these triangles"; return false; }
   BvhWork& w = *work;
-  if (!gpu_rebuild_begin_enqueue(t.rs, s, err)) return false;
+  if (!gpu_rebuild_begin_enqueue(t.rs, t.conditional, s, err)) return false;
   hipLaunchKernelGGL(k_build_init, dim3(1), dim3(64), 0, s, w.cb, w.qa, w.ctr);
   const int B = 256, G = (n + B - 1) / B;
   hipLaunchKernelGGL(k_prim_boxes, dim3(std::min(G, 2048)), dim3(B), 0, s, pos, n, w.blo, w.bhi, w.cb);
@@ -1037,7 +1095,8 @@ bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cos
   const int B = 256;
   float* part = reinterpret_cast<float*>(w.codes);
   float* sums = reinterpret_cast<float*>(w.ctr + 5);  // sum, root area
-  hipLaunchKernelGGL(k_cost_terms, dim3((num_nodes + B - 1) / B), dim3(B), 0, s, nodes, num_nodes, part, sums + 1);
+  hipLaunchKernelGGL(k_cost_terms<false>, dim3((num_nodes + B - 1) / B), dim3(B), 0, s, nodes, num_nodes, part, sums + 1,
+                     nullptr, nullptr);
   size_t tb = w.tmp_bytes;
   hipcub::DeviceReduce::Sum(w.tmp, tb, part, sums, num_nodes, s);
   hipMemcpyAsync(w.host + 5, w.ctr + 5, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
@@ -1050,6 +1109,48 @@ bool gpu_bvh_cost(BvhWork* work, const BvhNode* nodes, int num_nodes, float* cos
   memcpy(&root, w.host + 6, sizeof(float));
   if (!(root > 0.0f)) { err = "GPU BVH cost: the root box has no area"; return false; }
   *cost = (float)(1.0 + (double)sum / (double)root);
+  return true;
+}
+
+// The cost in stream order, for a conditional build (fr_rebuild_bvh_enqueue_if): gpu_bvh_cost's terms and sum into the
+// same scratch, nothing read back. nodes_dev (NULL: num_nodes is the tree's): the node count in device memory; the
+// grid and the sum then cover the capacity, n. gate: k_cost_terms'.
+static void cost_enqueue(BvhWork& w, const BvhNode* nodes, int num_nodes, int n, const uint32_t* nodes_dev,
+                         const uint32_t* gate, hipStream_t s) {
+  const int B = 256, len = nodes_dev ? n : num_nodes;
+  float* part = reinterpret_cast<float*>(w.codes);
+  float* sums = reinterpret_cast<float*>(w.ctr + 5);
+  hipLaunchKernelGGL(nodes_dev ? k_cost_terms<true> : k_cost_terms<false>, dim3((len + B - 1) / B), dim3(B), 0, s, nodes,
+                     len, part, sums + 1, nodes_dev, gate);
+  size_t tb = w.tmp_bytes;
+  hipcub::DeviceReduce::Sum(w.tmp, tb, part, sums, len, s);
+}
+
+// The decision of a conditional build, ahead of its schedule: the cost of the tree in use (num_nodes, or nodes_dev for
+// a tree the host has not seen) and k_rebuild_decide, which leaves the verdict word in rs->fail. No wait.
+bool gpu_rebuild_decide_enqueue(BvhWork* work, RebuildState* rs, const BvhNode* nodes, int num_nodes, int n,
+                                const uint32_t* nodes_dev, float ratio, bool base_stale, hipStream_t s,
+                                std::string& err) {
+  if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
+    err = "GPU BVH cost: no workspace for this tree";
+    return false;
+  }
+  BvhWork& w = *work;
+  if (nodes_dev || num_nodes > 0) cost_enqueue(w, nodes, num_nodes, n, nodes_dev, nullptr, s);
+  hipLaunchKernelGGL(k_rebuild_decide, dim3(1), dim3(64), 0, s, rs, reinterpret_cast<const float*>(w.ctr + 5),
+                     nodes_dev ? -1 : num_nodes, nodes_dev, ratio, base_stale ? 1 : 0);
+  if (hipGetLastError() != hipSuccess) { err = "GPU BVH cost: launch failure"; return false; }
+  return true;
+}
+
+// Behind a conditional build: the cost of the tree it made (t.nodes, whose node count is t.desc's) becomes the
+// baseline (k_rebuild_rebase). After a failed or skipped build the terms are not read and nothing changes. No wait.
+bool gpu_rebuild_rebase_enqueue(BvhWork* work, const RebuildTarget& t, int n, hipStream_t s, std::string& err) {
+  if (!work || n < 1 || n > work->cap) { err = "GPU BVH cost: no workspace for this tree"; return false; }
+  BvhWork& w = *work;
+  cost_enqueue(w, t.nodes, n, n, &t.desc->nodes, &t.rs->fail, s);
+  hipLaunchKernelGGL(k_rebuild_rebase, dim3(1), dim3(64), 0, s, t.rs, reinterpret_cast<const float*>(w.ctr + 5));
+  if (hipGetLastError() != hipSuccess) { err = "GPU BVH cost: launch failure"; return false; }
   return true;
 }
 

@@ -219,9 +219,15 @@ FR_DEV int split_node(const SahDev& D, int node, int depth, const uint32_t* bins
   return best_k;
 }
 
-// The root, its slot (the centroid bounds are k_prim_boxes') and the counters.
-__global__ void k_sah_init(SahDev D, const uint32_t* __restrict__ cb, uint32_t* __restrict__ slots0) {
+// The root, its slot (the centroid bounds are k_prim_boxes') and the counters. verdict: NULL, or the word of a
+// conditional build (RebuildState::fail); a skipped one starts without a root, so every level finds nothing.
+__global__ void k_sah_init(SahDev D, const uint32_t* __restrict__ cb, uint32_t* __restrict__ slots0,
+                           const uint32_t* __restrict__ verdict) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (verdict && (*verdict & FR_REBUILD_SKIP)) {
+    for (int k = 0; k < C_WORDS; k++) D.ctr[k] = 0u;
+    return;
+  }
   D.rng[0] = int2{0, D.n};
   D.kid[0] = int2{0, 0};
   D.nlo[0] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -518,7 +524,7 @@ bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode
            w.rng, w.kid, w.nlo, w.nhi, w.bslot, w.ctr};
   const int B = 256, G = (n + B - 1) / B;
   hipLaunchKernelGGL(k_sah_ids, dim3(G), dim3(B), 0, s, w.ids, w.node_of, n);
-  hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, s, D, v.cb, w.slots[0]);
+  hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, s, D, v.cb, w.slots[0], nullptr);
   // Levels in batches with one read of the counters per batch. A level without large nodes has none below it:
   // from the batch after the read that shows it, only the small nodes' kernel runs.
   const int kBatch = 8;
@@ -562,19 +568,20 @@ bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode
 // The build in stream order: every level of the depth bound is launched, with the large nodes' kernels whenever the
 // scene can have a large node at all. Each kernel reads its level's range and C_BIG_CUR from ctr, so a level past the
 // last one, or one without large nodes, finds nothing. C_FAIL stays on the device: it gates the collapse and feeds
-// the verdict (k_bvh.hip).
+// the verdict (k_bvh.hip). A conditional build the device skipped (t.conditional, RebuildState::fail) starts without
+// a root: every level is such a level.
 bool gpu_build_bvh_sah_enqueue(SahWork* sw, BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s,
                                std::string& err) {
   if (n < 3) { err = "GPU BVH builder needs at least 3 triangles"; return false; }
   if (!sw || !work || n > sw->cap) { err = "GPU SAH builder: no workspace for these triangles"; return false; }
-  if (!gpu_rebuild_begin_enqueue(t.rs, s, err) || !gpu_prim_boxes_enqueue(work, pos, n, s, err)) return false;
+  if (!gpu_rebuild_begin_enqueue(t.rs, t.conditional, s, err) || !gpu_prim_boxes_enqueue(work, pos, n, s, err)) return false;
   const BvhWorkView v = bvh_work_view(work);
   SahWork& w = *sw;
   SahDev D{n, 2 * n, (int)slot_cap_of(n), v.blo, v.bhi, w.ids, w.node_of, w.flag, w.scan, w.tmp_id, w.tmp_dst,
            w.rng, w.kid, w.nlo, w.nhi, w.bslot, w.ctr};
   const int B = 256, G = (n + B - 1) / B;
   hipLaunchKernelGGL(k_sah_ids, dim3(G), dim3(B), 0, s, w.ids, w.node_of, n);
-  hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, s, D, v.cb, w.slots[0]);
+  hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, s, D, v.cb, w.slots[0], t.conditional ? &t.rs->fail : nullptr);
   const bool big = n > kSmall;
   for (int level = 0; level < kMaxDepth; level++) {
     uint32_t *cur = w.slots[level & 1], *next = w.slots[(level + 1) & 1];

@@ -146,6 +146,8 @@ bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids,
 // A build in stream order (fr_rebuild_bvh_enqueue): where it goes (nodes / tri / prim, n entries each, and the
 // record of its numbers), the context's record of such builds, and the tree in use, which a build that fails on the
 // device copies over the destination (src_host_nodes >= 0: the host knows its numbers, src_host_desc; else src_desc).
+// conditional: the build is fr_rebuild_bvh_enqueue_if's; gpu_rebuild_decide_enqueue has left FR_REBUILD_SKIP or 0 in
+// rs->fail earlier on the stream, and a skipped build runs the same schedule over an empty level 0.
 struct RebuildTarget {
   RebuildState* rs;
   BvhNode* nodes;
@@ -158,14 +160,22 @@ struct RebuildTarget {
   int src_host_nodes;
   TreeDesc src_host_desc;
   const TreeDesc* src_desc;
+  int conditional;
 };
 // gpu_build_bvh / gpu_collapse_marked on a fixed launch schedule: no wait, no read-back, no allocation. The verdict
 // and the tree's numbers stay on the device (t.rs, t.desc). levels: the collapse launches (the binary tree's depth
 // bounds them); sah_fail: the device word that says the binary tree failed.
-bool gpu_rebuild_begin_enqueue(RebuildState* rs, hipStream_t s, std::string& err);
+bool gpu_rebuild_begin_enqueue(RebuildState* rs, int conditional, hipStream_t s, std::string& err);
 bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s, std::string& err);
 bool gpu_collapse_marked_enqueue(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, int levels,
                                  const uint32_t* sah_fail, const RebuildTarget& t, hipStream_t s, std::string& err);
+// Around a conditional build: the SAH cost of the tree in use and the decision ahead of it (num_nodes, or nodes_dev;
+// the rule is beside fr_rebuild_bvh_enqueue_if in include/fovrt.h), and behind it the cost of a tree it built, which
+// becomes the baseline. gpu_bvh_cost's kernels and scratch; no wait, no read-back.
+bool gpu_rebuild_decide_enqueue(BvhWork* work, RebuildState* rs, const BvhNode* nodes, int num_nodes, int n,
+                                const uint32_t* nodes_dev, float ratio, bool base_stale, hipStream_t s,
+                                std::string& err);
+bool gpu_rebuild_rebase_enqueue(BvhWork* work, const RebuildTarget& t, int n, hipStream_t s, std::string& err);
 
 // k_bvh_sah.hip: the device binned-SAH builder (fr_config.bvh_builder = 2), whose tree is the host builder's
 struct SahWork;

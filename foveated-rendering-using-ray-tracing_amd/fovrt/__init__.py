@@ -184,6 +184,10 @@ _SIGS = {
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_rebuild_bvh_enqueue": [C.c_void_p],
     "fr_bvh_rebuild_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "fr_rebuild_bvh_enqueue_if": [C.c_void_p, C.c_float],
+    "fr_set_rebuild_policy": [C.c_void_p, C.c_float, C.c_int],
+    "fr_bvh_rebuild_policy_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float)],
     "fr_model_count": [C.c_void_p, C.POINTER(C.c_int)],
     "fr_model_info": [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "fr_scene_model_count": [C.c_void_p, C.POINTER(C.c_int)],
@@ -720,6 +724,25 @@ class PathTracer:
         b, f = C.c_uint64(), C.c_uint64()
         self._check(_lib.fr_bvh_rebuild_status(self._ctx, C.byref(b), C.byref(f)))
         return b.value, f.value
+
+    def rebuild_bvh_enqueue_if(self, ratio):
+        """fr_rebuild_bvh_enqueue_if: rebuild_bvh_enqueue() when the device finds the SAH cost of the tree in use
+        above `ratio` times its baseline (the cost of that tree when it was built, or when the first conditional
+        call saw it). Nothing waits; a skipped build leaves tree and frames as they were."""
+        self._check(_lib.fr_rebuild_bvh_enqueue_if(self._ctx, float(ratio)))
+
+    def set_rebuild_policy(self, ratio, period):
+        """fr_set_rebuild_policy: after every `period`-th update_geometry_enqueue or enqueued pose the context
+        makes rebuild_bvh_enqueue_if(ratio) itself. period 0 turns the policy off (the default)."""
+        self._check(_lib.fr_set_rebuild_policy(self._ctx, float(ratio), int(period)))
+
+    def bvh_rebuild_policy_status(self):
+        """(evaluated, skipped, last_cost, base_cost): the conditional rebuilds since the context was created, how
+        many of them the device declined, the SAH cost it evaluated last and the baseline it compares with.
+        Waits for the context's pending work."""
+        e, s, l, b = C.c_uint64(), C.c_uint64(), C.c_float(), C.c_float()
+        self._check(_lib.fr_bvh_rebuild_policy_status(self._ctx, C.byref(e), C.byref(s), C.byref(l), C.byref(b)))
+        return e.value, s.value, l.value, b.value
 
     def models(self):
         """[(name, first_tri, ntris)]: the scene's models, contiguous triangle ranges in scene order."""

@@ -451,9 +451,43 @@ int fr_set_positions(fr_ctx* ctx, const float* xyz, size_t ntris);
  * Every other call behaves as before and orders itself behind a pending rebuild; the synchronous ones
  * (fr_refit_bvh, fr_bvh_sah_cost, fr_scene_export, fr_snapshot, the synchronous updates) wait as they already do
  * and then learn the tree's numbers from the device. A context that never makes the call differs in nothing.
- * Not covered: groups and sharded contexts; a rebuild the device itself triggers from the tree's SAH cost. */
+ * Not covered: groups and sharded contexts. */
 int fr_rebuild_bvh_enqueue(fr_ctx* ctx);
 int fr_bvh_rebuild_status(fr_ctx* ctx, uint64_t* built, uint64_t* failed);
+/* fr_rebuild_bvh_enqueue when the device finds that the tree in use has grown: the stream, the fences, the swap of
+ * the tree arrays, the refusals and the guarantees of that call (no wait, no copy to the host that anything waits
+ * for, no allocation), and the decision is made on the device. Behind the context's pending work the SAH cost of the
+ * tree in use is evaluated (fr_bvh_sah_cost's formula over the stored boxes; held to that call to 1e-4 relative, not
+ * bit for bit: the sum may run over another length) and one lane decides:
+ *   - the tree has no node, or its root area is not > 0, or the cost is not finite: skip, the baseline is untouched;
+ *   - the baseline is stale (the tree in use came from fr_create, fr_rebuild_bvh, an FR_BVH_REBUILD update,
+ *     fr_set_positions or the unconditional fr_rebuild_bvh_enqueue, or no baseline was ever adopted): the cost
+ *     becomes the baseline, skip. The first evaluation of a tree adopts it;
+ *   - cost > ratio * baseline (an fp32 product, strictly greater): build;
+ *   - otherwise: skip.
+ * A build is fr_rebuild_bvh_enqueue's, unchanged; after one that succeeded the new tree's cost is evaluated in stream
+ * order and becomes the baseline. After one that failed on the device tree and baseline are as before and
+ * fr_bvh_rebuild_status counts it as failed. A skipped build runs the same schedule of launches over an empty first
+ * level (an LBVH context still sorts its codes) and ends as a failed one does, with the tree in use copied whole into
+ * the arrays that become the scene's: tree, numbers and every later frame are as if the call had not been made. It
+ * is counted as skipped, not as failed.
+ * Refused at once, nothing enqueued: everything fr_rebuild_bvh_enqueue refuses, with the same codes; a ratio that is
+ * not finite or is below 1 (FR_E_INVALID).
+ * fr_set_rebuild_policy makes the context pose the question itself: with period > 0 it counts the updates and poses
+ * that fr_update_geometry_enqueue and fr_set_model_transforms_enqueue accept on the host (whatever the device's later
+ * verdict on them), from the call that set the policy, and after every period-th of them makes
+ * fr_rebuild_bvh_enqueue_if(ctx, ratio) inside the same call: the context is equal to one whose caller makes those
+ * calls by hand. Should that implicit call be refused (the context's state changed since), the update stays enqueued
+ * and the update call returns the refusal. period 0 turns the policy off (the default; ratio is ignored then);
+ * period < 0 is FR_E_INVALID, and with period > 0 the call is refused wherever fr_rebuild_bvh_enqueue_if would be.
+ * fr_bvh_rebuild_policy_status waits as fr_bvh_rebuild_status does, for the same record: evaluated = conditional
+ * calls since fr_create (built + failed + skipped of those alone), skipped, the cost evaluated last (after a build,
+ * the new tree's) and the baseline. Any pointer may be NULL. fr_bvh_rebuild_status keeps counting every enqueued
+ * build that built or failed, conditional or not. */
+int fr_rebuild_bvh_enqueue_if(fr_ctx* ctx, float ratio);
+int fr_set_rebuild_policy(fr_ctx* ctx, float ratio, int period);
+int fr_bvh_rebuild_policy_status(fr_ctx* ctx, uint64_t* evaluated, uint64_t* skipped, float* last_cost,
+                                 float* base_cost);
 /* Moving geometry without giving up the tree. fr_refit_bvh keeps the topology of the tree in use (whichever
  * builder made it: the host SAH tree too) and recomputes every slot box bottom-up and every leaf triangle
  * from the current positions, in place; node count, depth and stack need do not change; *ms = its wall time.

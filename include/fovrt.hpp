@@ -201,6 +201,20 @@ class PathTracer {
   void bvh_rebuild_status(uint64_t* built, uint64_t* failed) {
     check(fr_bvh_rebuild_status(ctx(), built, failed), ctx_, "bvh_rebuild_status");
   }
+  // fr_rebuild_bvh_enqueue_if: rebuild_bvh_enqueue when the device finds the tree's SAH cost above ratio times its
+  // baseline (the rule is in fovrt.h); set_rebuild_policy has the context make that call after every period-th
+  // enqueued update or pose (period 0: off). bvh_rebuild_policy_status: conditional calls evaluated and skipped, the
+  // cost evaluated last and the baseline (waits for pending work; any pointer may be null).
+  void rebuild_bvh_enqueue_if(float ratio) {
+    check(fr_rebuild_bvh_enqueue_if(ctx(), ratio), ctx_, "rebuild_bvh_enqueue_if");
+  }
+  void set_rebuild_policy(float ratio, int period) {
+    check(fr_set_rebuild_policy(ctx(), ratio, period), ctx_, "set_rebuild_policy");
+  }
+  void bvh_rebuild_policy_status(uint64_t* evaluated, uint64_t* skipped, float* last_cost, float* base_cost) {
+    check(fr_bvh_rebuild_policy_status(ctx(), evaluated, skipped, last_cost, base_cost), ctx_,
+          "bvh_rebuild_policy_status");
+  }
   // The scene's models (load_obj's meshes, FR/PathTracer.cpp:604-772): contiguous triangle ranges in scene order.
   struct Model {
     std::string name;
