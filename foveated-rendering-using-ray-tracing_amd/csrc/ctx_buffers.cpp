@@ -234,6 +234,7 @@ int fr_restore(fr_ctx* c, const void* host, size_t bytes) {
   c->lp_gaze = f2{-1e30f, -1e30f};  // the log-polar mask cache is recomputed for the restored gaze
   c->lp_mode = -1;
   c->sib_prefix_fresh = false;
+  c->jfa_force = true;  // a snapshot carries no JFA state: the next JumpFlooding runs its passes, not what this context retained
   c->hvalid_fresh = false;
   c->moved = false;  // a snapshot carries no previous positions: the next G-buffer reprojects as over still geometry
   return FR_OK;

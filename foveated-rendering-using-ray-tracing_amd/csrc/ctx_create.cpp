@@ -107,6 +107,7 @@ static void read_env_knobs(fr_ctx* c) {
     c->shade_blocks_per_cu = v ? std::max(1, std::min(full, atoi(v))) : full;
   }
   if (const char* v = getenv("FOVRT_JFA_XCD")) c->jfa_xcd = atoi(v);
+  if (const char* v = getenv("FOVRT_JFA_REUSE")) c->jfa_reuse = atoi(v) != 0;  // A/B knob: 0 = every JFA runs its passes
   if (const char* v = getenv("FOVRT_SIB_STRIP_MID")) c->sib_strip_mid = atoi(v);
   if (const char* v = getenv("FOVRT_ATROUS_ROWS2")) c->atrous_rows2 = atoi(v) != 0;
   if (const char* v = getenv("FOVRT_ATROUS_XCD")) c->atrous_xcd = atoi(v) != 0;
@@ -338,7 +339,9 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   if (dalloc(&c->gclass, N) != hipSuccess || dalloc(&c->lp_cache, N) != hipSuccess ||
       dalloc(&c->lp_inv, logpolar_inv_words(c->W, c->H)) != hipSuccess || dalloc(&c->words, nwords) != hipSuccess ||
       dalloc(&c->counts, 4 * nblocks) != hipSuccess || dalloc(&c->offsets, 4 * nblocks) != hipSuccess ||
-      dalloc(&c->tiles, 1024) != hipSuccess || dalloc(&c->jfa_a, N) != hipSuccess || dalloc(&c->jfa_b, N) != hipSuccess ||
+      dalloc(&c->tiles, 1024) != hipSuccess || dalloc(&c->jfa.G, N) != hipSuccess || dalloc(&c->jfa.H, N) != hipSuccess ||
+      dalloc(&c->jfa.F, N) != hipSuccess || dalloc(&c->jfa.seeds, jfa_seed_words(c->W, c->H)) != hipSuccess ||
+      dalloc(&c->jfa.ctl, JFA_CTL_WORDS) != hipSuccess ||
       dalloc(&c->pull, atlas) != hipSuccess || dalloc(&c->push, atlas) != hipSuccess ||
       dalloc(&c->snap, pp_snap_count(c->pp_S)) != hipSuccess || dalloc(&c->stats, 1) != hipSuccess ||
       dalloc(&c->shade_ctr, shade_counter_words()) != hipSuccess || dalloc(&c->samples, std::max(N * cfg.spp, 2 * shade_fx_slots((uint32_t)N, cfg.spp, c->handoff, c->shade_blocks_per_cu))) != hipSuccess ||
@@ -420,7 +423,7 @@ int fr_destroy(fr_ctx* c) {
   for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);
   if (c->update_done.ev) hipEventDestroy(c->update_done.ev);
   for (auto e : c->ev_counts) if (e) hipEventDestroy(e);
-  fr(c->gclass); fr(c->lp_cache); fr(c->lp_inv); fr(c->words); fr(c->counts); fr(c->offsets); fr(c->tiles); fr(c->shade_ctr); fr(c->samples); fr(c->sample_help); fr(c->aux_p[0]); fr(c->aux_p[1]); fr(c->aux_seed_p[0]); fr(c->aux_seed_p[1]); fr(c->hvalid); fr(c->item_store); fr(c->jfa_a); fr(c->jfa_b); fr(c->ftab);
+  fr(c->gclass); fr(c->lp_cache); fr(c->lp_inv); fr(c->words); fr(c->counts); fr(c->offsets); fr(c->tiles); fr(c->shade_ctr); fr(c->samples); fr(c->sample_help); fr(c->aux_p[0]); fr(c->aux_p[1]); fr(c->aux_seed_p[0]); fr(c->aux_seed_p[1]); fr(c->hvalid); fr(c->item_store); fr(c->jfa.G); fr(c->jfa.H); fr(c->jfa.F); fr(c->jfa.seeds); fr(c->jfa.ctl); fr(c->ftab);
   fr(c->pull); fr(c->push); fr(c->snap); fr(c->stats); fr(c->sib_prefix); fr(c->sib_blocks); fr(c->sib_wide); fr(c->sib_strips); fr(c->sib_rowp);
   for (hipEvent_t* e : timed_events(c)) if (*e) hipEventDestroy(*e);
   if (c->front_done.ev) hipEventDestroy(c->front_done.ev);

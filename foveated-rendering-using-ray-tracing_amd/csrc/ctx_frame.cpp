@@ -302,12 +302,21 @@ static int enqueue_jfa(fr_ctx* c, int in_buffer, hipStream_t stream = nullptr) {
   if (resolve(c, in_buffer, &p)) return fail(c, FR_E_INVALID, "jfa: bad input buffer");
   const bool run_form = c->cfg.sibson_mode == 0;
   const bool lazy = run_form && c->lazy_jfa_outputs;
-  c->jfa_final = launch_jfa(c->img[p], c->jfa_a, c->jfa_b, c->img[P_JFA_COORD], c->img[P_JFA_COLOR], c->ftab, c->W,
-                            c->H, run_form ? c->sib_prefix : nullptr, run_form ? c->sib_blocks : nullptr, !lazy,
-                            c->jfa_xcd, stream ? stream : c->stream);
+  if (!stream) stream = c->stream;
+  // The launch's generation (k_jfa.hip). The passes run when the device finds the seed set changed, or when forced;
+  // either way the final state is in jfa.F afterwards, so nothing below or later depends on which it was.
+  if (++c->jfa_gen == 0) {  // wrapped: the device's word starts over with the count
+    hipMemsetAsync(c->jfa.ctl + JFA_CTL_CHANGED, 0, sizeof(uint32_t), stream);
+    c->jfa_gen = 1;
+  }
+  c->jfa_final = launch_jfa(c->img[p], c->jfa, c->jfa_gen, c->jfa_force || !c->jfa_reuse, c->img[P_JFA_COORD],
+                            c->img[P_JFA_COLOR], c->ftab, c->W, c->H, run_form ? c->sib_prefix : nullptr,
+                            run_form ? c->sib_blocks : nullptr, !lazy, c->jfa_xcd, stream);
   c->jfa_coord_owed = lazy;
   c->sib_prefix_fresh = run_form;
-  return check_launch(c);
+  const int rc = check_launch(c);
+  c->jfa_force = rc != FR_OK;  // (a launch that failed may have left the bitmap ahead of the state)
+  return rc;
 }
 static int enqueue_sibson(fr_ctx* c, hipStream_t stream = nullptr) {
   if (c->cfg.sibson_mode == 1) {  // per tap, bit-exact against the oracle (reads JFA_COORD)

@@ -282,7 +282,14 @@ struct fr_ctx {
   bool hvalid_fresh = false;
   bool setup_early = false;  // this frame's setup was enqueued by its front stages
   bool early_setup = true;   // FOVRT_EARLY_SETUP=0: every setup on the context stream before its megakernel
-  u2 *jfa_a = nullptr, *jfa_b = nullptr;  // JFA state ping-pong (seed coord texel + alpha flags)
+  // JFA state (seed coord texel + alpha flags): the passes' ping-pong G / H, the final state F, the seed bitmap and
+  // the control words (k_jfa.hip). jfa_gen: launches so far; jfa_force: the next launch runs its passes whatever the
+  // bitmap says (the first one, the one after fr_restore, one after a failed launch); jfa_reuse: FOVRT_JFA_REUSE=0
+  // forces every launch.
+  fr::JfaState jfa = {};
+  uint32_t jfa_gen = 0;
+  bool jfa_force = true;
+  bool jfa_reuse = true;
   uint32_t chunk_refr = 0;  // fixed refraction-class chunk of the megakernel (FOVRT_SHADE_CHUNK_REFR), 0 adaptive
   uint32_t xcd_bands = 1;   // megakernel queue: per-XCD class bands (FOVRT_SHADE_XCD_BANDS=0: interleaved chunks)
   uint32_t handoff = 1;     // megakernel tail handoff (FOVRT_SHADE_HANDOFF): 0 never, 1 small launches, 2 always

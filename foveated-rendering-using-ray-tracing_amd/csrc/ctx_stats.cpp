@@ -23,6 +23,15 @@ int fr_get_stats(fr_ctx* c, fr_stats* s) {
   return FR_OK;
 }
 
+int fr_jfa_reuse_count(fr_ctx* c, uint32_t* skipped) {
+  if (!c || !skipped) return FR_E_INVALID;
+  join_recon(c);  // (the frame's JumpFlooding runs on the reconstruction stream)
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(skipped, c->jfa.ctl + JFA_CTL_SKIPPED, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FR_OK;
+}
+
 // Test hook (not part of include/fovrt.h): the host build of the bound JFA and Sibson use.
 float fr__sqrt_le_bound(float s) { return sqrt_le_bound(s); }
 

@@ -1,6 +1,7 @@
 // k_jfa.hip — JumpFlooding            FR/JumpFlooding.cpp:60-140, FR/shader/cpFS.glsl, FR/shader/jfFS.glsl
-// JFA propagates a 32-bit seed index (+2 alpha flags) instead of two RGBA32F textures: the reference's
-// coord/colour pair is a pure function of the seed pixel.
+// JFA propagates the seed's texel centre (8 bytes per pixel) instead of two RGBA32F textures: the reference's
+// coord/colour pair is a pure function of the seed pixel. The passes run only when the seed set differs from the
+// previous launch's (a still camera and gaze leave it as it was); the colours are gathered every launch.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "fr_device.h"
@@ -19,17 +20,54 @@ namespace fr {
 // The alpha > 0 case of cpFS (.a in (0, 1)) only sets the current pixel's starting distance, which jfFS
 // ignores while .a < 1: it needs no state. The seed's pixel is recovered exactly as floor(sx * W)
 // (sx*W = x + 0.5 within 2^-8 for W < 2^15).
+//
+// Reuse. The state carries nothing of the colours, so the final state is a function of the seed set {p : alpha >= 1}
+// and of W, H alone. k_jfa_init keeps that set as a bitmap (`seeds`: one 64-bit wave ballot per 64 consecutive
+// pixels, zero bits past W H) and compares each word with the one the previous launch left. Every launch has a
+// generation number (the host counts them); a launch that finds a word changed, or that the host forces, raises
+// ctl[JFA_CTL_CHANGED] to its generation (an atomic max: nothing ever resets the word, so no block races with a reset).
+// The passes of a launch whose generation is not in that word leave at once: the fixed buffer F still holds the final
+// state of the last launch that changed the set, which is the state they would compute, bit for bit. For F to survive
+// such a launch nothing but a pass that runs writes it: k_jfa_init writes G, the passes go G -> H -> G ..., and the
+// last one writes F. The colours enter in the final kernels only, which run every launch and count the launches whose
+// passes were skipped in ctl[JFA_CTL_SKIPPED]. The host never learns the outcome: it forces the first launch of a
+// context, the one after fr_restore, and every launch when FOVRT_JFA_REUSE=0.
 // ------------------------------------------------------------------------------------------
 
-__global__ void k_jfa_init(const f4* __restrict__ in, u2* __restrict__ state, int W, int H, f2 screen) {
+__global__ __launch_bounds__(256) void k_jfa_init(const f4* __restrict__ in, u2* __restrict__ state,
+                                                  unsigned long long* __restrict__ seeds, uint32_t* ctl, uint32_t gen,
+                                                  int force, int W, int H, f2 screen) {
   // 32-bit pixel indices (fr_create keeps W H below 2^26): one 32-bit division per pixel, not a 64-bit one
   const uint32_t N = (uint32_t)W * (uint32_t)H;
-  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < N; p += gridDim.x * blockDim.x) {
-    const float a = in[p].w;
-    const uint32_t y = p / (uint32_t)W;
-    const f2 uv = frag_uv(p - y * (uint32_t)W, y, screen);
-    state[p] = a >= 1.0f ? u2{__float_as_uint(uv.x) | JFA_FLAG, __float_as_uint(uv.y) | JFA_FLAG}
-                         : u2{JFA_UNSEEDED, __float_as_uint(uv.y)};
+  const uint32_t lane = threadIdx.x & 63u;
+  // a wave always takes one whole bitmap word: 64 pixels from a multiple of 64 (the block is 4 waves and the stride
+  // a multiple of 256), the last word's lanes past N with nothing to load or store and a zero bit
+  int changed = 0;
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p - lane < N; p += gridDim.x * blockDim.x) {
+    bool seed = false;
+    if (p < N) {
+      const float a = in[p].w;
+      const uint32_t y = p / (uint32_t)W;
+      const f2 uv = frag_uv(p - y * (uint32_t)W, y, screen);
+      seed = a >= 1.0f;
+      state[p] = seed ? u2{__float_as_uint(uv.x) | JFA_FLAG, __float_as_uint(uv.y) | JFA_FLAG}
+                      : u2{JFA_UNSEEDED, __float_as_uint(uv.y)};
+    }
+    const unsigned long long bits = __ballot(seed);
+    if (lane == 0) {
+      const uint32_t w = p >> 6;
+      changed |= seeds[w] != bits;
+      seeds[w] = bits;
+    }
+  }
+  // One atomic from a forced launch; else at most one per block that met a changed word, and none once the mark is
+  // seen. (Measured and not kept: one per changed word, all on one address: 0.10 ms more for a 4K launch whose every
+  // word changed, and the panning frame 1 % slower than without the bitmap; MEASUREMENTS.md.)
+  if (force) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&ctl[JFA_CTL_CHANGED], gen);
+  } else if (__syncthreads_or(changed) && threadIdx.x == 0 &&
+             __atomic_load_n(&ctl[JFA_CTL_CHANGED], __ATOMIC_RELAXED) != gen) {
+    atomicMax(&ctl[JFA_CTL_CHANGED], gen);
   }
 }
 
@@ -122,7 +160,11 @@ FR_DEV u2 jfa_pick_rows(const u2 (&nb)[9], f2 me, bool up, bool down) {
 // JFA_ROWS = min(4, ceil(H / step)): the large steps have fewer rows to share.
 template <int JFA_ROWS>
 __global__ __launch_bounds__(256) void k_jfa_step(const u2* __restrict__ src, u2* __restrict__ dst, int W, int H,
-                                                  int step, const float* __restrict__ ftab, int xcd) {
+                                                  int step, const float* __restrict__ ftab, int xcd,
+                                                  const uint32_t* __restrict__ ctl, uint32_t gen) {
+  // the seed set is the previous launch's (k_jfa_init): F holds this launch's final state already. One scalar load
+  // and a wave-uniform branch ahead of everything else.
+  if (ctl[JFA_CTL_CHANGED] != gen) return;
   // xcd: the blocks of one XCD take one contiguous run of the row-major block order, so a block's left and
   // right taps (x -+ step, the neighbouring blocks for steps below 512) and its groups' shared rows are
   // mostly in the L2 that fetched them for its neighbours (round-robin order puts them on other XCDs)
@@ -177,8 +219,15 @@ int jfa_row_groups(int H, int step) {
   return ((H + band - 1) / band) * step;
 }
 
+// a launch whose passes were skipped, counted by one thread of its final kernel (fr_jfa_reuse_count)
+FR_DEV void jfa_count_skipped(uint32_t* ctl, uint32_t gen) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && ctl[JFA_CTL_CHANGED] != gen)
+    atomicAdd(&ctl[JFA_CTL_SKIPPED], 1u);
+}
+
 __global__ void k_jfa_final(const u2* __restrict__ state, const f4* __restrict__ in, f4* __restrict__ coord,
-                            f4* __restrict__ color, int W, int H, f2 screen) {
+                            f4* __restrict__ color, int W, int H, f2 screen, uint32_t* ctl, uint32_t gen) {
+  jfa_count_skipped(ctl, gen);
   const size_t N = (size_t)W * H;
   for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < N; p += (size_t)gridDim.x * blockDim.x) {
     const u2 s = state[p];
@@ -204,7 +253,8 @@ template <bool OUT>
 __global__ __launch_bounds__(64) void k_jfa_final_prefix(const u2* __restrict__ state, const f4* __restrict__ in,
                                                          f4* __restrict__ coord, f4* __restrict__ color,
                                                          f4* __restrict__ P, f4* __restrict__ T, int W, int H, int NB,
-                                                         f2 screen) {
+                                                         f2 screen, uint32_t* ctl, uint32_t gen) {
+  jfa_count_skipped(ctl, gen);
   const int lane = threadIdx.x;
   const int j = blockIdx.y, B = blockIdx.x;
   const int col = B * 64 + lane;
@@ -238,17 +288,19 @@ int jfa_max_step(int W, int H) {
   return m;
 }
 
-const u2* launch_jfa(const f4* in, u2* stateA, u2* stateB, f4* coord, f4* color, const float* ftab, int W, int H,
-                     f4* sibP, f4* sibT, bool outputs, int xcd, hipStream_t stream) {
+// st.F: the final state, of this launch or retained (see the head of this file); st.G, st.H: the passes' ping-pong.
+const u2* launch_jfa(const f4* in, const JfaState& st, uint32_t gen, bool force, f4* coord, f4* color,
+                     const float* ftab, int W, int H, f4* sibP, f4* sibT, bool outputs, int xcd, hipStream_t stream) {
   const size_t N = (size_t)W * H;
   int blocks = (int)std::min<size_t>((N + 255) / 256, 8192);
   f2 screen = mk2((float)W, (float)H);
   // (Measured and not kept: the first pass forming the seeds' states from the input's alpha itself, without
   // k_jfa_init: 138-154 us for that pass against 62 + 33 us for the pass and the init, its 16-byte texel
   // reads per tap doubling the pass's traffic.)
-  hipLaunchKernelGGL(k_jfa_init, dim3(blocks), dim3(256), 0, stream, in, stateA, W, H, screen);
-  u2* a = stateA;
-  u2* b = stateB;
+  hipLaunchKernelGGL(k_jfa_init, dim3(blocks), dim3(256), 0, stream, in, st.G, st.seeds, st.ctl, gen, force ? 1 : 0, W,
+                     H, screen);
+  u2* a = st.G;
+  u2* b = st.H;
   // (Measured and not kept: steps 8, 4, 2, 1 fused in one launch over 64x32 tiles with a 15-texel halo in
   // LDS, 151 us against 4 x 31 us. A pass is VALU-bound, ~130 instructions per pixel, not HBM-bound, and the
   // halos add 29 % of pixel work.)
@@ -256,17 +308,19 @@ const u2* launch_jfa(const f4* in, u2* stateA, u2* stateB, f4* coord, f4* color,
     dim3 grid((W + 63) / 64, (jfa_row_groups(H, step) + 3) / 4);
     auto k = jfa_rows(H, step) == 4 ? k_jfa_step<4> : jfa_rows(H, step) == 3 ? k_jfa_step<3>
            : jfa_rows(H, step) == 2 ? k_jfa_step<2> : k_jfa_step<1>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a, b, W, H, step, ftab, xcd);
+    // the last pass writes F, whichever of G and H it reads
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a, step == 1 ? st.F : b, W, H, step, ftab, xcd, st.ctl, gen);
     std::swap(a, b);
   }
   if (sibP) {
     const int NB = sibson_prefix_blocks(W);
     hipLaunchKernelGGL(outputs ? k_jfa_final_prefix<true> : k_jfa_final_prefix<false>, dim3(NB, H), dim3(64), 0, stream,
-                       a, in, coord, color, sibP, sibT, W, H, NB, screen);
+                       st.F, in, coord, color, sibP, sibT, W, H, NB, screen, st.ctl, gen);
   } else {
-    hipLaunchKernelGGL(k_jfa_final, dim3(blocks), dim3(256), 0, stream, a, in, coord, color, W, H, screen);
+    hipLaunchKernelGGL(k_jfa_final, dim3(blocks), dim3(256), 0, stream, st.F, in, coord, color, W, H, screen, st.ctl,
+                       gen);
   }
-  return a;  // the final state (k_sibson_runs reads its seeds from it)
+  return st.F;  // the final state (k_sibson_runs reads its seeds from it)
 }
 
 // JFA_COORD of a JumpFlooding run whose final pass did not write it (launch_jfa, outputs = false): k_jfa_final's

@@ -78,8 +78,18 @@ void launch_logpolar(const f4* in, f4* fwd, f4* inv, int W, int H, f2 gaze, hipS
 void launch_composite(const f4* views, int nviews, int W, int H, f4* out, hipStream_t stream);
 
 // k_jfa.hip, k_sibson.hip
-const u2* launch_jfa(const f4* in, u2* stateA, u2* stateB, f4* coord, f4* color, const float* ftab, int W, int H,
-                     f4* sibP, f4* sibT, bool outputs, int xcd, hipStream_t stream);
+// A context's JumpFlooding state: G, H the passes' ping-pong, F the final state (retained while the seed set stays),
+// seeds the seed bitmap of the last launch (jfa_seed_words), ctl the JFA_CTL_* words. gen: the launch's generation
+// (a context counts its launches from 1); force: run the passes whatever the bitmap says.
+struct JfaState {
+  u2 *G, *H, *F;
+  unsigned long long* seeds;
+  uint32_t* ctl;
+};
+enum { JFA_CTL_CHANGED = 0, JFA_CTL_SKIPPED = 1, JFA_CTL_WORDS = 2 };
+inline size_t jfa_seed_words(int W, int H) { return ((size_t)W * H + 63) / 64; }
+const u2* launch_jfa(const f4* in, const JfaState& st, uint32_t gen, bool force, f4* coord, f4* color,
+                     const float* ftab, int W, int H, f4* sibP, f4* sibT, bool outputs, int xcd, hipStream_t stream);
 void launch_jfa_coord(const u2* state, const f4* color, f4* coord, int W, int H, hipStream_t stream);
 void launch_sibson(const f4* coord, const f4* color, f4* out, int W, int H, hipStream_t stream);
 void launch_sibson_runs(const f4* coord, const u2* state, const f4* color, f4* P, f4* T, f4* G, uint32_t* wide,

@@ -631,8 +631,9 @@ __global__ __launch_bounds__(SIBR_THREADS) SIBR_ATTR void k_sibson_runs(const f4
   __shared__ uint32_t bucket[SIB_BUCKETS];
   __shared__ uint16_t order[SIBR_THREADS];
   __shared__ f4 slot[SIBR_THREADS];      // raster slot: the pixel's (seed.x, seed.y, d)
-  __shared__ uint8_t done[SIBR_THREADS];  // cleared and never read (left from the LDS-staged store): removing it is a
-                                          // kernel change, to be measured like one
+  __shared__ uint8_t done[SIBR_THREADS];  // cleared and never read (left from the LDS-staged store). Measured without
+                                          // it: Sibson alone 0.711 ms against 0.708 with it, the latter's spread
+                                          // 0.3 %: no gain to show, so it stays (MEASUREMENTS.md, JFA reuse)
   const int tid = threadIdx.x;
   // super-tiles of 4 x 4 tiles: the 16 blocks of one super-tile are dispatched to one XCD one after another (block b
   // runs on XCD b % 8), so the prefix rows its tiles share are fetched into one L2; consecutive super-tiles of the

@@ -203,6 +203,7 @@ _SIGS = {
     "fr_scene_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
     "fr_get_stats": [C.c_void_p, C.POINTER(fr_stats)],
     "fr_reset_stats": [C.c_void_p],
+    "fr_jfa_reuse_count": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fr_kernel_timing": [C.c_void_p, C.c_int],
     "fr_kernel_times": [C.c_void_p, C.POINTER(fr_stage_times)],
     "fr_frame_clock": [C.c_void_p, C.c_int],
@@ -516,6 +517,12 @@ class PathTracer:
 
     def reset_stats(self):
         self._check(_lib.fr_reset_stats(self._ctx))
+
+    def jfa_reuse_count(self) -> int:
+        """fr_jfa_reuse_count: JumpFlooding launches whose passes were skipped (the seed set had not changed)."""
+        v = C.c_uint32()
+        self._check(_lib.fr_jfa_reuse_count(self._ctx, C.byref(v)))
+        return v.value
 
     def kernel_timing(self, enable: bool):
         """Starts (or stops) the live HIP-event timing of entry 3 inside pipelined frames."""

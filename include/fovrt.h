@@ -690,6 +690,13 @@ int fr_restore(fr_ctx* ctx, const void* host, size_t bytes);
 
 int fr_get_stats(fr_ctx* ctx, fr_stats* stats);
 int fr_reset_stats(fr_ctx* ctx);
+/* JumpFlooding launches of this context, in frames and stage calls alike, whose passes were skipped because the
+ * device found the seed set {alpha >= 1} of the input equal to the previous launch's: their final state is the
+ * retained one, bit for bit what the passes would compute, and JFA_COLOR, JFA_COORD and Sibson follow from it as
+ * from any other. Counted on the device since fr_create (modulo 2^32); the call waits for the context's pending
+ * work. The first launch of a context and the first after fr_restore always run their passes, and with
+ * FOVRT_JFA_REUSE=0 in the environment of fr_create every launch does. FR_E_INVALID for a NULL argument. */
+int fr_jfa_reuse_count(fr_ctx* ctx, uint32_t* skipped);
 
 /* Live timing of entry 3 inside pipelined frames (no synchronisation added): after
  * fr_kernel_timing(ctx, 1) every shading stage records HIP events on the context stream around
