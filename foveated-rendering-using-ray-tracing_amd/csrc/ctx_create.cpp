@@ -111,6 +111,9 @@ static void read_env_knobs(fr_ctx* c) {
   if (const char* v = getenv("FOVRT_SIB_STRIP_MID")) c->sib_strip_mid = atoi(v);
   if (const char* v = getenv("FOVRT_ATROUS_ROWS2")) c->atrous_rows2 = atoi(v) != 0;
   if (const char* v = getenv("FOVRT_ATROUS_XCD")) c->atrous_xcd = atoi(v) != 0;
+  // FOVRT_RAYQ_BLOCKS: a cap on k_ray_queries' grid (0, the default: none), so that a test's few hundred rays make
+  // one wave take several chunks
+  if (const char* v = getenv("FOVRT_RAYQ_BLOCKS")) c->rayq_blocks = (uint32_t)std::max(0, atoi(v));
 }
 
 // The context's events that can be timed (plain hipEventCreate): the stage timing, the ordering events inside a frame
@@ -169,6 +172,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   hipEventCreateWithFlags(&c->geo_read.ev, hipEventDisableTiming);
   for (auto& f : c->set_read) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
   hipEventCreateWithFlags(&c->update_done.ev, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->rays_done.ev, hipEventDisableTiming);
   read_env_knobs(c);
 
   std::string err;
@@ -212,6 +216,11 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   }
   // the record of enqueued rebuilds (fr_rebuild_bvh_enqueue allocates nothing either)
   if (dalloc(&c->rb, 1) != hipSuccess || hipHostMalloc((void**)&c->h_rb, sizeof(fr::RebuildState)) != hipSuccess) {
+    c->err = "device allocation (scene) failed";
+    return bail(FR_E_NOMEM);
+  }
+  // the record of ray queries (fr_trace_rays allocates nothing)
+  if (dalloc(&c->rq, 1) != hipSuccess) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
@@ -419,6 +428,8 @@ int fr_destroy(fr_ctx* c) {
   if (c->h_geo) hipHostFree(c->h_geo);
   fr(c->rb);
   if (c->h_rb) hipHostFree(c->h_rb);
+  fr(c->rq); fr(c->rq_rays); fr(c->rq_out);
+  if (c->rays_done.ev) hipEventDestroy(c->rays_done.ev);
   if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
   for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);
   if (c->update_done.ev) hipEventDestroy(c->update_done.ev);

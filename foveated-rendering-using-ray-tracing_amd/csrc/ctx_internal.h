@@ -230,6 +230,17 @@ struct fr_ctx {
   int set_cur = 0;
   Fence set_read[2];
   Fence update_done;
+  // Ray queries (fr_trace_rays, ctx_query.cpp). rq: their record on the device (the chunk counter of k_ray_queries),
+  // made by fr_create and zeroed in stream order ahead of every launch. rq_rays / rq_out: the staging area of host
+  // batches, rq_cap rays and results (fr_ray_query_reserve; 32 B and 16 B each). rays_done: recorded on the context
+  // stream after the last enqueued query's kernel; the caller's stream waits for it (fr_rays_consumed; never
+  // consumed: any number of streams may ask). rayq_blocks: FOVRT_RAYQ_BLOCKS, a cap on the grid, 0 = none.
+  fr::RayQueryState* rq = nullptr;
+  void* rq_rays = nullptr;
+  void* rq_out = nullptr;
+  size_t rq_cap = 0;
+  Fence rays_done;
+  uint32_t rayq_blocks = 0;
   int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
   fr::SahWork* sah_work = nullptr;  // the device SAH builder's scratch (k_bvh_sah.hip): bvh_builder 2 contexts only

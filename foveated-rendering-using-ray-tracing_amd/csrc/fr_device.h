@@ -104,6 +104,15 @@ struct GeoUpdateState {
   float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
 };
 
+// Device-side record of ray queries (fr_trace_rays), one per context, made by fr_create and zeroed in stream order
+// ahead of every launch: the next chunk a wave of k_ray_queries claims in each of the batch's FR_RAYQ_SHARDS runs of
+// chunks (counter k at word k * FR_RAYQ_SHARD_STRIDE, a 128-B line each).
+#define FR_RAYQ_SHARDS 8
+#define FR_RAYQ_SHARD_STRIDE 32
+struct RayQueryState {
+  uint32_t next_chunk[FR_RAYQ_SHARDS * FR_RAYQ_SHARD_STRIDE];
+};
+
 // Device-side record of enqueued rebuilds (fr_rebuild_bvh_enqueue, fr_rebuild_bvh_enqueue_if), one per context. The
 // numbers of a tree the host has not seen live in tree[]: the build writes the record that is not the current
 // tree's, which then becomes it.

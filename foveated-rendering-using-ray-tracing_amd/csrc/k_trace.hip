@@ -1641,6 +1641,120 @@ uint32_t diag_recorded_queries(hipStream_t stream) {
 #endif
 
 // ---------------------------------------------------------------------------------------------
+// Ray queries (fr_trace_rays, include/fovrt.h): a caller's batch of rays against the scene, over trav_begin /
+// trav_step as every other ray of the engine. The shape is k_trace_queries': a persistent grid, a wave claims
+// chunks of RQ_CHUNK rays with one atomic on a counter of the record, a lane whose ray is answered takes the chunk's
+// next ray by its rank among the idle lanes, and a lane never waits for another wave. Against it: 32-B fr_ray
+// records (two 16-B loads) with their own tmin, the degenerate-ray rule ahead of trav_begin (no traversal ever
+// runs on NaN slabs), the scene's triangle index instead of the leaf's, the miss record (+inf, 0, 0, -1), and one
+// template arm per kind (KIND 0: closest hit, 16-B fr_ray_hit records; KIND 1: transmittance, one float each).
+// The batch's chunks are split into FR_RAYQ_SHARDS contiguous runs with a counter each, 128 B apart; a wave starts
+// on the run of its block's XCD (blockIdx & 7) and moves to the next run when its own is exhausted, for good: a
+// run never refills. With one counter the 8.29 M camera rays of a 4K frame took 1.61 ms whatever their order, 12.5 ns
+// per claim (129,600 same-address atomics, which the XCDs' L2s cannot combine); MEASUREMENTS.md, "Ray queries".
+// Launch bounds and waves per SIMD are k_trace_queries' (not retuned).
+// ---------------------------------------------------------------------------------------------
+#ifndef RQ_WAVES
+#define RQ_WAVES 5
+#endif
+#define RQ_CHUNK 64
+// Answered without traversal: a NaN among the eight floats, an origin or a direction that is not finite, the
+// direction (0, 0, 0), and an empty window (tmin >= tmax). (fabsf(NaN) < inf is false, so the finiteness tests
+// catch the NaNs of origin and direction; !(tmin < tmax) those of the window.)
+FR_DEV bool ray_degenerate(f4 a, f4 b) {
+  const bool finite = fabsf(a.x) < INFINITY && fabsf(a.y) < INFINITY && fabsf(a.z) < INFINITY &&
+                      fabsf(b.x) < INFINITY && fabsf(b.y) < INFINITY && fabsf(b.z) < INFINITY;
+  const bool zero = b.x == 0.0f && b.y == 0.0f && b.z == 0.0f;
+  return !finite || zero || !(a.w < b.w);
+}
+template <int KIND>
+FR_DEV void ray_answer(void* __restrict__ out, uint32_t i, const TravState* ts) {
+  if (KIND == 0) {
+    const bool hit = ts && ts->best.leaf >= 0;
+    static_cast<f4*>(out)[i] = hit ? mk4(ts->best.t, ts->best.beta, ts->best.gamma, __int_as_float(ts->best.prim))
+                                   : mk4(INFINITY, 0.0f, 0.0f, __int_as_float(-1));
+  } else {
+    static_cast<float*>(out)[i] = ts ? (float)ts->atten : 1.0f;
+  }
+}
+template <int KIND>
+__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(RQ_WAVES, RQ_WAVES))) void k_ray_queries(
+    DevScene sc, const f4* __restrict__ rays, uint32_t n, void* __restrict__ out, RayQueryState* __restrict__ rq) {
+  __shared__ int32_t lds_stack[BVH_STACK * TRACE_BLOCK];
+  Stack st{&lds_stack[threadIdx.x]};
+  uint32_t q_next = 0, q_end = 0;  // wave-uniform chunk
+  bool more = true;                // the batch may still have chunks
+  const uint32_t chunks = (n + RQ_CHUNK - 1) / RQ_CHUNK;
+  uint32_t shard = blockIdx.x % FR_RAYQ_SHARDS, tried = 0;  // the run this wave claims from; runs found exhausted
+  int qi = -1;                     // this lane's ray
+  f3 o, d;
+  float tmin, tmax;
+  TravState ts;
+  while (true) {
+    unsigned long long need = __ballot(qi < 0);
+    while (need && more) {
+      if (q_next >= q_end) {
+        // the next chunk of this wave's run, or of the first later run that still has one
+        bool got = false;
+        while (tried < FR_RAYQ_SHARDS) {
+          const uint32_t lo = (uint32_t)((uint64_t)chunks * shard / FR_RAYQ_SHARDS),
+                         hi = (uint32_t)((uint64_t)chunks * (shard + 1) / FR_RAYQ_SHARDS);
+          uint32_t j = 0;
+          if ((threadIdx.x & 63) == 0) j = atomicAdd(&rq->next_chunk[shard * FR_RAYQ_SHARD_STRIDE], 1u);
+          j = __builtin_amdgcn_readfirstlane(j);
+          // (j <= a run's chunks + the grid's waves, chunks <= 2^24: no sum or product here reaches 2^32)
+          if (j < hi - lo) {
+            q_next = (lo + j) * RQ_CHUNK;
+            q_end = min(q_next + RQ_CHUNK, n);
+            got = true;
+            break;
+          }
+          shard = (shard + 1) % FR_RAYQ_SHARDS;
+          tried++;
+        }
+        if (!got) { more = false; break; }
+      }
+      if (qi < 0) {
+        const uint32_t i = q_next + lanes_below(need);
+        if (i < q_end) {
+          const f4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
+          if (ray_degenerate(a, b)) {
+            ray_answer<KIND>(out, i, nullptr);  // (the lane stays idle and takes another ray of the chunk)
+          } else {
+            qi = (int)i;
+            o = mk3(a.x, a.y, a.z); tmin = a.w;
+            d = mk3(b.x, b.y, b.z); tmax = b.w;
+            trav_begin(ts, d, tmax);
+          }
+        }
+      }
+      q_next = min(q_next + (uint32_t)__popcll(need), q_end);
+      need = __ballot(qi < 0);
+    }
+    if (!__ballot(qi >= 0)) break;
+    if (qi >= 0 && trav_step(sc, st, ts, o, d, tmin, tmax, KIND == 1)) {
+      ray_answer<KIND>(out, (uint32_t)qi, &ts);
+      qi = -1;
+    }
+  }
+}
+
+// Resident blocks of k_ray_queries: RQ_WAVES waves per SIMD, 4 SIMDs per CU, 256 CUs (12 KB of LDS per block).
+static uint32_t ray_query_resident_blocks() { return 256u * 4u * RQ_WAVES / (TRACE_BLOCK / 64); }
+
+// kind: 0 closest hit (out: n records of 16 B), 1 transmittance (out: n floats). The counter of `rq` is zeroed in
+// stream order ahead of the kernel. max_blocks: the context's cap on the grid (FOVRT_RAYQ_BLOCKS), 0 = none.
+void launch_ray_queries(const DevScene& sc, const void* rays, uint32_t n, int kind, void* out, RayQueryState* rq,
+                        uint32_t max_blocks, hipStream_t stream) {
+  if (n == 0) return;
+  uint32_t blocks = std::min((n + TRACE_BLOCK - 1) / TRACE_BLOCK, ray_query_resident_blocks());
+  if (max_blocks) blocks = std::min(blocks, max_blocks);
+  (void)hipMemsetAsync(rq, 0, sizeof(RayQueryState), stream);
+  hipLaunchKernelGGL(kind == 1 ? k_ray_queries<1> : k_ray_queries<0>, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc,
+                     static_cast<const f4*>(rays), n, out, rq);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------------------------
 void launch_gbuffer(const DevScene& sc, const FrameUniforms& U, f4* position, f4* normal, f4* depth, f4* diffuse,

@@ -35,6 +35,9 @@ FR_BVH_REBUILD, FR_BVH_REFIT = 0, 1
 FR_MEM_HOST, FR_MEM_DEVICE = 0, 1
 # fr_update_geometry: what becomes of the shading normals
 FR_NORMALS_KEEP, FR_NORMALS_GIVEN, FR_NORMALS_RECOMPUTE = 0, 1, 2
+# fr_trace_rays: what a query answers
+FR_RAYS_CLOSEST, FR_RAYS_TRANSMITTANCE = 0, 1
+RAY_KINDS = {"closest": FR_RAYS_CLOSEST, "transmittance": FR_RAYS_TRANSMITTANCE}
 MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 0, 1, 2, 3, 4
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
@@ -103,6 +106,19 @@ class fr_group_config(C.Structure):
                 ("composite", C.c_int), ("recon_cost", C.c_float * 2), ("weights", C.c_float * GROUP_MAX_VIEW_RANKS),
                 ("sample_sum", C.c_int), ("front_local", C.c_int),
                 ("jfa_ranks", C.c_int)]
+
+
+class fr_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class fr_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("beta", C.c_float), ("gamma", C.c_float), ("prim", C.c_int32)]
+
+
+# fr_ray / fr_ray_hit as numpy record types (PathTracer.trace_rays)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmin", np.float32), ("dir", np.float32, 3), ("tmax", np.float32)])
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("prim", np.int32)])
 
 
 class fr_scene_arrays(C.Structure):
@@ -180,6 +196,10 @@ _SIGS = {
     "fr_update_geometry": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int],
     "fr_update_geometry_enqueue": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "fr_geometry_consumed": [C.c_void_p, C.c_void_p],
+    "fr_ray_query_reserve": [C.c_void_p, C.c_size_t],
+    "fr_trace_rays": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
+    "fr_trace_rays_enqueue": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p],
+    "fr_rays_consumed": [C.c_void_p, C.c_void_p],
     "fr_set_geometry_overlap": [C.c_void_p, C.c_int],
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_rebuild_bvh_enqueue": [C.c_void_p],
@@ -705,6 +725,66 @@ class PathTracer:
         the device for the last enqueued update's reads of the caller's arrays. Does not block the host."""
         s = getattr(stream, "cuda_stream", stream)
         self._check(_lib.fr_geometry_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
+
+    @staticmethod
+    def _ray_kind(kind):
+        if kind not in RAY_KINDS and kind not in RAY_KINDS.values():
+            raise ValueError(f"kind must be one of {sorted(RAY_KINDS)}")
+        return RAY_KINDS.get(kind, kind)
+
+    def ray_query_reserve(self, n):
+        """fr_ray_query_reserve: the staging area host batches of trace_rays go through, for n rays and results
+        (48 B per ray on the device; grows only). Waits for the context's pending work."""
+        self._check(_lib.fr_ray_query_reserve(self._ctx, int(n)))
+
+    def trace_rays(self, rays, kind="closest", out=None, n=None):
+        """fr_trace_rays: a batch of rays against the scene as it is now, waiting for the answers.
+        rays: a numpy array of n x 8 float32, rows (origin, tmin, dir, tmax), or RAY_DTYPE records; the answers come
+        back as numpy: RAY_HIT_DTYPE records (t, beta, gamma, prim; a miss is (inf, 0, 0, -1)) for "closest", n
+        float32 for "transmittance". The staging area is reserved on demand. Or rays: a device pointer or an object
+        with data_ptr() (n x 8 float32 on this context's device; n defaults to its numel() // 8), with `out` the
+        same kind of array for the answers (n x 16 B, or n floats); returns `out`."""
+        k = self._ray_kind(kind)
+        if isinstance(rays, np.ndarray):
+            a = np.ascontiguousarray(rays.view(np.float32) if rays.dtype == RAY_DTYPE else rays, dtype=np.float32)
+            a = a.reshape(-1, 8)
+            cnt = a.shape[0]
+            res = np.empty(cnt, RAY_HIT_DTYPE if k == FR_RAYS_CLOSEST else np.float32)
+            self.ray_query_reserve(cnt)  # (allocates only when the request grows)
+            self._check(_lib.fr_trace_rays(self._ctx, C.c_void_p(a.ctypes.data), cnt, FR_MEM_HOST, k,
+                                           C.c_void_p(res.ctypes.data)))
+            return res
+        if out is None:
+            raise ValueError("device rays need out, a device array for the answers")
+        if n is None:
+            n = rays.numel() // 8
+        self._check(_lib.fr_trace_rays(self._ctx, self._device_ptr(rays), int(n), FR_MEM_DEVICE, k,
+                                       self._device_ptr(out)))
+        return out
+
+    def trace_rays_enqueue(self, rays, out, n=None, kind="closest", ready_event=None):
+        """fr_trace_rays_enqueue: trace_rays over device arrays in stream order, without waiting for the GPU. The
+        query sees the scene as of this call's place among the enqueued updates, poses and rebuilds. rays, out: device
+        pointers or objects with data_ptr(); ready_event as in update_geometry_enqueue. Keep both arrays untouched
+        until rays_consumed() has ordered your stream behind the query."""
+        if n is None:
+            n = rays.numel() // 8
+        ev = getattr(ready_event, "cuda_event", ready_event)
+        self._check(_lib.fr_trace_rays_enqueue(self._ctx, self._device_ptr(rays), int(n), self._ray_kind(kind),
+                                               self._device_ptr(out), C.c_void_p(int(ev)) if ev else None))
+
+    def rays_consumed(self, stream=None):
+        """fr_rays_consumed: `stream` (a torch stream, a raw hipStream_t, or None for the null stream) waits on the
+        device for the last enqueued query: work submitted to it afterwards may read the answers and overwrite the
+        rays. Does not block the host."""
+        s = getattr(stream, "cuda_stream", stream)
+        self._check(_lib.fr_rays_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
+
+    def model_of(self, prims):
+        """The model index (the order of models()) of each triangle index; -1 for a miss (a negative index)."""
+        p = np.asarray(prims["prim"] if getattr(prims, "dtype", None) == RAY_HIT_DTYPE else prims).astype(np.int64)
+        first = np.array([m[1] for m in self.models()], np.int64)
+        return np.where(p < 0, -1, np.searchsorted(first, p, side="right") - 1).astype(np.int32)
 
     def set_geometry_overlap(self, on=True):
         """fr_set_geometry_overlap: enqueued updates and enqueued poses refit into a second tree and write second

@@ -597,6 +597,67 @@ int fr_geometry_consumed(fr_ctx* ctx, void* stream);
  * made the call. Not covered: groups and sharded contexts (their enqueued updates stay FR_E_UNSUPPORTED). */
 int fr_set_geometry_overlap(fr_ctx* ctx, int on);
 int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected);
+/* Ray queries: a caller's batch of rays against the scene, traced on the device by the traversal every other ray of
+ * the engine uses. rays: n records of 32 B; the direction need not be normalised, t is in units of its length, and
+ * tmax = +inf is allowed.
+ * FR_RAYS_CLOSEST (out: n fr_ray_hit records): the hit of the reference's intersect_triangle with the smallest t in
+ * the open interval (tmin, tmax), both ends strict; of equal t the lowest triangle index. prim is the scene's
+ * triangle index (the order of fr_scene_export and fr_model_info, not the tree's leaf order); t, beta and gamma are
+ * the bits of that triangle's own test. A miss is (t, beta, gamma, prim) = (+inf, 0, 0, -1): +inf, not the ray's tmax.
+ * FR_RAYS_TRANSMITTANCE (out: n floats): the engine's shadow ray (ray type 2) over (tmin, tmax): 0 at the first
+ * opaque triangle crossed; otherwise the product over every refractive triangle crossed of 1 - schlick(|n.d|, 5),
+ * kept in f64 and rounded to fp32 once (so the order of the crossings changes at most the last bit); 1 when nothing
+ * is crossed.
+ * Degenerate rays are answered without traversal, as a miss or transmittance 1: a NaN among the eight floats, an
+ * origin or a direction that is not finite, the direction (0, 0, 0), and tmin >= tmax.
+ * Where the closest hit equals brute force over every triangle, bit for bit. The tree culls by slab planes
+ * fma(lo, 1 / d, -o / d) against boxes inflated by 1e-5 + 4e-7 |v| per coordinate v. With u = 2^-24, 1 / d, o / d
+ * and the fma each round once: the computed distance is ((lo - o) / d) (1 + e0) (1 + e2) - (o / d) e1 (1 + e0) (1 + e2)
+ * with |e| <= u, off by at most (2 |lo - o| + |o|) u / |d_axis| to first order, which is a displacement of the plane
+ * along its axis of at most (2 |lo - o| + |o|) u. With every origin coordinate inside the scene box grown on each
+ * side by the box's longest edge L, and m the largest coordinate magnitude of the box, |o| <= m + L and
+ * |lo - o| <= 2 L, so the displacement is at most (m + 5 L) u = 6e-8 (m + 5 L): below the inflation's constant 1e-5
+ * while m + 5 L <= 160 units (the preset scenes: m = 10, L = 20, 6.6e-6), so a point of a triangle stays inside the
+ * computed slabs of every box around it with a third of the inflation to spare. The direction's length must lie in
+ * [1e-3, 1e3] so that no component of 1 / d or o / d leaves the normal range (2^100 stands for 1 / 0). That is as far
+ * as the argument goes: it bounds the planes, not the hit. A hit's own t carries its test's rounding, about
+ * 2^-22 (|n_x d_x| + |n_y d_y| + |n_z d_z|) / |n.d| of t, which grows at grazing incidence on triangles off the
+ * axes; the guarantee covers a hit while that error times t |d| stays below half the inflation at the hit point. The
+ * guaranteed domain is therefore narrower than "every ray from near the scene": a scene with m + 5 L <= 160, origins
+ * in the grown box, lengths in [1e-3, 1e3], and hits within that bound.
+ * Outside it the call still terminates (the tree is finite and every node is visited at most once) and every hit
+ * returned is a true one, the bits of that triangle's own test inside the window; a grazing hit may be culled.
+ * Which scene a query sees: tree, leaf triangles, primitive map, shading records and materials as of the call's
+ * place in the stream order, after every update, pose, refit and rebuild made or enqueued before the call and before
+ * every one after, in place and with fr_set_geometry_overlap on. A rebuild that failed or was skipped on the device
+ * and an update rejected there leave the scene, and so the answers, as before.
+ * fr_trace_rays waits for the context's pending work and for its own kernel. where (FR_MEM_HOST | FR_MEM_DEVICE)
+ * applies to both rays and out. Host arrays go through a staging area of max_rays rays and results, which
+ * fr_ray_query_reserve makes: it waits for pending work, allocates 48 B per ray at its first call and again only
+ * when the request grows (FR_E_NOMEM keeps what was there); a host batch above the reservation is FR_E_INVALID
+ * (fr_last_error names the reservation). Device arrays need no reservation. No query call allocates.
+ * fr_trace_rays_enqueue takes device arrays only and enqueues the query on the context stream without waiting for
+ * the GPU: it synchronises no stream and no event, copies nothing to the host and allocates nothing. ready_event is
+ * as in fr_update_geometry_enqueue. rays and out must stay untouched until fr_rays_consumed(ctx, stream) has made
+ * `stream` (a hipStream_t; 0 = the null stream) wait, on the device, for the last enqueued query's kernel: its reads
+ * of rays and its writes of out. Work submitted to that stream afterwards may read the results and overwrite the
+ * rays. It does not block the host; with no query enqueued it does nothing. The enqueued form joins no
+ * reconstruction and leaves the frame pipeline's schedule as it was.
+ * Refused at once, nothing enqueued, out untouched: a NULL context, NULL rays or out with n > 0, a bad kind or
+ * where, n > 2^30, a device pointer not 16-byte aligned (out of FR_RAYS_TRANSMITTANCE: 4-byte), rays and out
+ * overlapping (FR_E_INVALID); the enqueued form on a rank of a group or a sharded context (FR_E_UNSUPPORTED; the
+ * synchronous form works there). n == 0 is FR_OK and enqueues nothing.
+ * A query touches no image buffer, no temporal state, no counter of fr_stats: query rays are not counted, nothing of
+ * the JumpFlooding reuse, and no schedule of another context.
+ * Not covered: groups in stream order, per-ray masks, shading attributes of the hit (fr_scene_export has them). */
+typedef struct fr_ray     { float origin[3]; float tmin; float dir[3]; float tmax; } fr_ray;      /* 32 B */
+typedef struct fr_ray_hit { float t; float beta, gamma; int32_t prim; } fr_ray_hit;               /* 16 B */
+#define FR_RAYS_CLOSEST       0   /* out: n fr_ray_hit */
+#define FR_RAYS_TRANSMITTANCE 1   /* out: n floats */
+int fr_ray_query_reserve(fr_ctx* ctx, size_t max_rays);
+int fr_trace_rays(fr_ctx* ctx, const void* rays, size_t n, int where, int kind, void* out);
+int fr_trace_rays_enqueue(fr_ctx* ctx, const void* rays, size_t n, int kind, void* out, void* ready_event);
+int fr_rays_consumed(fr_ctx* ctx, void* stream);
 /* The scene's models, posed by matrix on the device. A scene is assembled from rigid models (ground, box, bunny,
  * earth, vokselia_spawn: PathTracer::load_obj's meshes with their transforms baked in), each a contiguous range of
  * the scene's triangles. The ranges partition [0, num_tris) in scene order: fr_model_count gives their number,

@@ -231,6 +231,43 @@ class PathTracer {
     }
     return out;
   }
+  // Ray queries (fr_trace_rays): a batch of rays against the scene as of the call's place in the stream order.
+  // The host forms reserve the staging area on demand and wait for the answers; a miss is (inf, 0, 0, -1).
+  void ray_query_reserve(size_t n) {
+    check(fr_ray_query_reserve(ctx(), n), ctx_, "ray_query_reserve");
+  }
+  std::vector<fr_ray_hit> trace_rays(const std::vector<fr_ray>& rays) {
+    std::vector<fr_ray_hit> out(rays.size());
+    ray_query_reserve(rays.size());  // (allocates only when the request grows)
+    check(fr_trace_rays(ctx(), rays.data(), rays.size(), FR_MEM_HOST, FR_RAYS_CLOSEST, out.data()), ctx_, "trace_rays");
+    return out;
+  }
+  std::vector<float> trace_transmittance(const std::vector<fr_ray>& rays) {
+    std::vector<float> out(rays.size());
+    ray_query_reserve(rays.size());  // (allocates only when the request grows)
+    check(fr_trace_rays(ctx(), rays.data(), rays.size(), FR_MEM_HOST, FR_RAYS_TRANSMITTANCE, out.data()), ctx_,
+          "trace_transmittance");
+    return out;
+  }
+  // device arrays (n fr_ray; n fr_ray_hit or n floats by kind), waiting for the answers
+  void trace_rays(const void* rays, size_t n, int kind, void* out) {
+    check(fr_trace_rays(ctx(), rays, n, FR_MEM_DEVICE, kind, out), ctx_, "trace_rays");
+  }
+  // ... and without waiting for the GPU; the arrays stay untouched until rays_consumed has ordered a stream (a
+  // hipStream_t; nullptr: the null stream) behind the query
+  void trace_rays_enqueue(const void* rays, size_t n, int kind, void* out, void* ready_event = nullptr) {
+    check(fr_trace_rays_enqueue(ctx(), rays, n, kind, out, ready_event), ctx_, "trace_rays_enqueue");
+  }
+  void rays_consumed(void* stream = nullptr) { check(fr_rays_consumed(ctx(), stream), ctx_, "rays_consumed"); }
+  // triangle indices (fr_ray_hit::prim) to model indices, the order of models(); -1 for a miss
+  std::vector<int> model_of(const std::vector<int32_t>& prims) {
+    const std::vector<Model> ms = models();
+    std::vector<int> out(prims.size(), -1);
+    for (size_t k = 0; k < prims.size(); k++)
+      for (size_t i = 0; i < ms.size(); i++)
+        if (prims[k] >= ms[i].first_tri && prims[k] < ms[i].first_tri + ms[i].ntris) out[k] = static_cast<int>(i);
+    return out;
+  }
   // Poses by matrix (fr_set_model_transforms): enable captures the current geometry as rest; m holds one row-major
   // 3 x 4 matrix per model (v' = A v + t over the rest geometry), posed on the device and taken as update_geometry
   // with given normals, or in stream order without waiting for the GPU (the enqueued form, always a refit).
