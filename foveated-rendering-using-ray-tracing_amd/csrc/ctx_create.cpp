@@ -238,16 +238,10 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   // in a rebuild cost ~10-20 ms and synchronise the device).
   {
     const size_t cap = (size_t)std::max(nt, 1);
-    if (hipMalloc((void**)&c->d_nodes, std::max(cap, c->bvh.nodes.size()) * sizeof(BvhNode)) != hipSuccess ||
-        hipMalloc((void**)&c->d_tri, cap * sizeof(TriGeo)) != hipSuccess ||
-        hipMalloc((void**)&c->d_prim, cap * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&c->spare_nodes, cap * sizeof(BvhNode)) != hipSuccess ||
-        hipMalloc((void**)&c->spare_tri, cap * sizeof(TriGeo)) != hipSuccess ||
-        hipMalloc((void**)&c->spare_prim, cap * sizeof(int32_t)) != hipSuccess) {
+    if (!fri::tree_alloc(&c->tree, std::max(cap, c->bvh.nodes.size()), cap) || !fri::tree_alloc(&c->spare, cap, cap)) {
       c->err = "device allocation (scene) failed";
       return bail(FR_E_NOMEM);
     }
-
     c->tree_full_cap = c->bvh.nodes.size() <= cap;
     std::string werr;
     if (nt >= 3 && !bvh_work_prepare(&c->bvh_work, nt, c->stream, werr)) { c->err = werr; return bail(FR_E_NOMEM); }
@@ -259,9 +253,9 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     }
   }
   if (cfg.bvh_builder == 0) {
-    if (hipMemcpy(c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_tri, c->bvh.tri_geo.data(), c->bvh.tri_geo.size() * sizeof(TriGeo), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_prim, c->bvh.tri_prim.data(), c->bvh.tri_prim.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(c->tree.nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->tree.tri, c->bvh.tri_geo.data(), c->bvh.tri_geo.size() * sizeof(TriGeo), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->tree.prim, c->bvh.tri_prim.data(), c->bvh.tri_prim.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
       c->err = "device copy (scene) failed";
       return bail(FR_E_HIP);
     }
@@ -289,7 +283,7 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronisation (scene) failed"; return bail(FR_E_HIP); }
   DevScene& d = c->dsc;
   memset(&d, 0, sizeof(d));
-  d.nodes = c->d_nodes; d.tri_geo = c->d_tri; d.tri_prim = c->d_prim; d.shade = c->d_shade;
+  fri::point_dsc(c);
   d.root_count = 0; d.num_tris = nt;
   c->d_tex.resize(s.texs.size(), nullptr);
   std::vector<DevTexture> htex(s.texs.size());
@@ -412,8 +406,8 @@ int fr_destroy(fr_ctx* c) {
   const hipStream_t streams[5] = {c->stream, c->atrous_stream, c->sibson_stream, c->carry_stream, c->front_stream};
   for (hipStream_t s : streams) if (s) hipStreamSynchronize(s);
   auto fr = [](void* p) { if (p) hipFree(p); };
-  fr(c->d_nodes); fr(c->d_tri); fr(c->d_prim); fr(c->d_shade); fr(c->d_pos);
-  fr(c->spare_nodes); fr(c->spare_tri); fr(c->spare_prim); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back);
+  fri::tree_free(&c->tree); fri::tree_free(&c->spare);
+  fr(c->d_shade); fr(c->d_pos); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back);
   fr(c->pose_rest_pos); fr(c->pose_rest_nrm); fr(c->pose_stage_pos); fr(c->pose_stage_nrm);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   if (c->sah_work) sah_work_free(c->sah_work);

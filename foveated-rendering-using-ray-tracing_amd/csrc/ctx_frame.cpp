@@ -130,7 +130,7 @@ static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
   c->moved = false;
   c->compacted = false;
   // (a G-buffer on front_stream is ordered before an overlapped update by the stream itself)
-  if (c->overlap_on && fs == c->stream) c->set_read[c->set_cur].record(c->stream);
+  if (fs == c->stream) mark_set_read(c);
   return check_launch(c);
 }
 
@@ -226,7 +226,7 @@ int fri::enqueue_shading(fr_ctx* c) {
   c->trace_done[c->slot].record(c->stream);
   // overlapped updates: the megakernel was the last reader of the scene's tree and normals; the update after the
   // next one writes them (fr_set_geometry_overlap)
-  if (c->overlap_on) c->set_read[c->set_cur].record(c->stream);
+  mark_set_read(c);
   int rc = check_launch(c);
   // swapBuffer("history_cache", "history_buffer"); swapBuffer("depth_cache", "depth_buffer") (:226-227)
   std::swap(c->hist_cur, c->hist_cache);
@@ -426,6 +426,11 @@ static int wait_for_previous_frame(fr_ctx* c, int prev) {
   return FR_OK;
 }
 
+void fri::stream_join(fr_ctx* c, hipStream_t waiter) {
+  hipEventRecord(c->ev_stream_join, c->stream);
+  hipStreamWaitEvent(waiter, c->ev_stream_join, 0);
+}
+
 // Frame halves: the trace half (update -> entries 0..3) and the reconstruction half (JFA -> SI ->
 // PPI -> AT). fr_frame runs both; a tile-sharded view runs the trace half on every rank and the
 // reconstruction half on the rank that composites (after fr_shard_unpack of the other ranks' tiles).
@@ -456,12 +461,9 @@ int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
     const bool latency = !t && c->pipeline_mode == FR_PIPELINE_LATENCY;
     const int prev = c->slot;  // the previous frame's slot
     if (latency && (rc = wait_for_previous_frame(c, prev))) return rc;
-    if (!t && c->stream_dirty) {
-      // the front stages overwrite buffers (gclass, DIFFUSE, EXTRA, depth, ballots, counts, lp_cache) that
-      // work enqueued on `stream` by other calls may still read: order them after it explicitly
-      hipEventRecord(c->ev_stream_join, c->stream);
-      hipStreamWaitEvent(fs, c->ev_stream_join, 0);
-    }
+    // the front stages overwrite buffers (gclass, DIFFUSE, EXTRA, depth, ballots, counts, lp_cache) that
+    // work enqueued on `stream` by other calls may still read: order them after it explicitly
+    if (!t && c->stream_dirty) stream_join(c, fs);
     c->stream_dirty = false;
     c->fc_arm = c->fc_on && recon;  // whole frames only (a group's trace half has no end of its own)
     c->lat.arm = latency && recon;

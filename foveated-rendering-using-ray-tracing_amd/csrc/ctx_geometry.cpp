@@ -1,6 +1,7 @@
 // ctx_geometry.cpp — the scene's geometry after fr_create: the tree (GPU rebuild, refit, SAH cost), position and
-// normal updates (synchronous; in stream order, in place or overlapped into a second set), the model table and poses
-// by matrix, the switches of motion reprojection and of overlapped updates, and the scene export calls.
+// normal updates (synchronous; in stream order, in place or overlapped into a second set), the models' poses by
+// matrix, and the switches of motion reprojection and of overlapped updates. (The scene's description on the host, the
+// model table and fr_scene_export among it: ctx_scene.cpp.)
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -10,18 +11,38 @@
 using namespace fr;
 using namespace fri;
 
+bool fri::tree_alloc(TreeArrays* t, size_t node_cap, size_t tri_cap) {
+  if (hipMalloc((void**)&t->nodes, node_cap * sizeof(BvhNode)) == hipSuccess &&
+      hipMalloc((void**)&t->tri, tri_cap * sizeof(TriGeo)) == hipSuccess &&
+      hipMalloc((void**)&t->prim, tri_cap * sizeof(int32_t)) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  tree_free(t);
+  return false;
+}
+
+void fri::tree_free(TreeArrays* t) {
+  for (void* p : {(void*)t->nodes, (void*)t->tri, (void*)t->prim})
+    if (p) hipFree(p);
+  *t = TreeArrays{};
+}
+
+void fri::adopt_spare(fr_ctx* c, bool with_shade) {
+  std::swap(c->tree, c->spare);
+  if (with_shade) {
+    std::swap(c->d_shade, c->shade_back);
+    c->set_cur ^= 1;
+  }
+  point_dsc(c);
+}
+
 // GPU build over `pos` (device; k_bvh.hip) into the spare arrays, which become the scene's tree when every
 // step succeeded (the old tree becomes the spare). No allocation after the first rebuild, no read-back
 // of the tree: the host keeps its node count, stack need and depth (fr_scene_export).
 int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   const int nt = c->scene.num_tris();
   const size_t cap = (size_t)std::max(nt, 1);
-  auto alloc_spare = [&] {
-    return hipMalloc((void**)&c->spare_nodes, cap * sizeof(BvhNode)) == hipSuccess &&
-           hipMalloc((void**)&c->spare_tri, cap * sizeof(TriGeo)) == hipSuccess &&
-           hipMalloc((void**)&c->spare_prim, cap * sizeof(int32_t)) == hipSuccess;
-  };
-  if (!c->spare_nodes && !alloc_spare()) {  // (a failed re-allocation below left none)
+  if (!c->spare.nodes && !tree_alloc(&c->spare, cap, cap)) {  // (a failed re-allocation below left none)
     c->err = "GPU BVH: device allocation failed";
     return FR_E_NOMEM;
   }
@@ -29,10 +50,10 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   std::string err;
   // the context's builder: the LBVH, or on a bvh_builder 2 context the binned SAH of k_bvh_sah.hip
   bool unsupported = false;
-  if (c->cfg.bvh_builder == 2 ? !gpu_build_bvh_sah(c->sah_work, c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri,
-                                                   c->spare_prim, &nn, &max_stack, &depth, &unsupported, c->stream, err)
-                              : !gpu_build_bvh(&c->bvh_work, pos, nt, c->spare_nodes, c->spare_tri, c->spare_prim, &nn,
-                                               &max_stack, &depth, c->stream, err)) {
+  if (c->cfg.bvh_builder == 2
+          ? !gpu_build_bvh_sah(c->sah_work, c->bvh_work, pos, nt, c->spare, &nn, &max_stack, &depth, &unsupported,
+                               c->stream, err)
+          : !gpu_build_bvh(&c->bvh_work, pos, nt, c->spare, &nn, &max_stack, &depth, c->stream, err)) {
     c->err = err;
     return unsupported ? FR_E_UNSUPPORTED : FR_E_HIP;
   }
@@ -40,22 +61,16 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
     c->err = "GPU BVH needs a traversal stack deeper than FR_BVH_STACK";
     return FR_E_UNSUPPORTED;
   }
-  std::swap(c->d_nodes, c->spare_nodes);
-  std::swap(c->d_tri, c->spare_tri);
-  std::swap(c->d_prim, c->spare_prim);
+  adopt_spare(c, false);
   if (!c->tree_full_cap) {
     // the replaced tree was sized for the host builder's node count (or there was none): the next spare
     // needs room for any device-built tree (at most one node per triangle)
-    if (c->spare_nodes) { hipFree(c->spare_nodes); hipFree(c->spare_tri); hipFree(c->spare_prim); }
-    c->spare_nodes = nullptr; c->spare_tri = nullptr; c->spare_prim = nullptr;
+    tree_free(&c->spare);
     c->tree_full_cap = true;
-    if (!alloc_spare()) {
-      hipFree(c->spare_nodes); hipFree(c->spare_tri); hipFree(c->spare_prim);
-      c->spare_nodes = nullptr; c->spare_tri = nullptr; c->spare_prim = nullptr;  // allocated again next time
-      c->overlap_on = false;  // (no second tree: updates are in place until fr_set_geometry_overlap makes one)
-    }
+    // (a failure leaves no spare: allocated again next time; and no second tree: updates are in place until
+    // fr_set_geometry_overlap makes one)
+    if (!tree_alloc(&c->spare, cap, cap)) c->overlap_on = false;
   }
-  c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim;
   Bvh b;
   b.root_count = 0; b.max_stack = max_stack; b.max_depth = depth;
   b.gpu_nodes = nn;
@@ -66,27 +81,31 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
   return FR_OK;
 }
 
-// The numbers of the tree an enqueued rebuild left, from the pinned copy of the record (the caller has waited).
-static void take_tree_numbers(fr_ctx* c) {
+// A device record behind the context's pending work, in its pinned copy (a wait).
+static int fetch_record(fr_ctx* c, void* pinned, const void* dev, size_t bytes) {
+  join_recon(c);
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, hipMemcpyAsync(pinned, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FR_OK;
+}
+
+// The record of enqueued rebuilds, and with it the numbers of the tree an enqueued rebuild left, if the host has not
+// seen them.
+static int fetch_rebuild_record(fr_ctx* c) {
+  if (int rc = fetch_record(c, c->h_rb, c->rb, sizeof(fr::RebuildState))) return rc;
+  if (!c->tree_on_device) return FR_OK;
   const fr::TreeDesc& d = c->h_rb->tree[c->desc_cur];
   c->bvh.gpu_nodes = (int)d.nodes;
   c->bvh.max_stack = (int)d.max_stack;
   c->bvh.max_depth = (int)d.depth;
   c->tree_on_device = false;
+  return FR_OK;
 }
 
 int fri::tree_numbers(fr_ctx* c) {
   if (!c->tree_on_device) return FR_OK;
-  join_recon(c);
-  hipSetDevice(c->cfg.device);
-  HIP_TRY(c, hipMemcpyAsync(c->h_rb, c->rb, sizeof(fr::RebuildState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  take_tree_numbers(c);
-  return FR_OK;
-}
-
-static int tree_nodes(const Bvh& b) {
-  return b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size();
+  return fetch_rebuild_record(c);
 }
 
 // Refit of the tree in use (either builder's) over `pos` (device), in place (k_bvh.hip). The caller has joined
@@ -95,7 +114,7 @@ static int gpu_refit(fr_ctx* c, const f3* pos) {
   if (int rc = tree_numbers(c)) return rc;
   std::string err;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
-  if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->d_nodes, nn, c->d_tri, c->d_prim, c->stream, err)) {
+  if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->tree, nn, c->stream, err)) {
     c->err = err;
     return c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED;
   }
@@ -127,12 +146,11 @@ int fr_bvh_sah_cost(fr_ctx* c, float* cost) {
   join_recon(c);
   hipSetDevice(c->cfg.device);
   std::string err;
-  if (!gpu_bvh_cost(c->bvh_work, c->d_nodes, tree_nodes(c->bvh), cost, c->stream, err))
+  if (!gpu_bvh_cost(c->bvh_work, c->tree.nodes, tree_nodes(c->bvh), cost, c->stream, err))
     return fail(c, c->bvh_work ? FR_E_HIP : FR_E_UNSUPPORTED, err);
   return FR_OK;
 }
 
-static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
 // A caller's host normals: finite on every triangle that has normals (the others are ignored).
 static bool host_normals_finite(const fr_ctx* c, const float* nrm) {
   const HostScene& s = c->scene;
@@ -243,10 +261,7 @@ static int update_positions(fr_ctx* c, const void* xyz, size_t ntris, int where,
   if (where == FR_MEM_HOST) {
     memcpy(c->scene.pos.data(), xyz, bytes);
     c->pos_mirror_stale = false;
-    for (const f3& v : c->scene.pos) {
-      lo = mk3(fminf(lo.x, v.x), fminf(lo.y, v.y), fminf(lo.z, v.z));
-      hi = mk3(fmaxf(hi.x, v.x), fmaxf(hi.y, v.y), fmaxf(hi.z, v.z));
-    }
+    box_of(c->scene.pos.data(), c->scene.pos.size(), &lo, &hi);
   } else {
     c->pos_mirror_stale = true;  // refreshed by the next fr_scene_export
   }
@@ -287,12 +302,13 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
   return update_positions(c, xyz, ntris, where, how, "fr_update_geometry", nrm, normals);
 }
 
-// fr_update_geometry (device memory, refit) in stream order: every launch below goes on one stream and nothing
-// here waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no synchronisation, no copy to the
-// host, no allocation). What the host learnt from the device in update_positions stays there: the verdict of
-// the two checks is a device word that k_take_over publishes and every later kernel of the update reads, and the
-// scene box goes from the check's result into geo->box, where the saliency stage reads it from now on.
-// The three position arrays rotate here, at enqueue time and whatever the verdict, exactly as in update_positions;
+// fr_update_geometry (device memory, refit) in stream order (enqueue_update, below): every launch there goes on one
+// stream, GeoEnqueue's, and nothing waits for the GPU (the enqueue halves of k_bvh.hip / k_normals.hip; no
+// synchronisation, no copy to the host, no allocation). What the host learnt from the device in update_positions
+// stays there: the verdict of the two checks is a device word that k_take_over publishes and every later kernel of
+// the update reads, and the scene box goes from the check's result into geo->box, where the saliency stage reads it
+// from now on.
+// The three position arrays rotate there, at enqueue time and whatever the verdict, exactly as in update_positions;
 // their contents follow in stream order (k_take_over fills the array that becomes d_pos with the caller's
 // positions, or with the current ones when the update is rejected).
 // In place (the default), the stream is the context stream. That is safe because every reader and writer
@@ -301,7 +317,7 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 // update is enqueued behind it, and the next frame's front stages wait for the context stream (stream_dirty).
 // The reconstruction streams read none of it, so they are not joined.
 // Overlapped (fr_set_geometry_overlap), the stream is front_stream, and tree and normals are written out of place,
-// into the set no frame in flight reads, which becomes the scene's here (a swap, and dsc's pointers). The hazards:
+// into the set no frame in flight reads, which becomes the scene's there (adopt_spare). The hazards:
 //  - the set written was the scene's until the previous update: its last reader on the context stream is a
 //    megakernel (or a G-buffer there), whose fence front_stream waits for (set_read); the G-buffers of pipelined
 //    frames, the only other readers of it and of the position arrays, are earlier work of front_stream itself;
@@ -322,7 +338,7 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 // and in both modes builds out of place, into the spare tree arrays, which the host makes the scene's at enqueue time:
 //  - in place (context stream): the spare arrays' last readers are frames enqueued before the rebuild that retired
 //    them; their entry 3 is earlier work of the context stream and waited for their front stages (front_done, consumed
-//    here as above), and later front stages wait for the context stream (stream_dirty). Shading records and set_cur
+//    by GeoEnqueue), and later front stages wait for the context stream (stream_dirty). Shading records and set_cur
 //    stay: only the tree's pointers change, as in fr_rebuild_bvh;
 //  - overlapped (front_stream): the set written is the one the fences above guard (set_read of the other set,
 //    ev_stream_join), its shading records are brought along by gpu_normals_to_enqueue's copy, and tree and records
@@ -335,6 +351,28 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 //    order (nodes_dev); a host reader waits and fetches them (tree_numbers); a frame needs none of them;
 //  - a build that fails on the device reads the tree in use (the source of its last kernel's copy), which the
 //    previous update or rebuild wrote earlier on this stream.
+// The preamble of both (the caller has set the device): the stream, and the waits the notes above name.
+struct GeoEnqueue {
+  fr_ctx* c;
+  const bool overlap;
+  const hipStream_t s;
+  explicit GeoEnqueue(fr_ctx* c_) : c(c_), overlap(c_->overlap_on), s(overlap ? c_->front_stream : c_->stream) {
+    if (overlap) {
+      if (c->stream_dirty) {
+        stream_join(c, s);
+        c->stream_dirty = false;  // the next frame's front stages follow this work on front_stream
+      }
+      c->set_read[c->set_cur ^ 1].consume(s);
+    } else {
+      c->stream_dirty = true;  // the next pipelined frame's front stages (front_stream) start after this work
+      // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before it as well)
+      c->front_done.consume(c->stream);
+    }
+  }
+  // whatever was enqueued of overlapped work, the context stream's next work outside a frame waits for it
+  ~GeoEnqueue() { if (overlap) c->update_done.record(c->front_stream); }
+};
+
 static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, const void* nrm, size_t ntris, int normals,
                           void* ready_event, const fr::PoseArgs* pose = nullptr) {
   if (!xyz) return fail(c, FR_E_INVALID, name + ": positions are NULL");
@@ -344,26 +382,9 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
                                          (pose ? "fr_set_model_transforms)" : "fr_update_geometry)"));
   if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
   hipSetDevice(c->cfg.device);
-  const bool overlap = c->overlap_on;
-  const hipStream_t s = overlap ? c->front_stream : c->stream;
-  // whatever was enqueued of an overlapped update, the context stream's next work outside a frame waits for it
-  struct Done {
-    fr_ctx* c;
-    bool on;
-    ~Done() { if (on) c->update_done.record(c->front_stream); }
-  } done{c, overlap};
-  if (overlap) {
-    if (c->stream_dirty) {
-      hipEventRecord(c->ev_stream_join, c->stream);
-      hipStreamWaitEvent(s, c->ev_stream_join, 0);
-      c->stream_dirty = false;  // the next frame's front stages follow this update on front_stream
-    }
-    c->set_read[c->set_cur ^ 1].consume(s);
-  } else {
-    c->stream_dirty = true;  // the next pipelined frame's front stages (front_stream) start after this update
-    // (front stages whose entry 3 was never enqueued, after a failed frame: ordered before the update as well)
-    c->front_done.consume(c->stream);
-  }
+  const GeoEnqueue g(c);
+  const bool overlap = g.overlap;
+  const hipStream_t s = g.s;
   if (ready_event) HIP_TRY(c, hipStreamWaitEvent(s, static_cast<hipEvent_t>(ready_event), 0));
   const int nt = (int)ntris;
   std::string err;
@@ -387,10 +408,8 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
   // (behind an enqueued rebuild the host's count is stale: the refit takes the tree's from its device record)
   const uint32_t* nn_dev = c->tree_on_device ? &c->rb->tree[c->desc_cur].nodes : nullptr;
-  if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim,
-                                          c->spare_nodes, c->spare_tri, c->spare_prim, reject, nn_dev, s, err)
-              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->d_nodes, nn, c->d_tri, c->d_prim, reject, nn_dev,
-                                       s, err))
+  if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, c->spare_pos, nt, c->tree, nn, c->spare, reject, nn_dev, s, err)
+              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->tree, nn, reject, nn_dev, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   rotate_positions(c);
   c->pos_mirror_stale = true;
@@ -409,14 +428,7 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
   }
   if (given) HIP_TRY(c, c->geo_read.record(s));  // nrm has been read as well
   if (given || recompute) c->nrm_mirror_stale = true;
-  if (overlap) {
-    std::swap(c->d_nodes, c->spare_nodes);
-    std::swap(c->d_tri, c->spare_tri);
-    std::swap(c->d_prim, c->spare_prim);
-    std::swap(c->d_shade, c->shade_back);
-    c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim; c->dsc.shade = c->d_shade;
-    c->set_cur ^= 1;
-  }
+  if (overlap) adopt_spare(c, true);
   return FR_OK;
 }
 
@@ -436,10 +448,7 @@ int fr_geometry_consumed(fr_ctx* c, void* stream) {
 
 int fr_geometry_update_status(fr_ctx* c, uint64_t* applied, uint64_t* rejected) {
   if (!c) return FR_E_INVALID;
-  join_recon(c);
-  hipSetDevice(c->cfg.device);
-  HIP_TRY(c, hipMemcpyAsync(c->h_geo, c->geo, sizeof(fr::GeoUpdateState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = fetch_record(c, c->h_geo, c->geo, sizeof(fr::GeoUpdateState))) return rc;
   const fr::GeoUpdateState& g = *c->h_geo;
   if (applied) *applied = g.applied;
   if (rejected) *rejected = g.rejected;
@@ -462,7 +471,7 @@ static int check_rebuild_state(fr_ctx* c, const std::string& name) {
   const int nt = c->scene.num_tris();
   if (nt < 3) return fail(c, FR_E_HIP, name + ": GPU BVH builder needs at least 3 triangles");
   const bool sah = c->cfg.bvh_builder == 2;
-  if (!c->tree_full_cap || !c->spare_nodes || (!c->tree_on_device && c->bvh.gpu_nodes < 0) || !c->bvh_work || !c->rb ||
+  if (!c->tree_full_cap || !c->spare.nodes || (!c->tree_on_device && c->bvh.gpu_nodes < 0) || !c->bvh_work || !c->rb ||
       !c->geo || (sah && !c->sah_work) || (c->overlap_on && !c->shade_back))
     return fail(c, FR_E_STATE, name + ": the tree in use is not yet a device-built one with a spare set beside it "
                                       "(call fr_rebuild_bvh once first; this call allocates nothing)");
@@ -474,9 +483,9 @@ static int check_ratio(fr_ctx* c, const std::string& name, float ratio) {
 }
 
 // fr_rebuild_bvh in stream order: the context's builder on its fixed launch schedule (gpu_build_bvh_enqueue,
-// gpu_build_bvh_sah_enqueue), on the stream enqueue_update would use and behind the same fences; see the notes above
-// it. The build goes into the spare tree arrays, which become the scene's here, whatever the verdict (a failed build
-// ends with the tree in use copied over them, whole). Nothing waits, nothing is copied to the host, nothing is
+// gpu_build_bvh_sah_enqueue), on the stream enqueue_update would use and behind the same fences: GeoEnqueue and the
+// notes above it. The build goes into the spare tree arrays, which become the scene's here, whatever the verdict (a failed
+// build ends with the tree in use copied over them, whole). Nothing waits, nothing is copied to the host, nothing is
 // allocated: the new tree's numbers are the device record's until a host reader asks (tree_numbers).
 // ratio: NULL, or the condition of fr_rebuild_bvh_enqueue_if (checked by the caller). The conditional form puts the
 // decision ahead of the schedule and the new tree's cost behind it, on the same stream: the cost's scratch is the
@@ -487,36 +496,21 @@ static int enqueue_rebuild(fr_ctx* c, const std::string& name, const float* rati
   const int nt = c->scene.num_tris();
   const bool sah = c->cfg.bvh_builder == 2;
   hipSetDevice(c->cfg.device);
-  const bool overlap = c->overlap_on;
-  const hipStream_t s = overlap ? c->front_stream : c->stream;
-  struct Done {
-    fr_ctx* c;
-    bool on;
-    ~Done() { if (on) c->update_done.record(c->front_stream); }
-  } done{c, overlap};
-  if (overlap) {
-    if (c->stream_dirty) {
-      hipEventRecord(c->ev_stream_join, c->stream);
-      hipStreamWaitEvent(s, c->ev_stream_join, 0);
-      c->stream_dirty = false;
-    }
-    c->set_read[c->set_cur ^ 1].consume(s);
-  } else {
-    c->stream_dirty = true;
-    c->front_done.consume(c->stream);
-  }
+  const GeoEnqueue g(c);
+  const bool overlap = g.overlap;
+  const hipStream_t s = g.s;
   fr::RebuildTarget t{};
   t.rs = c->rb;
-  t.nodes = c->spare_nodes; t.tri = c->spare_tri; t.prim = c->spare_prim;
+  t.dst = c->spare;
   t.desc = &c->rb->tree[c->desc_cur ^ 1];
-  t.src_nodes = c->d_nodes; t.src_tri = c->d_tri; t.src_prim = c->d_prim;
+  t.src = c->tree;
   t.src_host_nodes = c->tree_on_device ? -1 : tree_nodes(c->bvh);
   t.src_host_desc = fr::TreeDesc{(uint32_t)std::max(t.src_host_nodes, 0), (uint32_t)c->bvh.max_stack,
                                  (uint32_t)c->bvh.max_depth, 0u};
   t.src_desc = &c->rb->tree[c->desc_cur];
   t.conditional = ratio ? 1 : 0;
   std::string err;
-  if (ratio && !gpu_rebuild_decide_enqueue(c->bvh_work, c->rb, c->d_nodes, std::max(t.src_host_nodes, 0), nt,
+  if (ratio && !gpu_rebuild_decide_enqueue(c->bvh_work, c->rb, c->tree.nodes, std::max(t.src_host_nodes, 0), nt,
                                            c->tree_on_device ? &t.src_desc->nodes : nullptr, *ratio, c->base_stale, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   if (sah ? !gpu_build_bvh_sah_enqueue(c->sah_work, c->bvh_work, c->d_pos, nt, t, s, err)
@@ -527,15 +521,7 @@ static int enqueue_rebuild(fr_ctx* c, const std::string& name, const float* rati
   // (overlapped: the other set's shading records are an update old; the tree's verdict does not touch them)
   if (overlap && !gpu_normals_to_enqueue(c->nrm_work, nullptr, nullptr, c->d_shade, c->shade_back, &c->geo->reject, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
-  std::swap(c->d_nodes, c->spare_nodes);
-  std::swap(c->d_tri, c->spare_tri);
-  std::swap(c->d_prim, c->spare_prim);
-  c->dsc.nodes = c->d_nodes; c->dsc.tri_geo = c->d_tri; c->dsc.tri_prim = c->d_prim;
-  if (overlap) {
-    std::swap(c->d_shade, c->shade_back);
-    c->dsc.shade = c->d_shade;
-    c->set_cur ^= 1;
-  }
+  adopt_spare(c, overlap);
   c->desc_cur ^= 1;
   c->bvh.root_count = 0;
   c->tree_on_device = true;
@@ -579,16 +565,6 @@ static int policy_after_update(fr_ctx* c) {
   return enqueue_rebuild(c, "fr_set_rebuild_policy (the update is enqueued; the rebuild it owes)", &c->policy_ratio);
 }
 
-// The record of enqueued rebuilds, behind the context's pending work, in its pinned copy (a wait).
-static int fetch_rebuild_record(fr_ctx* c) {
-  join_recon(c);
-  hipSetDevice(c->cfg.device);
-  HIP_TRY(c, hipMemcpyAsync(c->h_rb, c->rb, sizeof(fr::RebuildState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->tree_on_device) take_tree_numbers(c);
-  return FR_OK;
-}
-
 extern "C" {
 
 int fr_bvh_rebuild_policy_status(fr_ctx* c, uint64_t* evaluated, uint64_t* skipped, float* last_cost, float* base_cost) {
@@ -623,29 +599,7 @@ int fr_bvh_rebuild_status(fr_ctx* c, uint64_t* built, uint64_t* failed) {
   return FR_OK;
 }
 
-// Model poses. The models are the contiguous triangle ranges add_mesh recorded (scene.cpp), in scene order.
-static int model_info(const HostScene& s, int i, const char** name, int* first_tri, int* ntris) {
-  if (i < 0 || i >= (int)s.model_tri_count.size()) return FR_E_INVALID;
-  int first = 0;
-  for (int k = 0; k < i; k++) first += s.model_tri_count[k];
-  if (name) *name = s.model_names[i].c_str();
-  if (first_tri) *first_tri = first;
-  if (ntris) *ntris = s.model_tri_count[i];
-  return FR_OK;
-}
-
-int fr_model_count(fr_ctx* c, int* n) {
-  if (!c || !n) return FR_E_INVALID;
-  *n = (int)c->scene.model_tri_count.size();
-  return FR_OK;
-}
-
-int fr_model_info(fr_ctx* c, int i, const char** name, int* first_tri, int* ntris) {
-  if (!c) return FR_E_INVALID;
-  if (model_info(c->scene, i, name, first_tri, ntris)) return fail(c, FR_E_INVALID, "fr_model_info: no such model");
-  return FR_OK;
-}
-
+// Model poses (the models themselves: model_info, ctx_scene.cpp).
 static_assert(FR_MAX_MODELS == FR_POSE_MAX_MODELS, "k_pose's kernel arguments hold FR_MAX_MODELS models");
 
 int fr_model_pose_enable(fr_ctx* c, int on) {
@@ -752,30 +706,23 @@ static int make_second_set(fr_ctx* c, const std::string& name) {
   if (int rc = tree_numbers(c)) return rc;
   const size_t nt = (size_t)c->scene.num_tris(), cap = std::max<size_t>(nt, 1), nn = (size_t)tree_nodes(c->bvh);
   const bool first = !c->shade_back;
-  const bool tree = !c->spare_nodes || (first && nn > cap);
-  BvhNode* nodes = nullptr;
-  TriGeo* tri = nullptr;
-  int32_t* prim = nullptr;
+  const bool tree = !c->spare.nodes || (first && nn > cap);
+  TreeArrays made;
   TriShade* shade = nullptr;
-  bool ok = true;
-  if (tree)
-    ok = hipMalloc((void**)&nodes, std::max(cap, nn) * sizeof(BvhNode)) == hipSuccess &&
-         hipMalloc((void**)&tri, cap * sizeof(TriGeo)) == hipSuccess &&
-         hipMalloc((void**)&prim, cap * sizeof(int32_t)) == hipSuccess;
+  bool ok = !tree || tree_alloc(&made, std::max(cap, nn), cap);
   if (ok && first)
     ok = dalloc(&shade, cap) == hipSuccess &&
          hipMemcpyAsync(shade, c->d_shade, nt * sizeof(TriShade), hipMemcpyDeviceToDevice, c->stream) == hipSuccess &&
          hipStreamSynchronize(c->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    for (void* p : {(void*)nodes, (void*)tri, (void*)prim, (void*)shade})
-      if (p) hipFree(p);
+    tree_free(&made);
+    if (shade) hipFree(shade);
     return fail(c, FR_E_NOMEM, name + ": device allocation (second tree and normals) failed");
   }
   if (tree) {
-    for (void* p : {(void*)c->spare_nodes, (void*)c->spare_tri, (void*)c->spare_prim})
-      if (p) hipFree(p);
-    c->spare_nodes = nodes; c->spare_tri = tri; c->spare_prim = prim;
+    tree_free(&c->spare);
+    c->spare = made;
   }
   if (first) c->shade_back = shade;
   return FR_OK;
@@ -815,22 +762,6 @@ int fr_recompute_normals(fr_ctx* c, float* ms) {
   return host_timed(c, ms, [&] { return recompute_normals(c, "fr_recompute_normals"); });
 }
 
-static int copy_groups(const NormalGroups& g, int32_t* corner_vertex, size_t ncorners, int* nverts) {
-  if (corner_vertex) {
-    if (ncorners != g.corner_vertex.size()) return FR_E_INVALID;
-    memcpy(corner_vertex, g.corner_vertex.data(), ncorners * sizeof(int32_t));
-  }
-  if (nverts) *nverts = g.num_verts;
-  return FR_OK;
-}
-
-int fr_normal_groups(fr_ctx* c, int32_t* corner_vertex, size_t ncorners, int* nverts) {
-  if (!c) return FR_E_INVALID;
-  if (copy_groups(c->groups, corner_vertex, ncorners, nverts))
-    return fail(c, FR_E_INVALID, "fr_normal_groups: ncorners is not 3 per triangle");
-  return FR_OK;
-}
-
 // Test hook (not part of include/fovrt.h): the tree in use, whichever builder made it, copied to the host:
 // fr_scene_export's bvh_nodes BvhNode, then num_tris TriGeo and num_tris leaf-order primitive indices.
 int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size_t tri_bytes, int32_t* prim,
@@ -843,9 +774,9 @@ int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size
   if (nodes_bytes < nn * sizeof(BvhNode) || tri_bytes < nt * sizeof(TriGeo) || prim_bytes < nt * sizeof(int32_t))
     return fail(c, FR_E_INVALID, "fr__bvh_read: buffer too small");
   if (int rc = quiesce(c)) return rc;
-  HIP_TRY(c, hipMemcpy(nodes, c->d_nodes, nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(tri_geo, c->d_tri, nt * sizeof(TriGeo), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(prim, c->d_prim, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(nodes, c->tree.nodes, nn * sizeof(BvhNode), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(tri_geo, c->tree.tri, nt * sizeof(TriGeo), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(prim, c->tree.prim, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
   return FR_OK;
 }
 
@@ -853,168 +784,8 @@ int fr__bvh_read(fr_ctx* c, void* nodes, size_t nodes_bytes, void* tri_geo, size
 // now reads them there). No wait.
 int fr__scene_addresses(fr_ctx* c, const void** nodes, const void** shade) {
   if (!c || !nodes || !shade) return FR_E_INVALID;
-  *nodes = c->d_nodes;
+  *nodes = c->tree.nodes;
   *shade = c->d_shade;
-  return FR_OK;
-}
-
-}  // extern "C"
-
-struct fr_scene {
-  HostScene scene;
-  Bvh bvh;
-  NormalGroups groups;
-  std::string err;
-  std::vector<const float*> tex_ptrs;
-  std::vector<int32_t> tex_dims, mat_pairs;
-};
-
-static void fill_arrays(const HostScene& s, const Bvh& bvh, f3 emission, std::vector<int32_t>& mat_pairs,
-                        std::vector<int32_t>& tex_dims, std::vector<const float*>& tex_ptrs, fr_scene_arrays* o) {
-  memset(o, 0, sizeof(*o));
-  o->num_tris = s.num_tris();
-  o->pos = &s.pos[0].x; o->nrm = &s.nrm[0].x; o->uv = &s.uv[0].x; o->flags = s.flags.data();
-  mat_pairs.clear();
-  for (auto& m : s.mats) { mat_pairs.push_back(m.type); mat_pairs.push_back(m.tex); }
-  o->num_materials = (int)s.mats.size();
-  o->materials = mat_pairs.data();
-  tex_dims.clear(); tex_ptrs.clear();
-  for (auto& t : s.texs) { tex_dims.push_back(t.w); tex_dims.push_back(t.h); tex_ptrs.push_back(&t.data[0].x); }
-  o->num_textures = (int)s.texs.size();
-  o->tex_dims = tex_dims.data();
-  o->tex_data = tex_ptrs.data();
-  o->envmap = s.envmap;
-  const f3 L[5] = {s.light_position, s.light_v1, s.light_v2, s.light_normal, emission};
-  for (int i = 0; i < 5; i++) { o->light[3 * i] = L[i].x; o->light[3 * i + 1] = L[i].y; o->light[3 * i + 2] = L[i].z; }
-  o->bbox[0] = s.bbox_min.x; o->bbox[1] = s.bbox_min.y; o->bbox[2] = s.bbox_min.z;
-  o->bbox[3] = s.bbox_max.x; o->bbox[4] = s.bbox_max.y; o->bbox[5] = s.bbox_max.z;
-  o->bvh_nodes = tree_nodes(bvh);
-  o->bvh_depth = bvh.max_depth;
-  o->bvh_max_stack = bvh.max_stack;
-}
-
-extern "C" {
-
-int fr_scene_export(fr_ctx* c, fr_scene_arrays* o) {
-  if (!c || !o) return FR_E_INVALID;
-  if (int rc = tree_numbers(c)) return rc;
-  if (c->geo_read.pending && (c->pos_mirror_stale || c->box_mirror_stale || c->nrm_mirror_stale)) {
-    // enqueued updates may still be running: the copies below (null stream) do not wait for the context stream
-    // (nor for front_stream, where an overlapped update runs: the context stream waits for that one first)
-    hipSetDevice(c->cfg.device);
-    join_update(c);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  if (c->pos_mirror_stale) {  // positions last came from device memory (fr_update_positions): fetch them now
-    hipSetDevice(c->cfg.device);
-    HIP_TRY(c, hipMemcpy(c->scene.pos.data(), c->d_pos, c->scene.pos.size() * sizeof(f3), hipMemcpyDeviceToHost));
-    c->pos_mirror_stale = false;
-  }
-  if (c->box_mirror_stale) {  // an enqueued update left the scene box on the device (fr_update_geometry_enqueue)
-    hipSetDevice(c->cfg.device);
-    float box[6];
-    HIP_TRY(c, hipMemcpy(box, c->geo->box, sizeof(box), hipMemcpyDeviceToHost));
-    c->scene.bbox_min = c->dsc.bbox_min = mk3(box[0], box[1], box[2]);
-    c->scene.bbox_max = c->dsc.bbox_max = mk3(box[3], box[4], box[5]);
-    c->box_mirror_stale = false;
-  }
-  if (c->nrm_mirror_stale) {  // normals were last written on the device: they are d_shade's n0 / n1 / n2 .xyz
-    hipSetDevice(c->cfg.device);
-    std::vector<TriShade> shade(c->scene.flags.size());
-    HIP_TRY(c, hipMemcpy(shade.data(), c->d_shade, shade.size() * sizeof(TriShade), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < shade.size(); i++) {
-      c->scene.nrm[3 * i] = xyz(shade[i].n0);
-      c->scene.nrm[3 * i + 1] = xyz(shade[i].n1);
-      c->scene.nrm[3 * i + 2] = xyz(shade[i].n2);
-    }
-    c->nrm_mirror_stale = false;
-  }
-  fill_arrays(c->scene, c->bvh, c->dsc.light_emission, c->mat_pairs, c->tex_dims, c->tex_ptrs, o);
-  return FR_OK;
-}
-
-int fr_scene_create(const fr_config* cfg_in, fr_scene** out) {
-  if (!out) return fail(nullptr, FR_E_INVALID, "out is NULL");
-  *out = nullptr;
-  fr_config cfg;
-  if (cfg_in) cfg = *cfg_in; else fr_config_default(&cfg);
-  if (cfg.scene < 0 || cfg.scene > 2) return fail(nullptr, FR_E_INVALID, "bad scene preset");
-  if (cfg.mesh_mode < 0 || cfg.mesh_mode > 2) return fail(nullptr, FR_E_INVALID, "bad mesh_mode");
-  fr_scene* sc = new fr_scene();
-  std::string err;
-  if (!build_preset_scene(cfg.scene, cfg.asset_dir ? cfg.asset_dir : "assets", cfg.texture_mode, cfg.light_power,
-                          cfg.detail, sc->scene, err, cfg.mesh_mode)) {
-    delete sc;
-    return fail(nullptr, FR_E_IO, "scene: " + err);
-  }
-  build_bvh(sc->scene, sc->bvh);
-  build_normal_groups(sc->scene, sc->groups);
-  *out = sc;
-  return FR_OK;
-}
-
-int fr_scene_get_arrays(fr_scene* sc, fr_scene_arrays* o) {
-  if (!sc || !o) return FR_E_INVALID;
-  fill_arrays(sc->scene, sc->bvh, sc->scene.light_emission, sc->mat_pairs, sc->tex_dims, sc->tex_ptrs, o);
-  return FR_OK;
-}
-
-int fr_scene_normal_groups(fr_scene* sc, int32_t* corner_vertex, size_t ncorners, int* nverts) {
-  if (!sc) return FR_E_INVALID;
-  return copy_groups(sc->groups, corner_vertex, ncorners, nverts);
-}
-
-int fr_scene_model_count(fr_scene* sc, int* n) {
-  if (!sc || !n) return FR_E_INVALID;
-  *n = (int)sc->scene.model_tri_count.size();
-  return FR_OK;
-}
-
-int fr_scene_model_info(fr_scene* sc, int i, const char** name, int* first_tri, int* ntris) {
-  if (!sc) return FR_E_INVALID;
-  return model_info(sc->scene, i, name, first_tri, ntris);
-}
-
-// Test hook (not part of include/fovrt.h): the host-built tree of an fr_scene (pointers into it, valid until
-// fr_scene_destroy): num_nodes BvhNode, then num_leaf_tris TriGeo and leaf-order primitive indices.
-int fr__scene_bvh(fr_scene* sc, const void** nodes, int* num_nodes, const void** tri_geo, const int32_t** prim,
-                  int* num_leaf_tris) {
-  if (!sc || !nodes || !num_nodes || !tri_geo || !prim || !num_leaf_tris) return FR_E_INVALID;
-  *nodes = sc->bvh.nodes.data();
-  *num_nodes = (int)sc->bvh.nodes.size();
-  *tri_geo = sc->bvh.tri_geo.data();
-  *prim = sc->bvh.tri_prim.data();
-  *num_leaf_tris = (int)sc->bvh.tri_prim.size();
-  return FR_OK;
-}
-
-// Test hook (not part of include/fovrt.h): replaces the positions of an fr_scene (xyz: ntris x 9 floats, finite;
-// ntris the scene's) and its box, and builds its tree over them with the host builder, as fr_scene_create did over
-// the preset's. The host builder's tree for any geometry, without a device: the reference of the device SAH
-// builder. Returns a negative status, or the number of splits that took the median fallback although the node's
-// centroids differ on the split axis (the one case in which the device builder fails instead; 0 on geometry of
-// ordinary size). Pointers fr__scene_bvh and fr_scene_get_arrays gave before the call are stale after it.
-int fr__scene_rebuild_over(fr_scene* sc, const float* xyz, size_t ntris) {
-  if (!sc || !xyz || ntris != (size_t)sc->scene.num_tris()) return FR_E_INVALID;
-  for (size_t i = 0; i < ntris * 9; i++)
-    if (!std::isfinite(xyz[i])) return FR_E_INVALID;
-  f3 lo = mk3(INFINITY), hi = mk3(-INFINITY);
-  for (size_t v = 0; v < ntris * 3; v++) {
-    const f3 p = mk3(xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2]);
-    sc->scene.pos[v] = p;
-    lo = mk3(fminf(lo.x, p.x), fminf(lo.y, p.y), fminf(lo.z, p.z));
-    hi = mk3(fmaxf(hi.x, p.x), fmaxf(hi.y, p.y), fmaxf(hi.z, p.z));
-  }
-  sc->scene.bbox_min = lo;
-  sc->scene.bbox_max = hi;
-  int medians = 0;
-  build_bvh(sc->scene, sc->bvh, &medians);
-  return medians;
-}
-
-int fr_scene_destroy(fr_scene* sc) {
-  if (!sc) return FR_E_INVALID;
-  delete sc;
   return FR_OK;
 }
 

@@ -152,15 +152,11 @@ struct fr_ctx {
   uint32_t* ray_count_p[MAX_SLOTS] = {};
   HostScene scene;
   Bvh bvh;
-  // device scene
-  BvhNode* d_nodes = nullptr;
+  // device scene: the tree in use, and the GPU builder's target arrays (adopt_spare swaps the two after a successful
+  // build; tree_alloc / tree_free make and release either)
+  fr::TreeArrays tree, spare;
+  bool tree_full_cap = false;  // `tree` holds one entry per triangle (a device-built tree)
   f3* d_pos = nullptr;  // world-space vertices, 3 per triangle (the GPU builder's input)
-  TriGeo* d_tri = nullptr;
-  int32_t* d_prim = nullptr;
-  // the GPU builder's target arrays (swapped with the current tree after a successful build) and its scratch
-  BvhNode* spare_nodes = nullptr;
-  TriGeo* spare_tri = nullptr;
-  int32_t* spare_prim = nullptr;
   // fr_update_positions writes new positions here and swaps with d_pos once the update succeeded: the old
   // positions survive a failed rebuild on the device, without the host mirror
   f3* spare_pos = nullptr;
@@ -219,7 +215,7 @@ struct fr_ctx {
   std::vector<float> pose_m;
   // Overlapped updates (fr_set_geometry_overlap). While overlap_on, an enqueued update runs on front_stream and writes
   // the set no frame in flight reads: the spare tree arrays above and shade_back (made by the first on = 1, a copy of
-  // d_shade), which then become the scene's (a swap with d_nodes / d_tri / d_prim / d_shade and a refresh of dsc;
+  // d_shade), which then become the scene's (adopt_spare: a swap with `tree` and d_shade and a refresh of dsc;
   // frames already enqueued keep the dsc they were given). set_cur: which of the two sets is the scene's.
   // set_read[i]: recorded on the context stream after the last reader of set i there (entry 3; a G-buffer on the
   // context stream); front_stream waits for the other set's before the update's first write. update_done: recorded on
@@ -251,7 +247,6 @@ struct fr_ctx {
   // scene.nrm (the host mirror of d_shade's normals) is behind: normals were written on the device.
   // fr_scene_export refreshes it; nothing else reads it.
   bool nrm_mirror_stale = false;
-  bool tree_full_cap = false;  // d_nodes / d_tri / d_prim hold one entry per triangle (a device-built tree)
   TriShade* d_shade = nullptr;
   std::vector<void*> d_tex;
   bool tex_packing = true;  // textures in their densest exact storage (pack_texture); FOVRT_TEX_PACKING=0: RGBA32F
@@ -395,12 +390,35 @@ int enqueue_shading(fr_ctx* c);  // entry 3 alone (the FR_STAMPS probes launch i
 int P_pos(const fr_ctx* c), P_shd(const fr_ctx* c), P_wgt(const fr_ctx* c);  // this frame slot's physical images
 int resolve(fr_ctx* c, int id, int* phys);  // buffer id -> physical image, with the lazy outputs it names written
 void kt_harvest(fr_ctx* c, int i), fc_harvest(fr_ctx* c, int i);  // one ring entry of fr_kernel_timing / fr_frame_clock
+// `waiter` waits for everything enqueued on the context stream so far (ev_stream_join). The caller keeps stream_dirty.
+void stream_join(fr_ctx* c, hipStream_t waiter);
+// While overlap_on: the context stream has just enqueued the last reader there of the scene's tree and normals.
+inline hipError_t mark_set_read(fr_ctx* c) {
+  return c->overlap_on ? c->set_read[c->set_cur].record(c->stream) : hipSuccess;
+}
 int gpu_rebuild(fr_ctx* c, const f3* pos);  // ctx_geometry.cpp
+// The arrays of one tree (ctx_geometry.cpp), all or nothing: on failure what was made is freed, *t stays null and
+// the sticky HIP error is cleared. tree_free releases them and nulls *t.
+bool tree_alloc(fr::TreeArrays* t, size_t node_cap, size_t tri_cap);
+void tree_free(fr::TreeArrays* t);
+// The spare tree arrays become the scene's and the scene's the spare; with_shade: the shading records (d_shade /
+// shade_back) and set_cur go with them. dsc's four pointers then name the scene's. (ctx_geometry.cpp)
+void adopt_spare(fr_ctx* c, bool with_shade);
+inline void point_dsc(fr_ctx* c) {  // dsc's pointers to the tree and the shading records in use
+  c->dsc.nodes = c->tree.nodes; c->dsc.tri_geo = c->tree.tri; c->dsc.tri_prim = c->tree.prim; c->dsc.shade = c->d_shade;
+}
+inline int tree_nodes(const Bvh& b) {
+  return b.gpu_nodes >= 0 ? b.gpu_nodes : b.host_nodes ? b.host_nodes : (int)b.nodes.size();
+}
+// Model i of the scene: the contiguous triangle range add_mesh recorded (ctx_scene.cpp). FR_E_INVALID: no such model.
+int model_info(const HostScene& s, int i, const char** name, int* first_tri, int* ntris);
+void box_of(const f3* v, size_t n, f3* lo, f3* hi);  // the box of n points (ctx_scene.cpp)
 // The host's numbers of the tree in use (bvh.gpu_nodes / max_stack / max_depth) made current: while tree_on_device
 // they are fetched from the device, behind the context's pending work (a wait). Every host reader of them goes
 // through this first. (ctx_geometry.cpp)
 int tree_numbers(fr_ctx* c);
 }  // namespace fri
+static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
 
 #define HIP_TRY(ctx, expr)                                                                                      \
   do {                                                                                                          \

@@ -101,7 +101,7 @@ int fr_trace_rays_enqueue(fr_ctx* c, const void* rays, size_t n, int kind, void*
   if (int rc = launch_query(c, rays, n, kind, out)) return rc;
   HIP_TRY(c, c->rays_done.record(c->stream));
   // overlapped updates: the query read the set in use; the update after the next one writes it
-  if (c->overlap_on) HIP_TRY(c, c->set_read[c->set_cur].record(c->stream));
+  HIP_TRY(c, mark_set_read(c));
   return FR_OK;
 }
 

@@ -711,17 +711,16 @@ __global__ void k_build_init(uint32_t* __restrict__ cb, CollapseItem* __restrict
 }
 
 template <class Tree, class Phase>
-static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes, TriGeo* tri,
-                              int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err,
-                              Phase&& phase);
+static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, const TreeArrays& t,
+                              int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err, Phase&& phase);
 
 // Builds the four-wide BVH of n triangles (pos: 3 vertices per triangle, device) into the caller's
-// nodes / tri / prim (device, n entries each) with the workspace *work (created or grown here, kept
+// arrays t (device, n entries each) with the workspace *work (created or grown here, kept
 // by the caller). Returns false with err set on failure. num_nodes, max_stack and depth (levels of
 // the four-wide tree below the root) describe the result. The collapse runs its levels in batches of
 // launches that skip themselves once the level queue is empty, with one host read per batch.
-bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim, int* num_nodes,
-                   int* max_stack, int* depth, hipStream_t s, std::string& err) {
+bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, const TreeArrays& t, int* num_nodes, int* max_stack, int* depth,
+                   hipStream_t s, std::string& err) {
   if (n < 3) { err = "GPU BVH builder needs at least 3 triangles"; return false; }
   // FOVRT_BVH_PHASES=1: host time of each phase (each followed by a stream sync) on stderr, a diagnostic
   static const bool phases = [] { const char* v = getenv("FOVRT_BVH_PHASES"); return v && atoi(v) != 0; }();
@@ -767,7 +766,7 @@ bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo*
                      w.arrivals);
   phase("karras");
   BinTree T{n, w.child, w.range, w.nlo, w.nhi, w.blo, w.bhi, w.ids_s};
-  return collapse_and_emit(w, T, w.ids_s, pos, n, nodes, tri, prim, num_nodes, max_stack, depth, s, err, phase);
+  return collapse_and_emit(w, T, w.ids_s, pos, n, t, num_nodes, max_stack, depth, s, err, phase);
 }
 
 BvhWorkView bvh_work_view(BvhWork* w) { return BvhWorkView{w->blo, w->bhi, w->cb}; }
@@ -782,22 +781,20 @@ bool gpu_prim_boxes_enqueue(BvhWork* work, const f3* pos, int n, hipStream_t s, 
   return true;
 }
 
-bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes,
-                         TriGeo* tri, int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s,
-                         std::string& err) {
+bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, const TreeArrays& t,
+                         int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err) {
   if (!work || n < 3 || n > work->cap) { err = "GPU BVH builder: no workspace for these triangles"; return false; }
   // (qa[0], ctr: k_build_init ran in gpu_prim_boxes_enqueue, and nothing since has touched them)
-  return collapse_and_emit(*work, MarkedBinTree{T.child, T.range, T.lo, T.hi}, ids, pos, n, nodes, tri, prim, num_nodes,
-                           max_stack, depth, s, err, [](const char*) {});
+  return collapse_and_emit(*work, MarkedBinTree{T.child, T.range, T.lo, T.hi}, ids, pos, n, t, num_nodes, max_stack,
+                           depth, s, err, [](const char*) {});
 }
 
 // The four-wide part of a build: the collapse of the binary tree T, whose leaves own ranges of ids, then the leaf
 // scan and the triangle relayout. The collapse runs its levels in batches of launches that skip themselves once
 // the level queue is empty, with one host read per batch.
 template <class Tree, class Phase>
-static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes, TriGeo* tri,
-                              int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err,
-                              Phase&& phase) {
+static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* pos, int n, const TreeArrays& t,
+                              int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err, Phase&& phase) {
   const int B = 256, G = (n + B - 1) / B;
   size_t tb = w.tmp_bytes;
   // (qa[0] = the root item and ctr = {1, 0, 1, 0, 0}: k_build_init)
@@ -808,8 +805,8 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
     for (int b = 0; b < kBatch; b++) {
       hipMemsetAsync(w.ctr + 3, 0, sizeof(uint32_t), s);
       // a level holds at most n items (one per inner node of the binary tree)
-      hipLaunchKernelGGL(k_collapse<Tree>, dim3(G), dim3(B), 0, s, T, qa, w.ctr + 2, qb, w.ctr + 3, w.ctr, nodes, w.ctr + 1,
-                         w.ctr + 4, nullptr);
+      hipLaunchKernelGGL(k_collapse<Tree>, dim3(G), dim3(B), 0, s, T, qa, w.ctr + 2, qb, w.ctr + 3, w.ctr, t.nodes,
+                         w.ctr + 1, w.ctr + 4, nullptr);
       hipMemcpyAsync(w.ctr + 2, w.ctr + 3, sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
       std::swap(qa, qb);
     }
@@ -824,11 +821,11 @@ static bool collapse_and_emit(BvhWork& w, Tree T, const int32_t* ids, const f3* 
   *max_stack = (int)w.host[1];
   *depth = (int)w.host[4] - 1;
   const int nn = *num_nodes, GN = (nn + B - 1) / B;
-  hipLaunchKernelGGL(k_leaf_counts<false>, dim3(GN), dim3(B), 0, s, nodes, nn, w.cnt, nullptr);
+  hipLaunchKernelGGL(k_leaf_counts<false>, dim3(GN), dim3(B), 0, s, t.nodes, nn, w.cnt, nullptr);
   tb = w.tmp_bytes;
   hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, nn, s);
   phase("scan");
-  hipLaunchKernelGGL(k_emit_leaves<false>, dim3(GN), dim3(B), 0, s, nodes, nn, w.off, ids, pos, tri, prim, nullptr);
+  hipLaunchKernelGGL(k_emit_leaves<false>, dim3(GN), dim3(B), 0, s, t.nodes, nn, w.off, ids, pos, t.tri, t.prim, nullptr);
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH builder: kernel failure";
     return false;
@@ -958,19 +955,19 @@ static bool collapse_and_emit_enqueue(BvhWork& w, Tree T, const int32_t* ids, co
   for (int L = 0; L < levels; L++) {
     const long long items = L < 15 ? std::min<long long>(1ll << (2 * L), n) : n;
     const int GL = (int)((items + B - 1) / B);
-    hipLaunchKernelGGL(collapse, dim3(GL), dim3(B), 0, s, T, qa, rs->level + L, qb, rs->level + L + 1, w.ctr, t.nodes,
+    hipLaunchKernelGGL(collapse, dim3(GL), dim3(B), 0, s, T, qa, rs->level + L, qb, rs->level + L + 1, w.ctr, t.dst.nodes,
                        w.ctr + 1, w.ctr + 4, sah_fail);
     std::swap(qa, qb);
   }
   hipLaunchKernelGGL(k_rebuild_verdict, dim3(1), dim3(64), 0, s, rs, sah_fail, w.ctr, levels, t.desc, t.conditional);
-  hipLaunchKernelGGL(k_leaf_counts<true>, dim3(G), dim3(B), 0, s, t.nodes, n, w.cnt, &rs->emit_nodes);
+  hipLaunchKernelGGL(k_leaf_counts<true>, dim3(G), dim3(B), 0, s, t.dst.nodes, n, w.cnt, &rs->emit_nodes);
   size_t tb = w.tmp_bytes;
   hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.cnt, w.off, n, s);
-  hipLaunchKernelGGL(k_emit_leaves<true>, dim3(G), dim3(B), 0, s, t.nodes, n, w.off, ids, pos, t.tri, t.prim,
+  hipLaunchKernelGGL(k_emit_leaves<true>, dim3(G), dim3(B), 0, s, t.dst.nodes, n, w.off, ids, pos, t.dst.tri, t.dst.prim,
                      &rs->emit_nodes);
   const int GK = (int)std::min<long long>(((long long)n * 8 + B - 1) / B, 2048);
-  hipLaunchKernelGGL(k_rebuild_keep, dim3(GK), dim3(B), 0, s, rs, t.src_nodes, t.src_tri, t.src_prim, t.src_host_nodes,
-                     t.src_host_desc, t.src_desc, n, t.nodes, t.tri, t.prim, t.desc, t.conditional);
+  hipLaunchKernelGGL(k_rebuild_keep, dim3(GK), dim3(B), 0, s, rs, t.src.nodes, t.src.tri, t.src.prim, t.src_host_nodes,
+                     t.src_host_desc, t.src_desc, n, t.dst.nodes, t.dst.tri, t.dst.prim, t.desc, t.conditional);
   if (hipGetLastError() != hipSuccess) { err = "GPU BVH builder: launch failure"; return false; }
   return true;
 }
@@ -1011,7 +1008,7 @@ bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTar
   return collapse_and_emit_enqueue(w, T, w.ids_s, pos, n, FR_REBUILD_LEVELS, nullptr, t, s, err);
 }
 
-// Refits the four-wide tree nodes[0, num_nodes) (either builder's) over new positions, in place: every slot box
+// Refits the four-wide tree t.nodes[0, num_nodes) (either builder's) over new positions, in place: every slot box
 // and tri[j] for every leaf-order j are rewritten, child / count / prim are not. num_nodes == 0 (the whole scene
 // is one leaf): tri only. Three launches whatever the depth, no allocation; the scratch is *work's nlo / nhi
 // (raw node boxes), parent and arrivals, which hold one entry per triangle (a tree has at most as many nodes).
@@ -1019,9 +1016,8 @@ bool gpu_build_bvh_enqueue(BvhWork* work, const f3* pos, int n, const RebuildTar
 // which selects the gated kernels); gpu_refit_bvh also waits for them.
 // nodes_dev (the enqueue forms; NULL: num_nodes is the tree's): the tree's node count in device memory, for a tree
 // the host has not seen (fr_rebuild_bvh_enqueue). num_nodes is ignored then and the grids cover the capacity, n.
-bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
-                           const int32_t* prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
-                           std::string& err) {
+bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, const TreeArrays& t, int num_nodes,
+                           const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s, std::string& err) {
   if (nodes_dev) num_nodes = n;
   if (!work || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap || (nodes_dev && !reject)) {
     err = "GPU BVH refit: no workspace for this tree";
@@ -1032,11 +1028,11 @@ bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, 
   auto tris = reject ? k_refit_tris<true> : k_refit_tris<false>;
   auto links = nodes_dev ? k_refit_links<true, true> : reject ? k_refit_links<true> : k_refit_links<false>;
   auto up = nodes_dev ? k_refit_up<true, true> : reject ? k_refit_up<true> : k_refit_up<false>;
-  hipLaunchKernelGGL(tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, prim, n, tri, reject);
+  hipLaunchKernelGGL(tris, dim3((n + B - 1) / B), dim3(B), 0, s, pos, t.prim, n, t.tri, reject);
   if (num_nodes > 0) {
     const int GN = (num_nodes + B - 1) / B;
-    hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, nodes, num_nodes, w.parent, w.arrivals, reject, nodes_dev);
-    hipLaunchKernelGGL(up, dim3(GN), dim3(B), 0, s, nodes, num_nodes, pos, prim, w.parent, w.arrivals, w.nlo, w.nhi,
+    hipLaunchKernelGGL(links, dim3(GN), dim3(B), 0, s, t.nodes, num_nodes, w.parent, w.arrivals, reject, nodes_dev);
+    hipLaunchKernelGGL(up, dim3(GN), dim3(B), 0, s, t.nodes, num_nodes, pos, t.prim, w.parent, w.arrivals, w.nlo, w.nhi,
                        reject, nodes_dev);
   }
   if (hipGetLastError() != hipSuccess) {
@@ -1046,12 +1042,11 @@ bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, 
   return true;
 }
 
-// The refit of an enqueued update out of place (k_refit_*_to): from the tree in use (src_*) over `pos` into the
-// arrays no frame in flight reads (dst_*, room for num_nodes nodes and n triangles), whole. reject: the device
+// The refit of an enqueued update out of place (k_refit_*_to): from the tree in use (src) over `pos` into the
+// arrays no frame in flight reads (dst, room for num_nodes nodes and n triangles), whole. reject: the device
 // verdict word, never NULL. The same scratch, the same three launches, no wait.
-bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
-                              const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
-                              int32_t* dst_prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const TreeArrays& src, int num_nodes,
+                              const TreeArrays& dst, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
                               std::string& err) {
   if (nodes_dev) num_nodes = n;
   if (!work || !reject || n < 1 || n > work->cap || num_nodes < 0 || num_nodes > work->cap) {
@@ -1060,14 +1055,14 @@ bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode
   }
   BvhWork& w = *work;
   const int B = 256;
-  hipLaunchKernelGGL(k_refit_tris_to, dim3((n + B - 1) / B), dim3(B), 0, s, pos, src_prim, src_tri, n, dst_tri, dst_prim,
+  hipLaunchKernelGGL(k_refit_tris_to, dim3((n + B - 1) / B), dim3(B), 0, s, pos, src.prim, src.tri, n, dst.tri, dst.prim,
                      reject);
   if (num_nodes > 0) {
     const int GN = (num_nodes + B - 1) / B;
-    hipLaunchKernelGGL(nodes_dev ? k_refit_links_to<true> : k_refit_links_to<false>, dim3(GN), dim3(B), 0, s, src_nodes,
-                       num_nodes, w.parent, w.arrivals, dst_nodes, reject, nodes_dev);
-    hipLaunchKernelGGL(nodes_dev ? k_refit_up_to<true> : k_refit_up_to<false>, dim3(GN), dim3(B), 0, s, src_nodes,
-                       dst_nodes, num_nodes, pos, src_prim, w.parent, w.arrivals, w.nlo, w.nhi, reject, nodes_dev);
+    hipLaunchKernelGGL(nodes_dev ? k_refit_links_to<true> : k_refit_links_to<false>, dim3(GN), dim3(B), 0, s, src.nodes,
+                       num_nodes, w.parent, w.arrivals, dst.nodes, reject, nodes_dev);
+    hipLaunchKernelGGL(nodes_dev ? k_refit_up_to<true> : k_refit_up_to<false>, dim3(GN), dim3(B), 0, s, src.nodes,
+                       dst.nodes, num_nodes, pos, src.prim, w.parent, w.arrivals, w.nlo, w.nhi, reject, nodes_dev);
   }
   if (hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: launch failure";
@@ -1076,9 +1071,9 @@ bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode
   return true;
 }
 
-bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
-                   hipStream_t s, std::string& err) {
-  if (!gpu_refit_bvh_enqueue(work, pos, n, nodes, num_nodes, tri, prim, nullptr, nullptr, s, err)) return false;
+bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, const TreeArrays& t, int num_nodes, hipStream_t s,
+                   std::string& err) {
+  if (!gpu_refit_bvh_enqueue(work, pos, n, t, num_nodes, nullptr, nullptr, s, err)) return false;
   if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
     err = "GPU BVH refit: kernel failure";
     return false;
@@ -1143,12 +1138,12 @@ bool gpu_rebuild_decide_enqueue(BvhWork* work, RebuildState* rs, const BvhNode* 
   return true;
 }
 
-// Behind a conditional build: the cost of the tree it made (t.nodes, whose node count is t.desc's) becomes the
+// Behind a conditional build: the cost of the tree it made (t.dst.nodes, whose node count is t.desc's) becomes the
 // baseline (k_rebuild_rebase). After a failed or skipped build the terms are not read and nothing changes. No wait.
 bool gpu_rebuild_rebase_enqueue(BvhWork* work, const RebuildTarget& t, int n, hipStream_t s, std::string& err) {
   if (!work || n < 1 || n > work->cap) { err = "GPU BVH cost: no workspace for this tree"; return false; }
   BvhWork& w = *work;
-  cost_enqueue(w, t.nodes, n, n, &t.desc->nodes, &t.rs->fail, s);
+  cost_enqueue(w, t.dst.nodes, n, n, &t.desc->nodes, &t.rs->fail, s);
   hipLaunchKernelGGL(k_rebuild_rebase, dim3(1), dim3(64), 0, s, t.rs, reinterpret_cast<const float*>(w.ctr + 5));
   if (hipGetLastError() != hipSuccess) { err = "GPU BVH cost: launch failure"; return false; }
   return true;

@@ -512,8 +512,8 @@ bool sah_work_create(SahWork** out, int n, hipStream_t s, std::string& err) {
   return true;
 }
 
-bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim,
-                       int* num_nodes, int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err) {
+bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, const TreeArrays& t, int* num_nodes,
+                       int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err) {
   *unsupported = false;
   if (n < 3) { err = "GPU BVH builder needs at least 3 triangles"; return false; }
   if (!sw || !work || n > sw->cap) { err = "GPU SAH builder: no workspace for these triangles"; return false; }
@@ -561,8 +561,8 @@ bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode
     if (w.host[C_NODES] == w.host[C_END]) break;  // the last level made no node
     if (w.host[C_BIG_NEXT] == 0) big = false;
   }
-  return gpu_collapse_marked(work, MarkedTree{w.kid, w.rng, w.nlo, w.nhi}, w.ids, pos, n, nodes, tri, prim, num_nodes,
-                             max_stack, depth, s, err);
+  return gpu_collapse_marked(work, MarkedTree{w.kid, w.rng, w.nlo, w.nhi}, w.ids, pos, n, t, num_nodes, max_stack, depth,
+                             s, err);
 }
 
 // The build in stream order: every level of the depth bound is launched, with the large nodes' kernels whenever the

@@ -2,7 +2,8 @@
 // by the file that defines each of them and, through ctx_internal.h, by every file that calls them. A declaration
 // whose types drift from its definition does not build: another return type is an error in the .hip file, other
 // parameter types declare an overload that nothing defines, which the link refuses (-z defs). Parameter names are
-// the definitions'; two same-typed parameters in the wrong order are still for the reader to catch.
+// the definitions'; two same-typed parameters in the wrong order are still for the reader to catch (so the three
+// arrays of a tree travel as one TreeArrays, below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -111,22 +112,27 @@ int pp_size(int W, int H);
 size_t pp_snap_count(int S);
 
 // k_bvh.hip
+// The three device arrays of one four-wide tree: nodes, and the triangles and primitive indices in leaf order. A host
+// type only: kernels keep their own parameter lists (and their const).
+struct TreeArrays {
+  BvhNode* nodes = nullptr;
+  TriGeo* tri = nullptr;
+  int32_t* prim = nullptr;
+};
 struct BvhWork;
-bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim, int* num_nodes,
-                   int* max_stack, int* depth, hipStream_t s, std::string& err);
+bool gpu_build_bvh(BvhWork** work, const f3* pos, int n, const TreeArrays& t, int* num_nodes, int* max_stack, int* depth,
+                   hipStream_t s, std::string& err);
 void bvh_work_free(BvhWork* w);
 bool bvh_work_prepare(BvhWork** w, int n, hipStream_t s, std::string& err);
 bool bvh_builder_warm(BvhWork* w, hipStream_t s, std::string& err);
-bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri, const int32_t* prim,
-                   hipStream_t s, std::string& err);
+bool gpu_refit_bvh(BvhWork* work, const f3* pos, int n, const TreeArrays& t, int num_nodes, hipStream_t s,
+                   std::string& err);
 // (nodes_dev, here and below: NULL, or the node count in device memory of a tree the host has not seen)
-bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, BvhNode* nodes, int num_nodes, TriGeo* tri,
-                           const int32_t* prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
-                           std::string& err);
+bool gpu_refit_bvh_enqueue(BvhWork* work, const f3* pos, int n, const TreeArrays& t, int num_nodes,
+                           const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s, std::string& err);
 // the refit of an enqueued update out of place: from the tree in use into another set of arrays, whole
-bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const BvhNode* src_nodes, int num_nodes,
-                              const TriGeo* src_tri, const int32_t* src_prim, BvhNode* dst_nodes, TriGeo* dst_tri,
-                              int32_t* dst_prim, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
+bool gpu_refit_bvh_to_enqueue(BvhWork* work, const f3* pos, int n, const TreeArrays& src, int num_nodes,
+                              const TreeArrays& dst, const uint32_t* reject, const uint32_t* nodes_dev, hipStream_t s,
                               std::string& err);
 bool gpu_check_positions_enqueue(BvhWork* work, const float* xyz, int n, hipStream_t s, std::string& err);
 bool gpu_take_over_positions(BvhWork* work, const f3* xyz, const f3* cur, int n, f3* dst, const uint32_t* bad_nrm,
@@ -153,24 +159,18 @@ struct MarkedTree {
 };
 // The four-wide part of gpu_build_bvh over such a tree (root: node 0, not a leaf): collapse, leaf scan, triangle
 // relayout, with the same kernels. Waits for the result.
-bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, BvhNode* nodes,
-                         TriGeo* tri, int32_t* prim, int* num_nodes, int* max_stack, int* depth, hipStream_t s,
-                         std::string& err);
+bool gpu_collapse_marked(BvhWork* work, const MarkedTree& T, const int32_t* ids, const f3* pos, int n, const TreeArrays& t,
+                         int* num_nodes, int* max_stack, int* depth, hipStream_t s, std::string& err);
 
-// A build in stream order (fr_rebuild_bvh_enqueue): where it goes (nodes / tri / prim, n entries each, and the
-// record of its numbers), the context's record of such builds, and the tree in use, which a build that fails on the
+// A build in stream order (fr_rebuild_bvh_enqueue): where it goes (dst, n entries each, and the record of its
+// numbers), the context's record of such builds, and the tree in use (src), which a build that fails on the
 // device copies over the destination (src_host_nodes >= 0: the host knows its numbers, src_host_desc; else src_desc).
 // conditional: the build is fr_rebuild_bvh_enqueue_if's; gpu_rebuild_decide_enqueue has left FR_REBUILD_SKIP or 0 in
 // rs->fail earlier on the stream, and a skipped build runs the same schedule over an empty level 0.
 struct RebuildTarget {
   RebuildState* rs;
-  BvhNode* nodes;
-  TriGeo* tri;
-  int32_t* prim;
+  TreeArrays dst, src;
   TreeDesc* desc;
-  const BvhNode* src_nodes;
-  const TriGeo* src_tri;
-  const int32_t* src_prim;
   int src_host_nodes;
   TreeDesc src_host_desc;
   const TreeDesc* src_desc;
@@ -197,8 +197,8 @@ bool sah_work_create(SahWork** out, int n, hipStream_t s, std::string& err);
 void sah_work_free(SahWork* w);
 size_t sah_work_bytes(int n);
 // gpu_build_bvh's contract. *unsupported: the build met a node without a finite SAH candidate (see fovrt.h)
-bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, BvhNode* nodes, TriGeo* tri, int32_t* prim,
-                       int* num_nodes, int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err);
+bool gpu_build_bvh_sah(SahWork* sw, BvhWork* work, const f3* pos, int n, const TreeArrays& t, int* num_nodes,
+                       int* max_stack, int* depth, bool* unsupported, hipStream_t s, std::string& err);
 // the same build in stream order: all 30 levels are launched (those past the last find nothing), see RebuildTarget
 bool gpu_build_bvh_sah_enqueue(SahWork* sw, BvhWork* work, const f3* pos, int n, const RebuildTarget& t, hipStream_t s,
                                std::string& err);
