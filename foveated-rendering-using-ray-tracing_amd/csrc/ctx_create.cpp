@@ -422,7 +422,7 @@ int fr_destroy(fr_ctx* c) {
   if (c->h_geo) hipHostFree(c->h_geo);
   fr(c->rb);
   if (c->h_rb) hipHostFree(c->h_rb);
-  fr(c->rq); fr(c->rq_rays); fr(c->rq_out);
+  fr(c->rq); fr(c->rq_area);
   if (c->rays_done.ev) hipEventDestroy(c->rays_done.ev);
   if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
   for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);

@@ -227,13 +227,15 @@ struct fr_ctx {
   Fence set_read[2];
   Fence update_done;
   // Ray queries (fr_trace_rays, ctx_query.cpp). rq: their record on the device (the chunk counter of k_ray_queries),
-  // made by fr_create and zeroed in stream order ahead of every launch. rq_rays / rq_out: the staging area of host
-  // batches, rq_cap rays and results (fr_ray_query_reserve; 32 B and 16 B each). rays_done: recorded on the context
-  // stream after the last enqueued query's kernel; the caller's stream waits for it (fr_rays_consumed; never
-  // consumed: any number of streams may ask). rayq_blocks: FOVRT_RAYQ_BLOCKS, a cap on the grid, 0 = none.
+  // made by fr_create and zeroed in stream order ahead of every launch. rq_area: the staging area of host batches,
+  // rq_bytes bytes (fr_ray_query_reserve: 48 B per ray; fr_ray_query_reserve_kind: 32 B, the kind's result and 4 B of
+  // mask), laid out per call as rays, results, masks; rq_cap = rq_bytes / 48, the rays fr_ray_query_reserve's callers
+  // were promised. rays_done: recorded on the context stream after the last enqueued query's kernel; the caller's
+  // stream waits for it (fr_rays_consumed; never consumed: any number of streams may ask). rayq_blocks:
+  // FOVRT_RAYQ_BLOCKS, a cap on the grid, 0 = none.
   fr::RayQueryState* rq = nullptr;
-  void* rq_rays = nullptr;
-  void* rq_out = nullptr;
+  void* rq_area = nullptr;
+  size_t rq_bytes = 0;
   size_t rq_cap = 0;
   Fence rays_done;
   uint32_t rayq_blocks = 0;

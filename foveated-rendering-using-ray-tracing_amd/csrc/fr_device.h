@@ -150,6 +150,19 @@ struct PoseArgs {
   float K[FR_POSE_MAX_MODELS][9];         // cofactors of A, row-major (pose_args)
 };
 
+// The scene's model boundaries for ray queries (per-ray model masks, the model word of fr_ray_surface), passed by
+// value in the kernel arguments as PoseArgs::first_tri is: the model of a triangle is found without a load.
+struct RayModels {
+  int32_t first_tri[FR_POSE_MAX_MODELS];  // as PoseArgs::first_tri; unused: INT32_MAX
+  uint32_t valid;                         // bit i: the scene has a model i (mask bits above are ignored)
+};
+FR_HD int ray_model_of(const RayModels& rm, int prim) {
+  int m = 0;
+#pragma unroll
+  for (int i = 1; i < FR_POSE_MAX_MODELS; i++) m += prim >= rm.first_tri[i] ? 1 : 0;
+  return m;
+}
+
 // Per-frame uniforms (FR/PathTracer.cpp:85-116, 774-820).
 struct FrameUniforms {
   mat4 inv_vp;              // "mvp" on the device: inverse(P*V), row-major

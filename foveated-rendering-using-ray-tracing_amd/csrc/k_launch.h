@@ -48,10 +48,11 @@ void launch_vring_pack(const f4* hist, int W, int H, int T, const int32_t* tiles
                        hipStream_t stream);
 void launch_vring_unpack(const uint32_t* in, int W, int H, int T, const int32_t* tiles, int ntiles, f4* hist,
                          hipStream_t stream);
-// fr_trace_rays: n fr_ray records against sc; kind 0 closest hit (out: n fr_ray_hit), 1 transmittance (out: n floats);
+// fr_trace_rays: n fr_ray records against sc; kind 0 closest hit (out: n fr_ray_hit), 1 transmittance (out: n floats),
+// 2 surface (out: n fr_ray_surface; two launches); masks: NULL or n words, bit k: model k of rm takes part;
 // max_blocks caps the grid (0: as many blocks as are resident)
-void launch_ray_queries(const DevScene& sc, const void* rays, uint32_t n, int kind, void* out, RayQueryState* rq,
-                        uint32_t max_blocks, hipStream_t stream);
+void launch_ray_queries(const DevScene& sc, const void* rays, const uint32_t* masks, uint32_t n, int kind, void* out,
+                        RayQueryState* rq, const RayModels& rm, uint32_t max_blocks, hipStream_t stream);
 #ifdef FR_STAMPS
 void launch_trace_queries(const DevScene& sc, const f4* queries, uint32_t n, f4* hits, uint32_t* ctr,
                           hipStream_t stream, int kind);

@@ -103,6 +103,19 @@ FR_DEV f3 shading_normal_of(const DevScene& sc, const TriShade& s, float beta, f
 //                     reflection.cu:239-244); every refractive hit multiplies 1 - schlick(|n.d|, 5)
 //                     (refraction.cu:144-153). The product is kept in f64 so it does not depend on
 //                     the order in which the BVH delivers the hits.
+// fresnel_schlick(c, 5, 0, 1) with the power rounded once: x^5 in f64 (x^2 is exact there, the two further products
+// round at 2^-53), then to fp32. The platform's powf, which fresnel_schlick uses, is off by a last bit now and then,
+// and 1 - schlick magnifies that bit where the power is near 1: on rays whose direction is not a unit vector the
+// transmittance then misses the restatement (glibc's powf, which is this value) by up to 94 ulp. The masked queries,
+// which are held to that restatement on such rays, take this form; the frame's shadow rays and the unmasked queries
+// keep the one they have, instruction for instruction.
+FR_DEV float schlick5_rounded_once(float cos_theta) {
+  const double x = (double)fmaxf(0.0f, 1.0f - cos_theta);
+  const double x2 = x * x;
+  return fmaxf(0.0f, fminf(__builtin_fmaf(1.0f, (float)(x2 * x2 * x), 0.0f), 1.0f));
+}
+
+template <bool POW_ONCE = false>
 FR_DEV void take_hit(const DevScene& sc, int j, const TriGeo& g, f3 d, bool any_hit, float t, float b, float gm,
                      Hit& best, double& atten, bool& done) {
   if (!any_hit) {
@@ -129,14 +142,23 @@ FR_DEV void take_hit(const DevScene& sc, int j, const TriGeo& g, f3 d, bool any_
     // attribute normalised a second time (identity transform)
     f3 ns = normalizec(shading_normal_of(sc, s, b, gm, ng));
     float nDi = fabsf(dotc(ns, d));
-    atten *= (double)(1.0f - fresnel_schlick(nDi, 5.0f, 0.0f, 1.0f));
+    atten *= (double)(1.0f - (POW_ONCE ? schlick5_rounded_once(nDi) : fresnel_schlick(nDi, 5.0f, 0.0f, 1.0f)));
   }
 }
 
+// MASKED (ray queries with per-ray model masks): a candidate tri_test accepts is dropped when the bit of its
+// triangle's model is clear in `mask`, before take_hit sees it, so an excluded model neither wins, ties, blocks nor
+// attenuates; the primitive-map load is paid on accepted candidates only; a refractive crossing it keeps takes the
+// power of its Schlick term rounded once (schlick5_rounded_once). The frame's kernels and the unmasked
+// queries instantiate MASKED = false, which is the code without the arm.
+template <bool MASKED = false>
 FR_DEV void test_tri(const DevScene& sc, int j, const TriGeo& g, f3 o, f3 d, float tmin, float tmax, bool any_hit,
-                     Hit& best, double& atten, bool& done) {
+                     Hit& best, double& atten, bool& done, uint32_t mask = 0, const RayModels* rm = nullptr) {
   float t, b, gm;
-  if (tri_test(g, o, d, tmin, tmax, t, b, gm)) take_hit(sc, j, g, d, any_hit, t, b, gm, best, atten, done);
+  if (tri_test(g, o, d, tmin, tmax, t, b, gm)) {
+    if (MASKED && !((mask >> ray_model_of(*rm, sc.tri_prim[j])) & 1u)) return;
+    take_hit<MASKED>(sc, j, g, d, any_hit, t, b, gm, best, atten, done);
+  }
 }
 
 
@@ -299,7 +321,9 @@ FR_DEV void visit_node(const DevScene& sc, Stack st, TravState& ts, f3 o, float 
   visit_loaded(load_node(sc, ts.node, ts.inv), st, ts, o, tmin);
 }
 
-FR_DEV bool trav_step(const DevScene& sc, Stack st, TravState& ts, f3 o, f3 d, float tmin, float tmax, bool any_hit) {
+template <bool MASKED = false>
+FR_DEV bool trav_step(const DevScene& sc, Stack st, TravState& ts, f3 o, f3 d, float tmin, float tmax, bool any_hit,
+                      uint32_t mask = 0, const RayModels* rm = nullptr) {
   if (ts.tlo >= ts.thi) visit_node(sc, st, ts, o, tmin);
   if (ts.tlo < ts.thi) {
     const int j = ts.tlo;
@@ -307,10 +331,10 @@ FR_DEV bool trav_step(const DevScene& sc, Stack st, TravState& ts, f3 o, f3 d, f
     const TriGeo g0 = sc.tri_geo[j];
     const TriGeo g1 = sc.tri_geo[two ? j + 1 : j];
     bool done = false;
-    test_tri(sc, j, g0, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done);
+    test_tri<MASKED>(sc, j, g0, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done, mask, rm);
     if (done) return true;
     if (two) {
-      test_tri(sc, j + 1, g1, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done);
+      test_tri<MASKED>(sc, j + 1, g1, o, d, tmin, tmax, any_hit, ts.best, ts.atten, done, mask, rm);
       if (done) return true;
     }
     ts.tlo = j + 2;
@@ -1647,7 +1671,8 @@ uint32_t diag_recorded_queries(hipStream_t stream) {
 // next ray by its rank among the idle lanes, and a lane never waits for another wave. Against it: 32-B fr_ray
 // records (two 16-B loads) with their own tmin, the degenerate-ray rule ahead of trav_begin (no traversal ever
 // runs on NaN slabs), the scene's triangle index instead of the leaf's, the miss record (+inf, 0, 0, -1), and one
-// template arm per kind (KIND 0: closest hit, 16-B fr_ray_hit records; KIND 1: transmittance, one float each).
+// template arm per kind (KIND 0: closest hit, 16-B fr_ray_hit records; KIND 1: transmittance, one float each; KIND 2:
+// the closest hit as row 0 of 80-B fr_ray_surface records, which k_ray_surface completes) and per masking.
 // The batch's chunks are split into FR_RAYQ_SHARDS contiguous runs with a counter each, 128 B apart; a wave starts
 // on the run of its block's XCD (blockIdx & 7) and moves to the next run when its own is exhausted, for good: a
 // run never refills. With one counter the 8.29 M camera rays of a 4K frame took 1.61 ms whatever their order, 12.5 ns
@@ -1667,19 +1692,31 @@ FR_DEV bool ray_degenerate(f4 a, f4 b) {
   const bool zero = b.x == 0.0f && b.y == 0.0f && b.z == 0.0f;
   return !finite || zero || !(a.w < b.w);
 }
+// KIND 2 (FR_RAYS_SURFACE): the closest hit written as row 0 of an 80-B fr_ray_surface record, with the hit's leaf
+// index (-1: a miss) left in the record's word 7 for k_ray_surface, which overwrites it with the model.
+#define RS_ROWS 5  // 16-B rows of an fr_ray_surface record
 template <int KIND>
 FR_DEV void ray_answer(void* __restrict__ out, uint32_t i, const TravState* ts) {
   if (KIND == 0) {
     const bool hit = ts && ts->best.leaf >= 0;
     static_cast<f4*>(out)[i] = hit ? mk4(ts->best.t, ts->best.beta, ts->best.gamma, __int_as_float(ts->best.prim))
                                    : mk4(INFINITY, 0.0f, 0.0f, __int_as_float(-1));
+  } else if (KIND == 2) {
+    const bool hit = ts && ts->best.leaf >= 0;
+    f4* rec = static_cast<f4*>(out) + (size_t)RS_ROWS * i;
+    rec[0] = hit ? mk4(ts->best.t, ts->best.beta, ts->best.gamma, __int_as_float(ts->best.prim))
+                 : mk4(INFINITY, 0.0f, 0.0f, __int_as_float(-1));
+    reinterpret_cast<int32_t*>(rec)[7] = hit ? ts->best.leaf : -1;
   } else {
     static_cast<float*>(out)[i] = ts ? (float)ts->atten : 1.0f;
   }
 }
-template <int KIND>
+// MASKED: masks[i] selects the models ray i sees (test_tri); a ray whose mask selects no model of the scene is
+// answered without traversal, as a degenerate ray is. The unmasked instantiations never read masks or rm.
+template <int KIND, bool MASKED>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(RQ_WAVES, RQ_WAVES))) void k_ray_queries(
-    DevScene sc, const f4* __restrict__ rays, uint32_t n, void* __restrict__ out, RayQueryState* __restrict__ rq) {
+    DevScene sc, const f4* __restrict__ rays, uint32_t n, void* __restrict__ out, RayQueryState* __restrict__ rq,
+    const uint32_t* __restrict__ masks, const RayModels rm) {
   __shared__ int32_t lds_stack[BVH_STACK * TRACE_BLOCK];
   Stack st{&lds_stack[threadIdx.x]};
   uint32_t q_next = 0, q_end = 0;  // wave-uniform chunk
@@ -1689,6 +1726,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(RQ_
   int qi = -1;                     // this lane's ray
   f3 o, d;
   float tmin, tmax;
+  uint32_t mask = 0;               // MASKED: this lane's ray's models
   TravState ts;
   while (true) {
     unsigned long long need = __ballot(qi < 0);
@@ -1718,7 +1756,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(RQ_
         const uint32_t i = q_next + lanes_below(need);
         if (i < q_end) {
           const f4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
-          if (ray_degenerate(a, b)) {
+          if (MASKED) mask = masks[i] & rm.valid;
+          if (ray_degenerate(a, b) || (MASKED && mask == 0)) {
             ray_answer<KIND>(out, i, nullptr);  // (the lane stays idle and takes another ray of the chunk)
           } else {
             qi = (int)i;
@@ -1732,26 +1771,70 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(RQ_
       need = __ballot(qi < 0);
     }
     if (!__ballot(qi >= 0)) break;
-    if (qi >= 0 && trav_step(sc, st, ts, o, d, tmin, tmax, KIND == 1)) {
+    if (qi >= 0 && trav_step<MASKED>(sc, st, ts, o, d, tmin, tmax, KIND == 1, mask, &rm)) {
       ray_answer<KIND>(out, (uint32_t)qi, &ts);
       qi = -1;
     }
   }
 }
 
+// The surface at the hits k_ray_queries<2> found (FR_RAYS_SURFACE): one lane per ray reads its ray, row 0 of its
+// record and the leaf index in word 7, and writes rows 1 to 4 as the closest-hit programs see the hit: surface() and
+// kd_of(), the G-buffer's and the megakernel's, unchanged. A separate launch keeps the traversal kernel's registers
+// and occupancy, and the divergent fetches of shading record, material and texels are made by full waves rather
+// than by the lanes of a traversing wave that happen to finish. A lane stores its four rows as four 16-B stores,
+// 64 consecutive bytes of its own record: the record's 80-B stride leaves no wider store aligned, and a stage
+// through LDS to make the wave's stores contiguous would add 5 KB of LDS and two barriers per block to a kernel
+// whose time is the texel and shading-record fetches (MEASUREMENTS.md, "Ray queries: surface and masks").
+#define RS_BLOCK 256
+__global__ __launch_bounds__(RS_BLOCK) void k_ray_surface(DevScene sc, const f4* __restrict__ rays, uint32_t n, f4* out,
+                                                          const RayModels rm) {
+  const uint32_t i = blockIdx.x * RS_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  f4* rec = out + (size_t)RS_ROWS * i;
+  const f4 r0 = rec[0];
+  const int leaf = reinterpret_cast<const int32_t*>(rec)[7];
+  if (leaf < 0) {  // a miss, a degenerate ray or an empty mask: model -1, every other word 0
+    rec[1] = mk4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    rec[2] = rec[3] = rec[4] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  const f4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
+  const f3 o = mk3(a.x, a.y, a.z), d = mk3(b.x, b.y, b.z);
+  Hit h;
+  h.t = r0.x; h.beta = r0.y; h.gamma = r0.z; h.leaf = leaf; h.prim = __float_as_int(r0.w);
+  const SurfaceHit s = surface(sc, h, o, d);
+  const f3 kd = kd_of(sc, s.mat, s.uv);
+  const int flags = (int)fbits(sc.shade[h.prim].t.w);
+  const TriGeo g = sc.tri_geo[leaf];
+  // refine_and_offset's side test, on the attribute normal
+  const int back = dotc(normalizec(mk3(g.c.y, g.c.z, g.c.w)), d) > 0.0f ? 1 : 0;
+  const int word = s.mat | sc.mats[s.mat].type << 8 | (flags & (FR_SHADE_HAS_NORMALS | FR_SHADE_HAS_UV)) << 8 | back << 18;
+  rec[1] = mk4(s.front.x, s.front.y, s.front.z, __int_as_float(ray_model_of(rm, h.prim)));
+  rec[2] = mk4(s.ng.x, s.ng.y, s.ng.z, s.uv.x);
+  rec[3] = mk4(s.ns.x, s.ns.y, s.ns.z, s.uv.y);
+  rec[4] = mk4(kd.x, kd.y, kd.z, __int_as_float(word));
+}
+
 // Resident blocks of k_ray_queries: RQ_WAVES waves per SIMD, 4 SIMDs per CU, 256 CUs (12 KB of LDS per block).
 static uint32_t ray_query_resident_blocks() { return 256u * 4u * RQ_WAVES / (TRACE_BLOCK / 64); }
 
-// kind: 0 closest hit (out: n records of 16 B), 1 transmittance (out: n floats). The counter of `rq` is zeroed in
-// stream order ahead of the kernel. max_blocks: the context's cap on the grid (FOVRT_RAYQ_BLOCKS), 0 = none.
-void launch_ray_queries(const DevScene& sc, const void* rays, uint32_t n, int kind, void* out, RayQueryState* rq,
-                        uint32_t max_blocks, hipStream_t stream) {
+// kind: 0 closest hit (out: n records of 16 B), 1 transmittance (out: n floats), 2 surface (out: n records of 80 B;
+// k_ray_surface follows on the same stream). masks: NULL, or n words (bit k: model k takes part). The counter of `rq`
+// is zeroed in stream order ahead of the kernel. max_blocks: the context's cap on the grid (FOVRT_RAYQ_BLOCKS), 0 = none.
+void launch_ray_queries(const DevScene& sc, const void* rays, const uint32_t* masks, uint32_t n, int kind, void* out,
+                        RayQueryState* rq, const RayModels& rm, uint32_t max_blocks, hipStream_t stream) {
   if (n == 0) return;
   uint32_t blocks = std::min((n + TRACE_BLOCK - 1) / TRACE_BLOCK, ray_query_resident_blocks());
   if (max_blocks) blocks = std::min(blocks, max_blocks);
   (void)hipMemsetAsync(rq, 0, sizeof(RayQueryState), stream);
-  hipLaunchKernelGGL(kind == 1 ? k_ray_queries<1> : k_ray_queries<0>, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc,
-                     static_cast<const f4*>(rays), n, out, rq);
+  auto k = masks ? (kind == 1 ? k_ray_queries<1, true> : kind == 2 ? k_ray_queries<2, true> : k_ray_queries<0, true>)
+                 : (kind == 1 ? k_ray_queries<1, false> : kind == 2 ? k_ray_queries<2, false> : k_ray_queries<0, false>);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(TRACE_BLOCK), 0, stream, sc, static_cast<const f4*>(rays), n, out, rq, masks,
+                     rm);
+  if (kind == 2)
+    hipLaunchKernelGGL(k_ray_surface, dim3((n + RS_BLOCK - 1) / RS_BLOCK), dim3(RS_BLOCK), 0, stream, sc,
+                       static_cast<const f4*>(rays), n, static_cast<f4*>(out), rm);
 }
 
 // ---------------------------------------------------------------------------------------------

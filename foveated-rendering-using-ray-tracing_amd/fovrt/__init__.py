@@ -36,8 +36,8 @@ FR_MEM_HOST, FR_MEM_DEVICE = 0, 1
 # fr_update_geometry: what becomes of the shading normals
 FR_NORMALS_KEEP, FR_NORMALS_GIVEN, FR_NORMALS_RECOMPUTE = 0, 1, 2
 # fr_trace_rays: what a query answers
-FR_RAYS_CLOSEST, FR_RAYS_TRANSMITTANCE = 0, 1
-RAY_KINDS = {"closest": FR_RAYS_CLOSEST, "transmittance": FR_RAYS_TRANSMITTANCE}
+FR_RAYS_CLOSEST, FR_RAYS_TRANSMITTANCE, FR_RAYS_SURFACE = 0, 1, 2
+RAY_KINDS = {"closest": FR_RAYS_CLOSEST, "transmittance": FR_RAYS_TRANSMITTANCE, "surface": FR_RAYS_SURFACE}
 MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 0, 1, 2, 3, 4
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
@@ -116,9 +116,20 @@ class fr_ray_hit(C.Structure):
     _fields_ = [("t", C.c_float), ("beta", C.c_float), ("gamma", C.c_float), ("prim", C.c_int32)]
 
 
-# fr_ray / fr_ray_hit as numpy record types (PathTracer.trace_rays)
+class fr_ray_surface(C.Structure):
+    _fields_ = [("t", C.c_float), ("beta", C.c_float), ("gamma", C.c_float), ("prim", C.c_int32),
+                ("point", C.c_float * 3), ("model", C.c_int32), ("ng", C.c_float * 3), ("u", C.c_float),
+                ("ns", C.c_float * 3), ("v", C.c_float), ("kd", C.c_float * 3), ("surface", C.c_int32)]
+
+
+# fr_ray / fr_ray_hit / fr_ray_surface as numpy record types (PathTracer.trace_rays)
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmin", np.float32), ("dir", np.float32, 3), ("tmax", np.float32)])
 RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("prim", np.int32)])
+RAY_SURFACE_DTYPE = np.dtype([("t", np.float32), ("beta", np.float32), ("gamma", np.float32), ("prim", np.int32),
+                              ("point", np.float32, 3), ("model", np.int32), ("ng", np.float32, 3), ("u", np.float32),
+                              ("ns", np.float32, 3), ("v", np.float32), ("kd", np.float32, 3), ("surface", np.int32)])
+_RAY_RESULT = {FR_RAYS_CLOSEST: RAY_HIT_DTYPE, FR_RAYS_TRANSMITTANCE: np.dtype(np.float32),
+               FR_RAYS_SURFACE: RAY_SURFACE_DTYPE}
 
 
 class fr_scene_arrays(C.Structure):
@@ -200,6 +211,9 @@ _SIGS = {
     "fr_trace_rays": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
     "fr_trace_rays_enqueue": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p],
     "fr_rays_consumed": [C.c_void_p, C.c_void_p],
+    "fr_ray_query_reserve_kind": [C.c_void_p, C.c_size_t, C.c_int, C.c_int],
+    "fr_trace_rays_masked": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
+    "fr_trace_rays_masked_enqueue": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p],
     "fr_set_geometry_overlap": [C.c_void_p, C.c_int],
     "fr_geometry_update_status": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fr_rebuild_bvh_enqueue": [C.c_void_p],
@@ -737,41 +751,74 @@ class PathTracer:
         (48 B per ray on the device; grows only). Waits for the context's pending work."""
         self._check(_lib.fr_ray_query_reserve(self._ctx, int(n)))
 
-    def trace_rays(self, rays, kind="closest", out=None, n=None):
+    def ray_query_reserve_kind(self, n, kind="closest", masked=False):
+        """fr_ray_query_reserve_kind: the same staging area sized for n rays of one kind: 32 B per ray, the kind's
+        result (16, 4 or 80 B) and 4 B when masked (grows only). Waits for the context's pending work."""
+        self._check(_lib.fr_ray_query_reserve_kind(self._ctx, int(n), self._ray_kind(kind), int(bool(masked))))
+
+    def trace_rays(self, rays, kind="closest", out=None, n=None, masks=None):
         """fr_trace_rays: a batch of rays against the scene as it is now, waiting for the answers.
         rays: a numpy array of n x 8 float32, rows (origin, tmin, dir, tmax), or RAY_DTYPE records; the answers come
         back as numpy: RAY_HIT_DTYPE records (t, beta, gamma, prim; a miss is (inf, 0, 0, -1)) for "closest", n
-        float32 for "transmittance". The staging area is reserved on demand. Or rays: a device pointer or an object
-        with data_ptr() (n x 8 float32 on this context's device; n defaults to its numel() // 8), with `out` the
-        same kind of array for the answers (n x 16 B, or n floats); returns `out`."""
+        float32 for "transmittance", RAY_SURFACE_DTYPE records (the hit, then point, model, ng, u, ns, v, kd and the
+        material word; include/fovrt.h) for "surface". The staging area is reserved on demand. Or rays: a device
+        pointer or an object with data_ptr() (n x 8 float32 on this context's device; n defaults to its
+        numel() // 8), with `out` the same kind of array for the answers (n x 16 B, n floats, or n x 80 B); returns
+        `out`. masks (fr_trace_rays_masked): one uint32 per ray, bit k set: model k of models() takes part in that
+        ray; memory of the same kind as rays."""
         k = self._ray_kind(kind)
+        plain = masks is None and k != FR_RAYS_SURFACE
         if isinstance(rays, np.ndarray):
             a = np.ascontiguousarray(rays.view(np.float32) if rays.dtype == RAY_DTYPE else rays, dtype=np.float32)
             a = a.reshape(-1, 8)
             cnt = a.shape[0]
-            res = np.empty(cnt, RAY_HIT_DTYPE if k == FR_RAYS_CLOSEST else np.float32)
-            self.ray_query_reserve(cnt)  # (allocates only when the request grows)
-            self._check(_lib.fr_trace_rays(self._ctx, C.c_void_p(a.ctypes.data), cnt, FR_MEM_HOST, k,
-                                           C.c_void_p(res.ctypes.data)))
+            res = np.empty(cnt, _RAY_RESULT[k])
+            if plain:
+                self.ray_query_reserve(cnt)  # (allocates only when the request grows)
+                self._check(_lib.fr_trace_rays(self._ctx, C.c_void_p(a.ctypes.data), cnt, FR_MEM_HOST, k,
+                                               C.c_void_p(res.ctypes.data)))
+                return res
+            m = None
+            if masks is not None:
+                m = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+                if m.shape[0] != cnt:
+                    raise ValueError("masks needs one uint32 per ray")
+            self.ray_query_reserve_kind(cnt, k, m is not None)
+            self._check(_lib.fr_trace_rays_masked(self._ctx, C.c_void_p(a.ctypes.data),
+                                                  C.c_void_p(m.ctypes.data) if m is not None else None, cnt,
+                                                  FR_MEM_HOST, k, C.c_void_p(res.ctypes.data)))
             return res
         if out is None:
             raise ValueError("device rays need out, a device array for the answers")
         if n is None:
             n = rays.numel() // 8
-        self._check(_lib.fr_trace_rays(self._ctx, self._device_ptr(rays), int(n), FR_MEM_DEVICE, k,
-                                       self._device_ptr(out)))
+        if plain:
+            self._check(_lib.fr_trace_rays(self._ctx, self._device_ptr(rays), int(n), FR_MEM_DEVICE, k,
+                                           self._device_ptr(out)))
+        else:
+            self._check(_lib.fr_trace_rays_masked(self._ctx, self._device_ptr(rays),
+                                                  self._device_ptr(masks) if masks is not None else None, int(n),
+                                                  FR_MEM_DEVICE, k, self._device_ptr(out)))
         return out
 
-    def trace_rays_enqueue(self, rays, out, n=None, kind="closest", ready_event=None):
+    def trace_rays_enqueue(self, rays, out, n=None, kind="closest", ready_event=None, masks=None):
         """fr_trace_rays_enqueue: trace_rays over device arrays in stream order, without waiting for the GPU. The
-        query sees the scene as of this call's place among the enqueued updates, poses and rebuilds. rays, out: device
-        pointers or objects with data_ptr(); ready_event as in update_geometry_enqueue. Keep both arrays untouched
-        until rays_consumed() has ordered your stream behind the query."""
+        query sees the scene as of this call's place among the enqueued updates, poses and rebuilds. rays, out, masks:
+        device pointers or objects with data_ptr(); ready_event as in update_geometry_enqueue. Keep the arrays
+        untouched until rays_consumed() has ordered your stream behind the query. kind "surface" and masks go through
+        fr_trace_rays_masked_enqueue."""
         if n is None:
             n = rays.numel() // 8
         ev = getattr(ready_event, "cuda_event", ready_event)
-        self._check(_lib.fr_trace_rays_enqueue(self._ctx, self._device_ptr(rays), int(n), self._ray_kind(kind),
-                                               self._device_ptr(out), C.c_void_p(int(ev)) if ev else None))
+        k = self._ray_kind(kind)
+        if masks is None and k != FR_RAYS_SURFACE:
+            self._check(_lib.fr_trace_rays_enqueue(self._ctx, self._device_ptr(rays), int(n), k,
+                                                   self._device_ptr(out), C.c_void_p(int(ev)) if ev else None))
+        else:
+            self._check(_lib.fr_trace_rays_masked_enqueue(self._ctx, self._device_ptr(rays),
+                                                          self._device_ptr(masks) if masks is not None else None,
+                                                          int(n), k, self._device_ptr(out),
+                                                          C.c_void_p(int(ev)) if ev else None))
 
     def rays_consumed(self, stream=None):
         """fr_rays_consumed: `stream` (a torch stream, a raw hipStream_t, or None for the null stream) waits on the

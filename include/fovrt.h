@@ -649,7 +649,8 @@ int fr_geometry_update_status(fr_ctx* ctx, uint64_t* applied, uint64_t* rejected
  * synchronous form works there). n == 0 is FR_OK and enqueues nothing.
  * A query touches no image buffer, no temporal state, no counter of fr_stats: query rays are not counted, nothing of
  * the JumpFlooding reuse, and no schedule of another context.
- * Not covered: groups in stream order, per-ray masks, shading attributes of the hit (fr_scene_export has them). */
+ * Not covered by these two calls: groups in stream order; the surface at the hit and per-ray model masks are the
+ * masked calls' (below). */
 typedef struct fr_ray     { float origin[3]; float tmin; float dir[3]; float tmax; } fr_ray;      /* 32 B */
 typedef struct fr_ray_hit { float t; float beta, gamma; int32_t prim; } fr_ray_hit;               /* 16 B */
 #define FR_RAYS_CLOSEST       0   /* out: n fr_ray_hit */
@@ -658,6 +659,70 @@ int fr_ray_query_reserve(fr_ctx* ctx, size_t max_rays);
 int fr_trace_rays(fr_ctx* ctx, const void* rays, size_t n, int where, int kind, void* out);
 int fr_trace_rays_enqueue(fr_ctx* ctx, const void* rays, size_t n, int kind, void* out, void* ready_event);
 int fr_rays_consumed(fr_ctx* ctx, void* stream);
+/* Ray queries, second part: the surface at the hit, and per-ray model masks. fr_trace_rays_masked and
+ * fr_trace_rays_masked_enqueue are fr_trace_rays and fr_trace_rays_enqueue with two additions; with masks == NULL and
+ * one of the two kinds above they are those calls exactly. fr_trace_rays and fr_trace_rays_enqueue themselves keep
+ * their two kinds and refuse FR_RAYS_SURFACE as a bad kind, as they always have.
+ * FR_RAYS_SURFACE (out: n fr_ray_surface records of 80 B, five 16-byte rows; a device `out` is 16-byte aligned): the
+ * FR_RAYS_CLOSEST answer followed by the closest-hit programs' view of that hit, as the G-buffer and the path trace
+ * compute it. Every field has one right answer in bytes: fp32, the fmas written out below, dot products contracted
+ * and normalize as the reference's PTX has them and as every kernel of the engine does.
+ *   row 0          the fr_ray_hit FR_RAYS_CLOSEST returns for this ray: same window, tie rule and guaranteed domain.
+ *   attribute normal  g = normalize(n), n the stored normal of the hit's leaf triangle (cross(p0 - p2, p1 - p0), each
+ *                  product rounded), not a recomputation from positions.
+ *   ng             normalize(g): the reference normalises the attribute a second time.
+ *   ns             a = normalize(fma(w, n0, fma(beta, n1, gamma * n2))), w = 1 - beta - gamma, per component;
+ *                  ns = normalize(a) for a triangle with flags & 0x100, else ns = ng.
+ *   (u, v)         fma(w, t0, fma(beta, t1, gamma * t2)) per component when flags & 0x200, else (0, 0).
+ *   point          the front point of refine_and_offset(fma(t, d, o), d, g, p0), p0 the leaf triangle's first vertex;
+ *                  d as given, not normalised.
+ *   kd             .xyz of the Kd texture lookup at (u, v): REPEAT wrap, bilinear with 8-bit fractions, the texture
+ *                  of material m = flags & 0xff.
+ *   model          the i with first_tri[i] <= prim < first_tri[i + 1] (fr_model_info).
+ *   surface        m | type << 8 | (flags & 0x300) << 8 | back << 18: type the material's 0 (diffuse), 1
+ *                  (reflection) or 2 (refraction); bits 16 and 17 say the triangle has normals and uv; back = 1 when
+ *                  dot(g, d) > 0, the side test refine_and_offset makes.
+ *   a miss, a degenerate ray, a mask that selects no model: row 0 is the miss record, model = -1, every other word 0.
+ * For the camera ray of a pixel (tmin = the scene epsilon 1e-3, tmax = +inf) point equals POSITION.xyz,
+ * fma(ng, 0.5, 0.5) equals NORMAL.xyz, kd equals DIFFUSE.xyz as values and the class of type equals GCLASS, after
+ * fr_geometry_launch on the same scene.
+ * masks: NULL, or n words, one per ray: bit k set means model k (fr_model_info's order) takes part in that ray. Bits
+ * at or above the model count are ignored. A ray whose mask selects no model is answered without traversal, as a
+ * degenerate ray is. FR_RAYS_CLOSEST and FR_RAYS_SURFACE then answer the closest hit among the triangles of the
+ * selected models, with the tie rule among them; for FR_RAYS_TRANSMITTANCE an excluded model neither blocks nor
+ * attenuates. The answers equal brute force over the selected models' triangles under the terms above (bit for bit in
+ * the guaranteed domain; transmittance exactly 0 and 1, within one ulp between). With masks, the power of a
+ * refractive crossing's Schlick term is rounded once ((1 - |ns.d|)^5 in f64, then to fp32), where the unmasked kind
+ * and the frame's shadow rays take the platform's powf: a masked transmittance with every bit set and the unmasked one
+ * agree in their exact zeros and ones and may differ in the last bits between. The unmasked kind therefore holds the
+ * one-ulp bound against the restatement on unit directions only, where it was measured; on directions of other lengths
+ * its answers have been seen up to 94 ulp away. Making the two forms one means changing the frame's shadow ray, and is
+ * left as follow-up work. The tree is walked as without masks:
+ * a candidate is dropped after its triangle test accepts it, so a mask never makes a query cheaper than its traversal.
+ * Stream order, the scene a query sees, ready_event and fr_rays_consumed are as above; fr_rays_consumed also covers
+ * the reads of masks. where applies to rays, masks and out alike.
+ * Host staging: fr_ray_query_reserve(n) keeps meaning 48 B per ray, and a host batch of the first two kinds without
+ * masks is accepted when n is within it. fr_ray_query_reserve_kind sizes the same area for max_rays rays of one kind:
+ * 32 B per ray, plus the kind's result (16, 4 or 80 B), plus 4 B when masked; it grows the area only, waits for
+ * pending work, and fails with FR_E_NOMEM keeping what was there. A host batch with masks or of FR_RAYS_SURFACE is
+ * accepted when its bytes fit the area. No query call allocates.
+ * Refused at once, nothing enqueued, out untouched (FR_E_INVALID): what the calls above refuse, with an 80-byte stride
+ * in the overlap test of FR_RAYS_SURFACE; a device masks pointer not 4-byte aligned; masks overlapping out; a host
+ * batch above the area. FR_E_UNSUPPORTED: the enqueued form on a rank of a group or a sharded context; masks or
+ * FR_RAYS_SURFACE on a scene of more than FR_MAX_MODELS models.
+ * Not covered: groups in stream order, per-ray windows beyond tmin / tmax, any-hit callbacks, instance transforms. */
+typedef struct fr_ray_surface {
+  float t, beta, gamma; int32_t prim;   /* row 0: the fr_ray_hit of FR_RAYS_CLOSEST */
+  float point[3];       int32_t model;  /* row 1: front_hit_point; index into fr_model_info */
+  float ng[3];          float   u;      /* row 2: world_geometric_normal; texcoord.x */
+  float ns[3];          float   v;      /* row 3: world_shading_normal; texcoord.y */
+  float kd[3];          int32_t surface;/* row 4: the Kd lookup at (u, v); material word */
+} fr_ray_surface;                       /* 80 B */
+#define FR_RAYS_SURFACE 2   /* out: n fr_ray_surface; the masked calls only */
+int fr_ray_query_reserve_kind(fr_ctx* ctx, size_t max_rays, int kind, int masked);
+int fr_trace_rays_masked(fr_ctx* ctx, const void* rays, const uint32_t* masks, size_t n, int where, int kind, void* out);
+int fr_trace_rays_masked_enqueue(fr_ctx* ctx, const void* rays, const uint32_t* masks, size_t n, int kind, void* out,
+                                 void* ready_event);
 /* The scene's models, posed by matrix on the device. A scene is assembled from rigid models (ground, box, bunny,
  * earth, vokselia_spawn: PathTracer::load_obj's meshes with their transforms baked in), each a contiguous range of
  * the scene's triangles. The ranges partition [0, num_tris) in scene order: fr_model_count gives their number,

@@ -259,6 +259,34 @@ class PathTracer {
     check(fr_trace_rays_enqueue(ctx(), rays, n, kind, out, ready_event), ctx_, "trace_rays_enqueue");
   }
   void rays_consumed(void* stream = nullptr) { check(fr_rays_consumed(ctx(), stream), ctx_, "rays_consumed"); }
+  // The surface at the hit (FR_RAYS_SURFACE) and per-ray model masks (fr_trace_rays_masked): masks holds one word
+  // per ray, bit k set: model k of models() takes part in that ray; an empty masks vector is the unmasked query.
+  void ray_query_reserve_kind(size_t n, int kind, bool masked) {
+    check(fr_ray_query_reserve_kind(ctx(), n, kind, masked ? 1 : 0), ctx_, "ray_query_reserve_kind");
+  }
+  std::vector<fr_ray_surface> trace_surface(const std::vector<fr_ray>& rays, const std::vector<uint32_t>& masks = {}) {
+    std::vector<fr_ray_surface> out(rays.size());
+    trace_masked(rays, masks, FR_RAYS_SURFACE, out.data(), "trace_surface");
+    return out;
+  }
+  std::vector<fr_ray_hit> trace_rays(const std::vector<fr_ray>& rays, const std::vector<uint32_t>& masks) {
+    std::vector<fr_ray_hit> out(rays.size());
+    trace_masked(rays, masks, FR_RAYS_CLOSEST, out.data(), "trace_rays");
+    return out;
+  }
+  std::vector<float> trace_transmittance(const std::vector<fr_ray>& rays, const std::vector<uint32_t>& masks) {
+    std::vector<float> out(rays.size());
+    trace_masked(rays, masks, FR_RAYS_TRANSMITTANCE, out.data(), "trace_transmittance");
+    return out;
+  }
+  // device arrays (masks: n words or nullptr), waiting for the answers, and in stream order
+  void trace_rays(const void* rays, const uint32_t* masks, size_t n, int kind, void* out) {
+    check(fr_trace_rays_masked(ctx(), rays, masks, n, FR_MEM_DEVICE, kind, out), ctx_, "trace_rays");
+  }
+  void trace_rays_enqueue(const void* rays, const uint32_t* masks, size_t n, int kind, void* out,
+                          void* ready_event = nullptr) {
+    check(fr_trace_rays_masked_enqueue(ctx(), rays, masks, n, kind, out, ready_event), ctx_, "trace_rays_enqueue");
+  }
   // triangle indices (fr_ray_hit::prim) to model indices, the order of models(); -1 for a miss
   std::vector<int> model_of(const std::vector<int32_t>& prims) {
     const std::vector<Model> ms = models();
@@ -364,6 +392,14 @@ class PathTracer {
   AccumFrame m_accumFrame{&ctx_};
 
  private:
+  // the host forms of the masked queries: reserve the staging area for the kind, then fr_trace_rays_masked
+  void trace_masked(const std::vector<fr_ray>& rays, const std::vector<uint32_t>& masks, int kind, void* out,
+                    const char* what) {
+    if (!masks.empty() && masks.size() != rays.size()) throw std::invalid_argument("masks: one word per ray");
+    ray_query_reserve_kind(rays.size(), kind, !masks.empty());  // (allocates only when the request grows)
+    check(fr_trace_rays_masked(ctx(), rays.data(), masks.empty() ? nullptr : masks.data(), rays.size(), FR_MEM_HOST,
+                               kind, out), ctx_, what);
+  }
   fr_config cfg_{};
   fr_ctx* ctx_ = nullptr;
   std::string error_;

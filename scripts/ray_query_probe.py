@@ -7,7 +7,12 @@ Query throughput (arm T): the synchronous device form of fr_trace_rays over
 each timed by a host clock around the call (which ends in a synchronise of the context stream), 3 warm-up calls and
 10 timed ones; beside them fr_geometry_launch's own time over the same camera rays (its events), the only other
 kernel that traces them (it also writes five images: a reference point, not a bar). Arm G is that launch alone on an
-older build (--lib), the parent commit's.
+older build (--lib), the parent commit's; arm Tp is arm T's three sets on that build. On this build arm T goes on with
+  surface           the raster rays answered as 80-byte fr_ray_surface records (two kernels)
+  masked_all        raster, closest hit, every model's bit set in every mask
+  masked_no_ground  the same with model 0 left out
+  shadow_masked_all the shadow set, every model's bit set
+and arm S is the surface query alone, a few calls: the process to take a kernel trace of.
 
 Pipelined frame rate: untimed fr_frame in a loop, 30 warm-up frames and 120 timed ones per round (host clock, the
 context synchronised before and after), throughput mode, then latency mode.
@@ -76,10 +81,17 @@ def child(arm, W, H, rounds):
     import fovrt
     t = tracer(fovrt, W, H)
     common = dict(arm=arm, width=W, height=H, lib="older" if os.environ.get("FOVRT_LIB") else "built")
-    if arm in ("T", "G"):
+    if arm == "S":  # the surface query alone, a few calls: the process a kernel trace is taken of
+        rays = camera_rays(torch, fovrt, W, H)
+        n = rays.shape[0]
+        out = torch.empty((n, 20), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        ms = timed_calls(lambda: t.trace_rays(rays, "surface", out=out, n=n))
+        print(json.dumps(dict(kind="query", set="surface", rays=n, ms=ms, **common)), flush=True)
+    elif arm in ("T", "Tp", "G"):
         g = [t.geometry_launch() for _ in range(13)][3:]
         print(json.dumps(dict(kind="geometry_launch", ms=g, rays=W * H, **common)), flush=True)
-        if arm == "T":
+        if arm in ("T", "Tp"):
             rays = camera_rays(torch, fovrt, W, H)
             n = rays.shape[0]
             out = torch.empty((n, 4), dtype=torch.float32, device="cuda:0")
@@ -106,6 +118,24 @@ def child(arm, W, H, rounds):
             print(json.dumps(dict(kind="check", shuffled_hit_share=float(hits.mean()),
                                   gbuffer_hit_share=float(hit.float().mean()),
                                   shadow_mean=float(sout.mean()), **common)), flush=True)
+            if arm == "T":  # the second part's kinds, on this build only
+                surf = torch.empty((n, 20), dtype=torch.float32, device="cuda:0")
+                nm = len(t.models())
+                every = torch.full((n,), (1 << nm) - 1, dtype=torch.int32, device="cuda:0")
+                no_ground = torch.full((n,), ((1 << nm) - 1) & ~1, dtype=torch.int32, device="cuda:0")
+                every_s = every[:shadow.shape[0]].contiguous()
+                torch.cuda.synchronize()
+                for name, rr, kind, o, m in (("surface", rays, "surface", surf, None),
+                                             ("masked_all", rays, "closest", out, every),
+                                             ("masked_no_ground", rays, "closest", out, no_ground),
+                                             ("shadow_masked_all", shadow, "transmittance", sout, every_s)):
+                    k = rr.shape[0]
+                    ms = timed_calls(lambda: t.trace_rays(rr, kind, out=o, n=k, masks=m))
+                    print(json.dumps(dict(kind="query", set=name, rays=k, ms=ms,
+                                          mrays_per_s=k / (statistics.median(ms) * 1e-3) / 1e6, **common)), flush=True)
+                    if kind == "closest":
+                        h = out.cpu().numpy().view(fovrt.RAY_HIT_DTYPE).reshape(-1)["prim"] >= 0
+                        print(json.dumps(dict(kind="check", set=name, hit_share=float(h.mean()), **common)), flush=True)
     else:
         rays = out = None
         if arm == "Q":
@@ -142,14 +172,15 @@ def main():
     args = ap.parse_args()
     if args.arm:
         return child(args.arm, args.width, args.height, args.rounds)
-    arms = tuple(args.arms.split(",")) + (("G", "p") if args.lib else ())
+    arms = tuple(args.arms.split(","))
+    arms += tuple(a for a in ("G", "p", "Tp") if args.lib and a not in arms)
     rows = []
     for rep in range(args.reps):
         for arm in (arms if rep % 2 == 0 else arms[::-1]):
-            if arm in ("T", "G") and rep >= 2:
+            if arm in ("T", "Tp", "G", "S") and rep >= 2:
                 continue  # (two processes of each are enough: their calls repeat inside)
             env = dict(os.environ)
-            if arm in ("G", "p"):
+            if arm in ("G", "p", "Tp"):
                 env.update(FOVRT_LIB=os.path.abspath(args.lib), FOVRT_LIB_OLDER="1")
             res = subprocess.run([sys.executable, os.path.abspath(__file__), "--arm", arm, "--width", str(args.width),
                                   "--height", str(args.height), "--rounds", str(args.rounds)], env=env, check=True,
