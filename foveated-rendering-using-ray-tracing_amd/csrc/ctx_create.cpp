@@ -407,7 +407,7 @@ int fr_destroy(fr_ctx* c) {
   for (hipStream_t s : streams) if (s) hipStreamSynchronize(s);
   auto fr = [](void* p) { if (p) hipFree(p); };
   fri::tree_free(&c->tree); fri::tree_free(&c->spare);
-  fr(c->d_shade); fr(c->d_pos); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back);
+  fr(c->d_shade); fr(c->d_pos); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back); fr(c->vis_pos);
   fr(c->pose_rest_pos); fr(c->pose_rest_nrm); fr(c->pose_stage_pos); fr(c->pose_stage_nrm);
   if (c->bvh_work) bvh_work_free(c->bvh_work);
   if (c->sah_work) sah_work_free(c->sah_work);

@@ -36,6 +36,26 @@ void fri::adopt_spare(fr_ctx* c, bool with_shade) {
   point_dsc(c);
 }
 
+// Per-model visibility: the valid bits of a mask, and the positions a tree writer reads. Every call that builds or
+// refits the tree goes through tree_positions with the array it would read: with every model visible (every context
+// that never hid one) that array itself comes back and nothing is launched; while a model is hidden k_hide writes its
+// collapsed copy into vis_pos on `s`, the writer's stream, ahead of the writer (k_visibility.hip).
+static uint32_t vis_valid(const fr_ctx* c) {
+  const size_t nm = c->scene.model_tri_count.size();
+  return nm >= 32 ? 0xFFFFFFFFu : (1u << nm) - 1u;
+}
+static int tree_positions(fr_ctx* c, const f3* pos, hipStream_t s, const f3** out) {
+  *out = pos;
+  if (!(~c->vis_mask & vis_valid(c)) || !c->vis_pos) return FR_OK;
+  const int nm = (int)c->scene.model_tri_count.size(), nt = c->scene.num_tris();
+  int first[FR_MAX_MODELS];
+  for (int i = 0; i < nm; i++) model_info(c->scene, i, nullptr, &first[i], nullptr);
+  std::string err;
+  if (!gpu_hide_enqueue(hide_args(first, nm, nt, c->vis_mask), pos, c->vis_pos, nt, s, err)) return fail(c, FR_E_HIP, err);
+  *out = c->vis_pos;
+  return FR_OK;
+}
+
 // GPU build over `pos` (device; k_bvh.hip) into the spare arrays, which become the scene's tree when every
 // step succeeded (the old tree becomes the spare). No allocation after the first rebuild, no read-back
 // of the tree: the host keeps its node count, stack need and depth (fr_scene_export).
@@ -46,6 +66,7 @@ int fri::gpu_rebuild(fr_ctx* c, const f3* pos) {
     c->err = "GPU BVH: device allocation failed";
     return FR_E_NOMEM;
   }
+  if (int rc = tree_positions(c, pos, c->stream, &pos)) return rc;
   int nn = 0, max_stack = 0, depth = 0;
   std::string err;
   // the context's builder: the LBVH, or on a bvh_builder 2 context the binned SAH of k_bvh_sah.hip
@@ -112,6 +133,7 @@ int fri::tree_numbers(fr_ctx* c) {
 // and synchronised the context stream.
 static int gpu_refit(fr_ctx* c, const f3* pos) {
   if (int rc = tree_numbers(c)) return rc;
+  if (int rc = tree_positions(c, pos, c->stream, &pos)) return rc;
   std::string err;
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
   if (!gpu_refit_bvh(c->bvh_work, pos, c->scene.num_tris(), c->tree, nn, c->stream, err)) {
@@ -351,6 +373,22 @@ int fr_update_geometry(fr_ctx* c, const void* xyz, const void* nrm, size_t ntris
 //    order (nodes_dev); a host reader waits and fetches them (tree_numbers); a frame needs none of them;
 //  - a build that fails on the device reads the tree in use (the source of its last kernel's copy), which the
 //    previous update or rebuild wrote earlier on this stream.
+// Per-model visibility (fr_set_model_visibility_enqueue, and tree_positions inside the update and the rebuild) adds one
+// array, vis_pos, and one kernel, k_hide, which writes it right ahead of the tree writer that reads it, on that
+// writer's stream. One array is enough in both modes:
+//  - every enqueued writer and reader of vis_pos (k_hide; the refit, gated or not, in place or out of place; the
+//    builders' first kernels) runs on GeoEnqueue's stream, so they are serial there: a k_hide starts after the
+//    previous tree writer has read what the previous k_hide wrote;
+//  - the synchronous tree writers (gpu_rebuild, gpu_refit) run on the context stream behind quiesce, which waits for
+//    update_done, so for everything front_stream has enqueued; and they finish before the host enqueues anything else
+//    (both wait for their result), so a later k_hide on either stream finds vis_pos free;
+//  - nothing else reads vis_pos: frames and ray queries read the tree, never the positions the tree was made from (the
+//    motion form of the G-buffer reads d_pos and prev_pos, the true positions, and only for triangles a ray has hit,
+//    which a hidden triangle never is);
+//  - a change of mode (fr_set_geometry_overlap) waits for the context's pending work.
+// k_hide reads the array the writer would read (d_pos; the array that becomes d_pos, behind k_take_over), which that
+// writer's own fences already guard. The visibility call itself rotates no positions and writes no shading record in
+// place; overlapped it brings the records along as the rebuild does (the KEEP copy) and swaps set and records together.
 // The preamble of both (the caller has set the device): the stream, and the waits the notes above name.
 struct GeoEnqueue {
   fr_ctx* c;
@@ -408,8 +446,13 @@ static int enqueue_update(fr_ctx* c, const std::string& name, const void* xyz, c
   const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
   // (behind an enqueued rebuild the host's count is stale: the refit takes the tree's from its device record)
   const uint32_t* nn_dev = c->tree_on_device ? &c->rb->tree[c->desc_cur].nodes : nullptr;
-  if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, c->spare_pos, nt, c->tree, nn, c->spare, reject, nn_dev, s, err)
-              : !gpu_refit_bvh_enqueue(c->bvh_work, c->spare_pos, nt, c->tree, nn, reject, nn_dev, s, err))
+  // (a hidden model: k_hide behind k_take_over, over the array that becomes d_pos; after a rejected update that is the
+  // current positions again, so it reproduces the collapsed ones the tree was made from, and the gated refit writes
+  // nothing, as without it)
+  const f3* tree_pos = nullptr;
+  if (int rc = tree_positions(c, c->spare_pos, s, &tree_pos)) return rc;
+  if (overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, tree_pos, nt, c->tree, nn, c->spare, reject, nn_dev, s, err)
+              : !gpu_refit_bvh_enqueue(c->bvh_work, tree_pos, nt, c->tree, nn, reject, nn_dev, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   rotate_positions(c);
   c->pos_mirror_stale = true;
@@ -513,8 +556,10 @@ static int enqueue_rebuild(fr_ctx* c, const std::string& name, const float* rati
   if (ratio && !gpu_rebuild_decide_enqueue(c->bvh_work, c->rb, c->tree.nodes, std::max(t.src_host_nodes, 0), nt,
                                            c->tree_on_device ? &t.src_desc->nodes : nullptr, *ratio, c->base_stale, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
-  if (sah ? !gpu_build_bvh_sah_enqueue(c->sah_work, c->bvh_work, c->d_pos, nt, t, s, err)
-          : !gpu_build_bvh_enqueue(c->bvh_work, c->d_pos, nt, t, s, err))
+  const f3* tree_pos = nullptr;  // (a hidden model: the build reads the collapsed positions)
+  if (int rc = tree_positions(c, c->d_pos, s, &tree_pos)) return rc;
+  if (sah ? !gpu_build_bvh_sah_enqueue(c->sah_work, c->bvh_work, tree_pos, nt, t, s, err)
+          : !gpu_build_bvh_enqueue(c->bvh_work, tree_pos, nt, t, s, err))
     return fail(c, FR_E_HIP, name + ": " + err);
   if (ratio && !gpu_rebuild_rebase_enqueue(c->bvh_work, t, nt, s, err)) return fail(c, FR_E_HIP, name + ": " + err);
   c->base_stale = !ratio;  // (the unconditional build installs a tree whose cost nobody has evaluated)
@@ -683,6 +728,100 @@ int fr_model_transforms(fr_ctx* c, float* m, size_t nmodels) {
   memcpy(m, c->pose_m.data(), c->pose_m.size() * sizeof(float));
   return FR_OK;
 }
+
+// Per-model visibility (the rule: include/fovrt.h; the positions a tree writer reads: tree_positions, above).
+int fr_model_visibility_enable(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_model_visibility_enable";
+  if (on != 0 && on != 1) return fail(c, FR_E_INVALID, name + ": on is 0 or 1");
+  if (!on) {
+    if (~c->vis_mask & vis_valid(c)) return fail(c, FR_E_STATE, name + ": a model is hidden (show every model first)");
+    c->vis_on = false;
+    return FR_OK;
+  }
+  if (c->scene.model_tri_count.size() > FR_MAX_MODELS)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the scene has more than FR_MAX_MODELS models");
+  if (int rc = quiesce(c)) return rc;
+  if (!c->vis_pos) {
+    const size_t bytes = pose_array_bytes(std::max(c->scene.num_tris(), 1));
+    if (hipMalloc((void**)&c->vis_pos, bytes) != hipSuccess || hipMemset(c->vis_pos, 0, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      if (c->vis_pos) hipFree(c->vis_pos);
+      c->vis_pos = nullptr;
+      return fail(c, FR_E_NOMEM, name + ": device allocation (collapsed positions) failed");
+    }
+    // k_hide's code object is loaded now (HIP loads a module at its first launch, 0.7 to 1 ms measured): one launch
+    // with nothing hidden, a plain copy into the new array, so that no enqueued call pays for it
+    const int nt = c->scene.num_tris();
+    std::string err;
+    if (!gpu_hide_enqueue(hide_args(nullptr, 0, nt, FR_VISIBLE_ALL), c->d_pos, c->vis_pos, nt, c->stream, err))
+      return fail(c, FR_E_HIP, name + ": " + err);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->vis_on = true;
+  return FR_OK;
+}
+
+int fr_set_model_visibility(fr_ctx* c, uint32_t visible, int how) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_model_visibility";
+  if (how != FR_BVH_REBUILD && how != FR_BVH_REFIT) return fail(c, FR_E_INVALID, name + ": bad update kind");
+  if (!c->vis_on) return fail(c, FR_E_STATE, name + ": model visibility is not enabled (fr_model_visibility_enable)");
+  if (int rc = quiesce(c)) return rc;
+  // the tree writers read the mask in place: it goes back when they fail (a failed rebuild leaves the tree it found)
+  const uint32_t before = c->vis_mask;
+  c->vis_mask = visible & vis_valid(c);
+  if (const int rc = how == FR_BVH_REBUILD ? gpu_rebuild(c, c->d_pos) : gpu_refit(c, c->d_pos)) {
+    c->vis_mask = before;
+    return fail(c, rc, name + ": " + c->err);
+  }
+  c->base_stale = true;  // (a conditional rebuild adopts this tree's cost first: showing a model is not growth)
+  return FR_OK;
+}
+
+// The refit of fr_set_model_visibility in stream order, under GeoEnqueue as an update is: k_hide, then the refit
+// nothing gates (geo->accept is the verdict word where a kernel wants one), in place or, overlapped, into the other
+// set with the shading records copied along. Positions do not rotate; nothing waits, is copied or allocated.
+int fr_set_model_visibility_enqueue(fr_ctx* c, uint32_t visible) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_set_model_visibility_enqueue";
+  if (!c->vis_on) return fail(c, FR_E_STATE, name + ": model visibility is not enabled (fr_model_visibility_enable)");
+  if (c->group_refs > 0 || c->U.shard_count > 1)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded (use fr_set_model_visibility)");
+  if (!c->bvh_work || !c->geo) return fail(c, FR_E_UNSUPPORTED, name + ": GPU BVH refit: no workspace for this tree");
+  hipSetDevice(c->cfg.device);
+  const GeoEnqueue g(c);
+  const uint32_t before = c->vis_mask;
+  c->vis_mask = visible & vis_valid(c);
+  const f3* tree_pos = nullptr;
+  if (int rc = tree_positions(c, c->d_pos, g.s, &tree_pos)) {
+    c->vis_mask = before;
+    return rc;
+  }
+  const int nt = c->scene.num_tris();
+  const int nn = c->bvh.root_count > 0 ? 0 : tree_nodes(c->bvh);
+  const uint32_t* accept = &c->geo->accept;
+  const uint32_t* nn_dev = c->tree_on_device ? &c->rb->tree[c->desc_cur].nodes : nullptr;
+  std::string err;
+  if (g.overlap ? !gpu_refit_bvh_to_enqueue(c->bvh_work, tree_pos, nt, c->tree, nn, c->spare, accept, nn_dev, g.s, err) ||
+                      !gpu_normals_to_enqueue(c->nrm_work, nullptr, nullptr, c->d_shade, c->shade_back, accept, g.s, err)
+                : !gpu_refit_bvh_enqueue(c->bvh_work, tree_pos, nt, c->tree, nn, nn_dev ? accept : nullptr, nn_dev, g.s, err)) {
+    c->vis_mask = before;
+    return fail(c, FR_E_HIP, name + ": " + err);
+  }
+  if (g.overlap) adopt_spare(c, true);
+  c->base_stale = true;
+  return FR_OK;
+}
+
+int fr_model_visibility(fr_ctx* c, uint32_t* visible) {
+  if (!c || !visible) return FR_E_INVALID;
+  *visible = c->vis_mask & vis_valid(c);
+  return FR_OK;
+}
+
+// Test hook (not part of include/fovrt.h): k_hide's tile, in triangles.
+int fr__visibility_tile(void) { return FR_HIDE_TILE; }
 
 int fr_set_motion_reprojection(fr_ctx* c, int on) {
   if (!c) return FR_E_INVALID;

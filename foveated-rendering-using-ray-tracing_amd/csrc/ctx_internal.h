@@ -213,6 +213,14 @@ struct fr_ctx {
   f3 *pose_rest_pos = nullptr, *pose_rest_nrm = nullptr, *pose_stage_pos = nullptr, *pose_stage_nrm = nullptr;
   bool pose_on = false;
   std::vector<float> pose_m;
+  // Per-model visibility (fr_model_visibility_enable, fr_set_model_visibility). vis_mask: the mask last submitted,
+  // valid bits only for a context that has submitted one (FR_VISIBLE_ALL before). While a model is hidden every tree
+  // writer reads vis_pos, the collapsed copy k_hide makes of the positions it was handed (tree_positions,
+  // ctx_geometry.cpp), on the writer's own stream; with every model visible nothing reads or writes it. One array of
+  // 36 B per triangle, made by the first enable (the ordering argument: above GeoEnqueue).
+  f3* vis_pos = nullptr;
+  bool vis_on = false;
+  uint32_t vis_mask = FR_VISIBLE_ALL;
   // Overlapped updates (fr_set_geometry_overlap). While overlap_on, an enqueued update runs on front_stream and writes
   // the set no frame in flight reads: the spare tree arrays above and shade_back (made by the first on = 1, a copy of
   // d_shade), which then become the scene's (adopt_spare: a swap with `tree` and d_shade and a refresh of dsc;

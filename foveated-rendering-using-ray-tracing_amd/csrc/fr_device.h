@@ -102,6 +102,8 @@ struct GeoUpdateState {
   uint32_t bad_nrm;  // k_check_normals' flag for that update
   float box[6];      // the scene box (min, max) of the positions in place
   float xbox[6];     // the box an owed EXTRA heat map's sampling launch saw, when an update has replaced it since
+  uint32_t accept;   // always 0: the verdict word of an enqueued refit that nothing can reject, where a kernel wants one
+                     // (fr_set_model_visibility_enqueue)
 };
 
 // Device-side record of ray queries (fr_trace_rays), one per context, made by fr_create and zeroed in stream order
@@ -148,6 +150,13 @@ struct PoseArgs {
   uint32_t identity;                      // bit i: model i's matrix is the identity (it takes its rest bits)
   float M[FR_POSE_MAX_MODELS][12];        // row-major 3 x 4: v' = A v + t
   float K[FR_POSE_MAX_MODELS][9];         // cofactors of A, row-major (pose_args)
+};
+
+// A visibility mask of the scene's models (fr_set_model_visibility), passed to k_hide by value as a pose is.
+#define FR_HIDE_TILE 256  // triangles per block of k_hide
+struct HideArgs {
+  int32_t first_tri[FR_POSE_MAX_MODELS + 1];  // model i holds [first_tri[i], first_tri[i + 1]); unused: num_tris
+  uint32_t hidden;                            // bit i: model i is hidden (its triangles collapse onto their first corner)
 };
 
 // The scene's model boundaries for ray queries (per-ray model masks, the model word of fr_ray_surface), passed by

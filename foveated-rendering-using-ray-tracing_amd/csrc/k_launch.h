@@ -231,4 +231,10 @@ bool gpu_pose_enqueue(const PoseArgs& a, const f3* rest_pos, const f3* rest_nrm,
 bool gpu_pose_capture_enqueue(const f3* pos, const TriShade* shade, f3* rest_pos, f3* rest_nrm, int nt, hipStream_t s,
                               std::string& err);
 size_t pose_array_bytes(int nt);
+
+// k_visibility.hip, per-model visibility: a mask's kernel arguments, and the launch that writes the collapsed
+// positions (pos with every triangle of a hidden model collapsed onto its first corner) into out, an array of
+// pose_array_bytes(nt)
+HideArgs hide_args(const int* first_tri, int nmodels, int nt, uint32_t visible);
+bool gpu_hide_enqueue(const HideArgs& a, const f3* pos, f3* out, int nt, hipStream_t s, std::string& err);
 }  // namespace fr

@@ -32,6 +32,7 @@ FR_OK, FR_E_INVALID, FR_E_HIP, FR_E_NOMEM, FR_E_IO, FR_E_STATE, FR_E_UNSUPPORTED
 SCENE_BOX, SCENE_BUNNY, SCENE_VOKSELIA = 0, 1, 2
 # fr_update_positions: what follows the new positions, and where they come from
 FR_BVH_REBUILD, FR_BVH_REFIT = 0, 1
+FR_VISIBLE_ALL = 0xFFFFFFFF  # fr_set_model_visibility: every model visible
 FR_MEM_HOST, FR_MEM_DEVICE = 0, 1
 # fr_update_geometry: what becomes of the shading normals
 FR_NORMALS_KEEP, FR_NORMALS_GIVEN, FR_NORMALS_RECOMPUTE = 0, 1, 2
@@ -230,6 +231,10 @@ _SIGS = {
     "fr_set_model_transforms": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int],
     "fr_set_model_transforms_enqueue": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
     "fr_model_transforms": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
+    "fr_model_visibility_enable": [C.c_void_p, C.c_int],
+    "fr_set_model_visibility": [C.c_void_p, C.c_uint32, C.c_int],
+    "fr_set_model_visibility_enqueue": [C.c_void_p, C.c_uint32],
+    "fr_model_visibility": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -911,6 +916,44 @@ class PathTracer:
         m = np.empty((n.value, 3, 4), np.float32)
         self._check(_lib.fr_model_transforms(self._ctx, m.ctypes.data_as(C.POINTER(C.c_float)), n.value))
         return m
+
+    def enable_model_visibility(self, on=True):
+        """fr_model_visibility_enable: makes the device array the collapsed positions live in (36 B per triangle, at
+        the first call). on=False: set_model_visibility fails (FR_E_STATE) until the next enable; refused while a
+        model is hidden."""
+        self._check(_lib.fr_model_visibility_enable(self._ctx, int(bool(on))))
+
+    def _visible_mask(self, visible) -> int:
+        if isinstance(visible, (int, np.integer)):
+            return int(visible) & 0xFFFFFFFF
+        if isinstance(visible, str):
+            visible = [visible]
+        names = [m[0] for m in self.models()]
+        mask = 0
+        for name in visible:
+            if name not in names:
+                raise ValueError(f"no model named {name!r} (models: {names})")
+            mask |= 1 << names.index(name)
+        return mask
+
+    def set_model_visibility(self, visible, update="refit", enqueue=False):
+        """The models frames and ray queries see: `visible` is a mask (bit k: model k of models()) or an iterable of
+        model names; every other model is hidden, by a refit or a rebuild over the positions with its triangles
+        collapsed to points (fr_set_model_visibility), or with enqueue=True in stream order without waiting for the
+        GPU, always a refit (fr_set_model_visibility_enqueue). Exported arrays and the scene box do not change."""
+        mask = self._visible_mask(visible)
+        if enqueue:
+            if self._update_kind(update) != FR_BVH_REFIT:
+                raise ValueError("an enqueued visibility change always refits")
+            self._check(_lib.fr_set_model_visibility_enqueue(self._ctx, mask))
+        else:
+            self._check(_lib.fr_set_model_visibility(self._ctx, mask, self._update_kind(update)))
+
+    def model_visibility(self) -> int:
+        """The mask last submitted, valid bits only (every model before the first call)."""
+        v = C.c_uint32()
+        self._check(_lib.fr_model_visibility(self._ctx, C.byref(v)))
+        return v.value
 
     def set_normals(self, nrm: np.ndarray):
         """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have

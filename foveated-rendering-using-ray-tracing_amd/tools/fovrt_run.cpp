@@ -4,10 +4,14 @@
 //
 //   fovrt_run [W H] [--scene box|bunny|vokselia] [--mask saliency|logpolar|uniform|all|logpolar10]
 //             [--spp N] [--dmd N] [--frames N] [--assets DIR] [--procedural] [--dump BUFFER FILE.pfm]
+//             [--hide NAME[,NAME]]
 //
+// --hide takes the named models (ground, box, bunny, earth, vokselia_spawn) out of every frame, right after the
+// scene is created (fr_set_model_visibility), so a dump can leave a model out.
 // --dump writes one buffer (e.g. ATROUS, SHADING, SIBSON) after the last frame as a little-endian
 // RGB PFM (row 0 = bottom, as PFM stores it), the image-dump replacement of saveBMP24
 // (FR/gui.cpp:315-355).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,7 +51,7 @@ int main(int argc, char** argv) {
   cfg.mask_mode = FR_MASK_LOGPOLAR_SIGNED;
   cfg.spp = 4; cfg.diffuse_max_depth = 3;
   int frames = 10;
-  std::string dump_buf, dump_path, assets = "assets";
+  std::string dump_buf, dump_path, assets = "assets", hide;
   int pos = 0;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -64,6 +68,7 @@ int main(int argc, char** argv) {
     else if (a == "--assets") assets = next();
     else if (a == "--procedural") cfg.texture_mode = 1;
     else if (a == "--dump") { dump_buf = next(); dump_path = next(); }
+    else if (a == "--hide") hide = next();
     else if (pos == 0) { cfg.width = atoi(a.c_str()); pos++; }
     else if (pos == 1) { cfg.height = atoi(a.c_str()); pos++; }
     else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -79,6 +84,26 @@ int main(int argc, char** argv) {
   if (!tracer->initialize(cfg.width, cfg.height)) {
     fprintf(stderr, "initialize failed: %s\n", tracer->initialize_error().c_str());
     return 1;
+  }
+  if (!hide.empty()) {
+    try {
+      const std::vector<PathTracer::Model> ms = tracer->models();
+      uint32_t visible = FR_VISIBLE_ALL;
+      for (size_t b = 0; b <= hide.size();) {
+        const size_t e = std::min(hide.find(',', b), hide.size());
+        const std::string name = hide.substr(b, e - b);
+        size_t k = 0;
+        while (k < ms.size() && ms[k].name != name) k++;
+        if (k == ms.size()) { fprintf(stderr, "--hide: no model named %s\n", name.c_str()); return 2; }
+        visible &= ~(1u << k);
+        b = e + 1;
+      }
+      tracer->enable_model_visibility();
+      tracer->set_model_visibility(visible);
+    } catch (const Error& e) {
+      fprintf(stderr, "fovrt error %d: %s\n", e.code, e.what());
+      return 1;
+    }
   }
   // camera (FR/main.cpp:185-209): the preset pose of the scene
   Camera g_camera;

@@ -766,8 +766,8 @@ int fr_trace_rays_masked_enqueue(fr_ctx* ctx, const void* rays, const uint32_t* 
  * counted by fr_geometry_update_status; both leave the scene untouched.
  * With fr_set_geometry_overlap on, the enqueued form poses, refits and writes the normals beside the previous
  * frame's path trace.
- * Not covered: per-model visibility or materials, instancing, a two-level tree, changed triangle counts, groups
- * in stream order. */
+ * Not covered: per-model materials, instancing, a two-level tree, changed triangle counts, groups in stream order
+ * (per-model visibility: below). */
 #define FR_MAX_MODELS 16
 int fr_model_count(fr_ctx* ctx, int* n);
 int fr_model_info(fr_ctx* ctx, int i, const char** name, int* first_tri, int* ntris);
@@ -775,6 +775,45 @@ int fr_model_pose_enable(fr_ctx* ctx, int on);
 int fr_set_model_transforms(fr_ctx* ctx, const float* m, size_t nmodels, int how);  /* FR_BVH_REFIT | FR_BVH_REBUILD */
 int fr_set_model_transforms_enqueue(fr_ctx* ctx, const float* m, size_t nmodels);
 int fr_model_transforms(fr_ctx* ctx, float* m, size_t nmodels);
+/* Per-model visibility: models hidden from and shown to every frame and ray query, in stream order. Bit k of
+ * `visible` clear means model k (fr_model_info's order) is hidden; bits at or above the model count are ignored and
+ * read back clear; the default is every model visible. Visibility is applied where the tree is written, not where
+ * it is traversed. The collapsed positions C(P, visible) are P, except that a triangle t of a hidden model takes
+ * P[3t] for all three corners (the bits are copied): such a triangle has a zero normal and fails the triangle test
+ * of every ray, and its box is a point. From the call on, at its place in the stream order, every tree writer reads
+ * C(current positions, visible): the call's own refit or rebuild, fr_refit_bvh and fr_rebuild_bvh, fr_set_positions,
+ * fr_update_positions, fr_update_geometry, fr_set_model_transforms, the enqueued forms of these,
+ * fr_rebuild_bvh_enqueue, fr_rebuild_bvh_enqueue_if and the rebuild policy. The tree has one right answer in bytes:
+ * the tree the same call makes without this feature over those positions. A hidden model costs a frame nothing.
+ * Ray queries read the same tree: a hidden model neither wins, ties, blocks nor attenuates, in all three kinds,
+ * masked or not (the effective mask is masks[i] & visible).
+ * What does not change: the exported positions, normals, uv, flags and materials; the scene box the saliency mask
+ * reads (the box of the true positions); the weld and fr_recompute_normals (true positions); the pose rest
+ * geometry; motion reprojection (a visibility change is not a position update: the frame after it reprojects as
+ * over still geometry); fr_geometry_update_status and the policy's update count. A snapshot does not carry it.
+ * fr_model_visibility_enable(ctx, 1) waits for the context's pending work and allocates at its first call one
+ * device position array of 36 B per triangle (FR_E_NOMEM, with nothing kept and the setting off); no other call of
+ * this feature allocates. on = 0 makes the two set calls return FR_E_STATE until the next on = 1, is itself
+ * FR_E_STATE while a model is hidden, and frees nothing. More than FR_MAX_MODELS models: FR_E_UNSUPPORTED.
+ * fr_set_model_visibility waits as fr_refit_bvh does, then refits (FR_BVH_REFIT) or rebuilds with the context's
+ * builder (FR_BVH_REBUILD) over C, also when the mask is the one in place; a failed rebuild leaves the tree and the
+ * mask as they were. fr_set_model_visibility_enqueue is the refit in stream order, as fr_update_geometry_enqueue
+ * with kept normals is: no host wait, no copy, no allocation; with fr_set_geometry_overlap on it refits into the
+ * other set beside the previous frame's path trace. The mask changes at enqueue time: updates, poses and rebuilds
+ * enqueued later use it. An enqueued update the device rejects while a model is hidden leaves the tree as it was.
+ * Refused with nothing enqueued and tree and mask untouched: a NULL context or out-pointer, a bad `how`:
+ * FR_E_INVALID; visibility not enabled: FR_E_STATE; the enqueued form on a rank of a group or a sharded context, or
+ * without a refit workspace: FR_E_UNSUPPORTED (the synchronous form works on a group's contexts one by one).
+ * fr_model_visibility returns the mask last submitted, valid bits only.
+ * The rebuild policy: a tree written by either set call came by another route, so the next
+ * fr_rebuild_bvh_enqueue_if adopts its cost as the baseline and skips (showing a model would otherwise look like a
+ * tree that has grown). fr_bvh_sah_cost reports the tree in use, the point boxes of hidden triangles included.
+ * Not covered: per-ray-class visibility (hidden from the camera but casting shadows), groups in stream order. */
+#define FR_VISIBLE_ALL 0xffffffffu
+int fr_model_visibility_enable(fr_ctx* ctx, int on);
+int fr_set_model_visibility(fr_ctx* ctx, uint32_t visible, int how);   /* FR_BVH_REFIT | FR_BVH_REBUILD */
+int fr_set_model_visibility_enqueue(fr_ctx* ctx, uint32_t visible);    /* refit, stream order */
+int fr_model_visibility(fr_ctx* ctx, uint32_t* visible);               /* last submitted, & valid bits */
 /* History that follows moving geometry (off by default). The G-buffer reprojects a hit point with the previous
  * camera, and the sampling stage accepts the history there only when the depth stored a frame ago equals the
  * point's distance from the previous eye: both assume the point stood still. With motion reprojection on, the

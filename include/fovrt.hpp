@@ -314,6 +314,23 @@ class PathTracer {
     check(fr_model_transforms(ctx(), n ? m[0].data() : nullptr, m.size()), ctx_, "model_transforms");
     return m;
   }
+  // Per-model visibility (fr_set_model_visibility): bit k of `visible` clear hides model k of models() from every
+  // frame and ray query, by a refit or a rebuild over the collapsed positions, or in stream order without waiting for
+  // the GPU (the enqueued form, always a refit). model_visibility(): the mask last submitted, valid bits only.
+  void enable_model_visibility(bool on = true) {
+    check(fr_model_visibility_enable(ctx(), on ? 1 : 0), ctx_, "enable_model_visibility");
+  }
+  void set_model_visibility(uint32_t visible, int how = FR_BVH_REFIT) {
+    check(fr_set_model_visibility(ctx(), visible, how), ctx_, "set_model_visibility");
+  }
+  void set_model_visibility_enqueue(uint32_t visible) {
+    check(fr_set_model_visibility_enqueue(ctx(), visible), ctx_, "set_model_visibility_enqueue");
+  }
+  uint32_t model_visibility() {
+    uint32_t v = 0;
+    check(fr_model_visibility(ctx(), &v), ctx_, "model_visibility");
+    return v;
+  }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
