@@ -140,6 +140,8 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     return fail(nullptr, FR_E_INVALID, "width/height out of range (1..32767)");
   if (!(cfg.spp == 1 || cfg.spp == 2 || cfg.spp == 4 || cfg.spp == 8))
     return fail(nullptr, FR_E_UNSUPPORTED, "spp must be 1, 2, 4 or 8");
+  // (the two steered modes, FR_MASK_ECCENTRIC and FR_MASK_CALLER, are entered with fr_set_mask_mode: a context is
+  // created in one of the five reference modes, as it always was)
   if (cfg.mask_mode < 0 || cfg.mask_mode > 4) return fail(nullptr, FR_E_INVALID, "bad mask_mode");
   if (cfg.mesh_mode < 0 || cfg.mesh_mode > 2) return fail(nullptr, FR_E_INVALID, "bad mesh_mode");
   if (cfg.scene < 0 || cfg.scene > 2) return fail(nullptr, FR_E_INVALID, "bad scene preset");
@@ -173,6 +175,8 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
   for (auto& f : c->set_read) hipEventCreateWithFlags(&f.ev, hipEventDisableTiming);
   hipEventCreateWithFlags(&c->update_done.ev, hipEventDisableTiming);
   hipEventCreateWithFlags(&c->rays_done.ev, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->mask_taken.ev, hipEventDisableTiming);
+  hipEventCreateWithFlags(&c->mask_read.ev, hipEventDisableTiming);
   read_env_knobs(c);
 
   std::string err;
@@ -219,6 +223,12 @@ int fr_create(const fr_config* cfg_in, fr_ctx** out) {
     c->err = "device allocation (scene) failed";
     return bail(FR_E_NOMEM);
   }
+  // the record of the ray budget (fr_set_foveation allocates nothing), and the parameters a context starts from
+  if (dalloc(&c->fov_st, 1) != hipSuccess || hipHostMalloc((void**)&c->h_fov, sizeof(fr::FovState)) != hipSuccess) {
+    c->err = "device allocation (scene) failed";
+    return bail(FR_E_NOMEM);
+  }
+  fri::foveation_init(c);
   // the record of ray queries (fr_trace_rays allocates nothing)
   if (dalloc(&c->rq, 1) != hipSuccess) {
     c->err = "device allocation (scene) failed";
@@ -423,6 +433,10 @@ int fr_destroy(fr_ctx* c) {
   fr(c->rb);
   if (c->h_rb) hipHostFree(c->h_rb);
   fr(c->rq); fr(c->rq_area);
+  fr(c->fov_st); fr(c->cmask);
+  if (c->h_fov) hipHostFree(c->h_fov);
+  if (c->mask_taken.ev) hipEventDestroy(c->mask_taken.ev);
+  if (c->mask_read.ev) hipEventDestroy(c->mask_read.ev);
   if (c->rays_done.ev) hipEventDestroy(c->rays_done.ev);
   if (c->geo_read.ev) hipEventDestroy(c->geo_read.ev);
   for (auto& f : c->set_read) if (f.ev) hipEventDestroy(f.ev);

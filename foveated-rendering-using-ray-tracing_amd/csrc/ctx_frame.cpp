@@ -70,7 +70,10 @@ void fc_harvest(fr_ctx* c, int i) {
   c->fc_prev_end = e;
 }
 
-void join_update(fr_ctx* c) { c->update_done.consume(c->stream); }
+void join_update(fr_ctx* c) {
+  c->update_done.consume(c->stream);
+  c->mask_taken.consume(c->stream);  // (an enqueued caller mask's copy runs on front_stream as well)
+}
 
 void join_recon(fr_ctx* c) {
   c->stream_dirty = true;  // the caller is about to enqueue on `stream` outside a pipelined frame
@@ -144,9 +147,38 @@ static int enqueue_sampling(fr_ctx* c, hipStream_t fs) {
   // reads them, evaluates no saliency features; what k_extra needs of it is recorded. A tile-local front and tile
   // sharding keep the eager form (their G-buffer inputs do not cover the screen).
   const bool lazy = c->extra_lazy && c->cfg.write_extra && !c->U.front_need && c->U.shard_count <= 1;
-  launch_sampling(c->U, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
+  // Foveation control: the eccentricity mask and a caller's mask reach k_sampling as the log-polar mask does, through
+  // the mask it reads per pixel: a copy of the uniforms says MASK_LOGPOLAR and `cached` is the array to read. c->U keeps
+  // the real mode (the snapshot header and the EXTRA debt read it). Modes 0..4 enter neither branch.
+  FrameUniforms Uc = c->U;
+  uint8_t* cached = c->lp_cache;
+  if (c->U.mask_mode == FR_MASK_ECCENTRIC) {
+    // With a ray budget the controller runs first (one lane; it reads the count the last compaction left, when there
+    // was one since the last sampling launch) and the mask is generated at every launch from the r2 it leaves in
+    // fov_st; without one only when gaze, parameters or mode changed.
+    const bool budget = c->fov.ray_budget > 0;
+    const float w = (float)c->W, h = (float)c->H;
+    const float ww = w * w, hh = h * h;
+    if (budget)
+      launch_fov_control(c->fov_st, c->fov_count, c->fov_reset, c->fov_r2, c->fov.ray_budget, c->fov.tolerance, ww + hh, fs);
+    if (budget || c->fov_dirty || c->lp_mode != FR_MASK_ECCENTRIC || c->lp_gaze.x != c->U.gaze.x ||
+        c->lp_gaze.y != c->U.gaze.y) {
+      launch_ecc_mask(c->U.gaze, budget ? c->fov_st : nullptr, c->fov_r2, (uint32_t)c->fov.floor_ranks, c->W, c->H,
+                      c->lp_cache, fs);
+      c->lp_mode = FR_MASK_ECCENTRIC; c->lp_gaze = c->U.gaze;
+    }
+    c->fov_dirty = false; c->fov_reset = false;
+    c->fov_on_device = budget;
+    c->fov_used_r2 = c->fov_r2;
+    Uc.mask_mode = FR_MASK_LOGPOLAR;
+  } else if (c->U.mask_mode == FR_MASK_CALLER) {
+    cached = c->cmask;
+    Uc.mask_mode = FR_MASK_LOGPOLAR;
+  }
+  c->fov_count = nullptr;
+  launch_sampling(Uc, c->dsc, c->img[P_pos(c)], c->img[c->depth_cur], c->img[c->depth_cache], c->img[P_wgt(c)],
                   c->img[P_nrm(c)], c->img[P_DIFFUSE], c->img[P_EXTRA], c->mask, c->gclass, c->words, c->counts,
-                  lazy ? 0 : c->cfg.write_extra, c->lp_cache, c->lp_inv, lp_refresh,
+                  lazy ? 0 : c->cfg.write_extra, cached, c->lp_inv, lp_refresh,
                   c->U.shard_count > 1 ? c->bcount : nullptr, c->motion_frame, c->dev_box, fs);
   c->motion_frame = false;  // WEIGHT.z is the validity from here on: a repeated sampling launch runs the plain test
   if (c->cfg.write_extra) c->extra.owed = lazy;  // (write_extra = 0: EXTRA is never written, nothing is ever owed)
@@ -171,6 +203,7 @@ static int enqueue_optimize(fr_ctx* c, hipStream_t fs) {
   }
   launch_compaction(c->W, c->H, c->words, c->counts, c->offsets, c->tiles, c->ray_count, c->active, fs);
   c->compacted = true;
+  c->fov_count = c->ray_count;  // what the ray budget's controller reads ahead of the next sampling launch
   return check_launch(c);
 }
 
@@ -454,6 +487,7 @@ int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
     join_update(c);  // a timed frame's stages all run on `stream`: behind an overlapped update on front_stream
     hipEventRecord(T.begin, c->stream);
   }
+  if (trace && (rc = foveation_check(c))) return rc;
   if (trace) {
     // untimed frames pipeline: the front stages go to front_stream and overlap the previous frame's
     // entry 3 (timed frames keep every stage on `stream`, one after the other)
@@ -571,7 +605,11 @@ int fr_geometry_launch(fr_ctx* c, float* ms) {
   c->extra.settle(c);  // the stage call overwrites DIFFUSE and DEPTH, and the caller may read EXTRA before the next sampling
   return timed(c, [&] { return enqueue_geometry(c, c->stream); }, ms);
 }
-int fr_sampling_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_sampling(c, c->stream); }, ms); }
+int fr_sampling_launch(fr_ctx* c, float* ms) {
+  if (!c) return FR_E_INVALID;
+  if (int rc = foveation_check(c)) return rc;
+  return timed(c, [&] { return enqueue_sampling(c, c->stream); }, ms);
+}
 int fr_optimize_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_optimize(c, c->stream); }, ms); }
 int fr_shading_launch(fr_ctx* c, float* ms) { if (!c) return FR_E_INVALID; return timed(c, [&] { return enqueue_shading(c); }, ms); }
 

@@ -275,6 +275,26 @@ struct fr_ctx {
   uint32_t* lp_inv = nullptr;   // the inverse log-polar map of every (u, v) of that gaze (k_logpolar_inv)
   f2 lp_gaze{-1e30f, -1e30f};
   int lp_mode = -1;
+  // Foveation control (ctx_foveation.cpp). fov: the eccentricity mask's parameters (fr_set_foveation), fov_r2 their
+  // squared radius; the mask shares lp_cache with the log-polar modes and fov_dirty says the parameters changed since it
+  // was generated. The ray budget: fov_st its record on the device (made by fr_create; h_fov the pinned copy for
+  // fr_foveation_status), fov_reset: the next mode-5 sampling launch starts the controller from fov_r2; fov_count: the
+  // ray count of the compaction that followed the last sampling launch (NULL: none since); fov_on_device: the last
+  // mode-5 launch took its r2 from fov_st (else fov_used_r2 is what it used).
+  fr_foveation fov = {};
+  float fov_r2 = 0.0f, fov_used_r2 = 0.0f;
+  bool fov_dirty = true, fov_reset = true, fov_on_device = false;
+  fr::FovState* fov_st = nullptr;
+  fr::FovState* h_fov = nullptr;
+  const uint32_t* fov_count = nullptr;
+  // A caller's sampling mask (FR_MASK_CALLER). cmask: the context's 0 / 1 copy, W x H bytes, made by the first
+  // fr_sampling_mask_enable(1); cmask_set: a mask was submitted. An enqueued copy runs on front_stream, ahead of the
+  // next frame's front stages: mask_taken is recorded there after it (the context stream waits for it before anything
+  // it runs outside a pipelined frame: join_update), and mask_read too, for the caller's stream
+  // (fr_sampling_mask_consumed; never consumed).
+  uint8_t* cmask = nullptr;
+  bool cmask_on = false, cmask_set = false;
+  Fence mask_taken, mask_read;
   unsigned long long* words = nullptr;
   uint32_t* counts = nullptr;
   uint32_t* offsets = nullptr;  // per (class, block) local prefix
@@ -427,6 +447,11 @@ void box_of(const f3* v, size_t n, f3* lo, f3* hi);  // the box of n points (ctx
 // they are fetched from the device, behind the context's pending work (a wait). Every host reader of them goes
 // through this first. (ctx_geometry.cpp)
 int tree_numbers(fr_ctx* c);
+// Foveation control (ctx_foveation.cpp). foveation_init: fr_create's parameters (fr_foveation_default). foveation_check:
+// what a sampling launch refuses before anything of it or of its frame is enqueued (mode 6 without a mask; a ray
+// budget on a context that has become a rank or sharded).
+void foveation_init(fr_ctx* c);
+int foveation_check(fr_ctx* c);
 }  // namespace fri
 static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
 

@@ -227,6 +227,44 @@ FR_DEV bool shard_owns(const FrameUniforms& U, int x, int y) {
   return shard_owner(U, shard_tile_of(U, x, y)) == U.shard_rank;
 }
 
+// The eccentricity mask (FR_MASK_ECCENTRIC; the rule is beside fr_set_foveation in include/fovrt.h), one function for
+// the kernel (k_ecc_mask) and the host (fr_foveation_mask). ecc_rank: the 8 x 8 ordered-dither rank of a pixel, bit i
+// of (x ^ y) and of y interleaved from the top. fp32, every operation rounded on its own: the products are named so
+// that no compiler fuses them into the sum (the library builds with -ffp-contract=off as well).
+FR_HD uint32_t ecc_rank(uint32_t x, uint32_t y) {
+  const uint32_t yb = y & 7u, a = (x & 7u) ^ yb;
+  uint32_t r = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) r |= (2u * ((a >> i) & 1u) + ((yb >> i) & 1u)) << (2 * (2 - i));
+  return r;
+}
+FR_HD bool ecc_sampled(uint32_t x, uint32_t y, f2 gaze, float r2, uint32_t floor_ranks) {
+  const uint32_t rank = ecc_rank(x, y);
+  const float dx = (float)x - gaze.x, dy = (float)y - gaze.y;
+  const float xx = dx * dx, yy = dy * dy;
+  const float d2 = xx + yy;
+  const float lhs = (float)rank * d2, rhs = 64.0f * r2;
+  return rank < floor_ranks || lhs < rhs;
+}
+
+// Device-side record of the ray budget (fr_foveation.ray_budget), one per context, made by fr_create: k_fov_control
+// writes it ahead of every mode-5 sampling launch of a context with a budget, k_ecc_mask reads r2 there.
+struct FovState {
+  float r2;             // the squared radius the last sampling launch used
+  uint32_t last_count;  // the ray count the last adjustment or hold read (0: none since fr_set_foveation)
+  uint32_t adjusted, held;  // launches since fr_set_foveation that changed r2 / that found the count in the deadband
+};
+// One step of the controller (k_fov_control and the host's statement of it agree by construction: the same function).
+FR_HD float fov_next_r2(float r2, uint32_t n, uint32_t budget, float tolerance, float r2_max, bool* held) {
+  const float nf = (float)(n > 1u ? n : 1u), tf = (float)budget;
+  const float band = tolerance * tf;
+  *held = fabsf(nf - tf) <= band;
+  if (*held) return r2;
+  const float ratio = fminf(fmaxf(tf / nf, 0.5f), 2.0f);
+  const float scaled = r2 * ratio;
+  return fminf(fmaxf(scaled, 1.0f), r2_max);
+}
+
 // Ray-segment statistics, accumulated with one atomic per wave.
 struct DevStats {
   unsigned long long gbuffer_primary;

@@ -389,6 +389,88 @@ __global__ __launch_bounds__(256) void k_logpolar_mask(FrameUniforms U, float lp
   }
 }
 
+// The eccentricity mask (FR_MASK_ECCENTRIC, ecc_sampled in fr_device.h) into the context's cached mask, which
+// k_sampling then reads as it reads the log-polar one. k_logpolar_mask's store: 16 mask bytes per lane in one 16-byte
+// store, a scalar tail. Bit operations, two products and a sum per pixel: no transcendentals, no LDS. r2 is read
+// once, from the controller's record when the context holds a ray budget (r2_dev), else from the argument.
+__global__ __launch_bounds__(256) void k_ecc_mask(f2 gaze, const float* __restrict__ r2_dev, float r2_host,
+                                                  uint32_t floor_ranks, uint32_t W, size_t N, uint8_t* __restrict__ lp) {
+  const float r2 = r2_dev ? *r2_dev : r2_host;
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g * 16 < N; g += (size_t)gridDim.x * blockDim.x) {
+    const size_t p0 = g * 16;
+    uint32_t x = (uint32_t)(p0 % W), y = (uint32_t)(p0 / W);
+    if (p0 + 16 <= N) {
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int b = 0; b < 16; b++) {
+        w[b >> 2] |= (ecc_sampled(x, y, gaze, r2, floor_ranks) ? 1u : 0u) << (8 * (b & 3));
+        if (++x == W) { x = 0; y++; }
+      }
+      *reinterpret_cast<uint4*>(lp + p0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (size_t p = p0; p < N; p++) {
+        lp[p] = ecc_sampled(x, y, gaze, r2, floor_ranks) ? 1 : 0;
+        if (++x == W) { x = 0; y++; }
+      }
+    }
+  }
+}
+
+void launch_ecc_mask(f2 gaze, const FovState* st, float r2, uint32_t floor_ranks, int W, int H, uint8_t* lp_cache,
+                     hipStream_t stream) {
+  const size_t N = (size_t)W * H;
+  hipLaunchKernelGGL(k_ecc_mask, dim3((unsigned)std::min<size_t>((N / 16 + 256) / 256, 8192)), dim3(256), 0, stream, gaze,
+                     st ? &st->r2 : nullptr, r2, floor_ranks, (uint32_t)W, N, lp_cache);
+}
+
+// The ray budget's controller (the rule is beside fr_set_foveation in include/fovrt.h), one lane, ahead of the mask
+// generation on the stream of the front stages. reset: the first launch after fr_set_foveation starts from r2_0 and
+// reads no count. count: the ray count of the compaction that followed the previous sampling launch, or NULL when
+// there was none (r2 is kept).
+__global__ __launch_bounds__(64) void k_fov_control(FovState* __restrict__ st, const uint32_t* __restrict__ count, int reset,
+                                                    float r2_0, uint32_t budget, float tolerance, float r2_max) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (reset) {
+    st->r2 = r2_0;
+    st->last_count = 0u;
+    st->adjusted = 0u;
+    st->held = 0u;
+  } else if (count) {
+    const uint32_t n = *count;
+    bool held;
+    st->r2 = fov_next_r2(st->r2, n, budget, tolerance, r2_max, &held);
+    st->last_count = n;
+    if (held) st->held++; else st->adjusted++;
+  }
+}
+
+void launch_fov_control(FovState* st, const uint32_t* count, bool reset, float r2_0, uint32_t budget, float tolerance,
+                        float r2_max, hipStream_t stream) {
+  hipLaunchKernelGGL(k_fov_control, dim3(1), dim3(64), 0, stream, st, count, reset ? 1 : 0, r2_0, budget, tolerance, r2_max);
+}
+
+// A caller's sampling mask (FR_MASK_CALLER) into the context's copy: a 16-byte load, every byte normalised to 0 / 1,
+// a 16-byte store; a scalar tail. src is 16-byte aligned (fr_set_sampling_mask refuses other device pointers).
+FR_DEV uint32_t bytes_to_01(uint32_t w) { return ((((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u) >> 7; }
+// (src may be dst: a host mask is copied into place first; every lane reads its bytes before it writes them)
+__global__ __launch_bounds__(256) void k_mask_take(const uint8_t* src, uint8_t* dst, size_t N) {
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g * 16 < N; g += (size_t)gridDim.x * blockDim.x) {
+    const size_t p0 = g * 16;
+    if (p0 + 16 <= N) {
+      const uint4 v = *reinterpret_cast<const uint4*>(src + p0);
+      *reinterpret_cast<uint4*>(dst + p0) = make_uint4(bytes_to_01(v.x), bytes_to_01(v.y), bytes_to_01(v.z), bytes_to_01(v.w));
+    } else {
+      for (size_t p = p0; p < N; p++) dst[p] = src[p] != 0 ? 1 : 0;
+    }
+  }
+}
+
+void launch_mask_take(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t stream) {
+  const size_t N = (size_t)W * H;
+  hipLaunchKernelGGL(k_mask_take, dim3((unsigned)std::min<size_t>((N / 16 + 256) / 256, 8192)), dim3(256), 0, stream, src,
+                     dst, N);
+}
+
 void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* position, const f4* depth,
                      const f4* depth_cache, f4* weight, const f4* normal, const f4* diffuse, f4* extra, uint8_t* mask,
                      const uint8_t* gclass, unsigned long long* words, uint32_t* counts, int write_extra,

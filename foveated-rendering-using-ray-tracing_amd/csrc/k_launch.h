@@ -67,6 +67,13 @@ void launch_sampling(const FrameUniforms& U, const DevScene& sc, const f4* posit
                      const uint8_t* gclass, unsigned long long* words, uint32_t* counts, int write_extra,
                      uint8_t* lp_cache, uint32_t* lp_inv, bool lp_refresh, uint32_t* bcount, bool motion,
                      const float* dev_box, hipStream_t stream);
+// foveation control: the eccentricity mask into lp_cache (st: the ray budget's record, whose r2 the kernel then reads;
+// NULL: r2), the budget's controller ahead of it, and the copy of a caller's mask (src 16-byte aligned) into dst
+void launch_ecc_mask(f2 gaze, const FovState* st, float r2, uint32_t floor_ranks, int W, int H, uint8_t* lp_cache,
+                     hipStream_t stream);
+void launch_fov_control(FovState* st, const uint32_t* count, bool reset, float r2_0, uint32_t budget, float tolerance,
+                        float r2_max, hipStream_t stream);
+void launch_mask_take(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t stream);
 void launch_extra(const FrameUniforms& U, const DevScene& sc, const f4* depth, const f4* weight, const f4* normal,
                   const f4* diffuse, f4* extra, const float* dev_box, hipStream_t stream);
 size_t logpolar_inv_words(int W, int H);

@@ -40,11 +40,14 @@ FR_NORMALS_KEEP, FR_NORMALS_GIVEN, FR_NORMALS_RECOMPUTE = 0, 1, 2
 FR_RAYS_CLOSEST, FR_RAYS_TRANSMITTANCE, FR_RAYS_SURFACE = 0, 1, 2
 RAY_KINDS = {"closest": FR_RAYS_CLOSEST, "transmittance": FR_RAYS_TRANSMITTANCE, "surface": FR_RAYS_SURFACE}
 MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 0, 1, 2, 3, 4
+MASK_ECCENTRIC, MASK_CALLER = 5, 6  # fr_set_foveation / fr_set_sampling_mask
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
 SCENES = {"box": SCENE_BOX, "bunny": SCENE_BUNNY, "vokselia": SCENE_VOKSELIA}
 MASKS = {"saliency": MASK_SALIENCY, "logpolar": MASK_LOGPOLAR, "uniform": MASK_UNIFORM2X2, "all": MASK_ALL,
          "logpolar10": MASK_LOGPOLAR_SIGNED}
+# the steered modes: entered with PathTracer.set_mask_mode (a context is created in one of MASKS)
+STEERED_MASKS = {"eccentric": MASK_ECCENTRIC, "caller": MASK_CALLER}
 
 
 class TextureName:
@@ -107,6 +110,11 @@ class fr_group_config(C.Structure):
                 ("composite", C.c_int), ("recon_cost", C.c_float * 2), ("weights", C.c_float * GROUP_MAX_VIEW_RANKS),
                 ("sample_sum", C.c_int), ("front_local", C.c_int),
                 ("jfa_ranks", C.c_int)]
+
+
+class fr_foveation(C.Structure):
+    _fields_ = [("radius_px", C.c_float), ("floor_ranks", C.c_int), ("ray_budget", C.c_uint32),
+                ("tolerance", C.c_float)]
 
 
 class fr_ray(C.Structure):
@@ -235,6 +243,19 @@ _SIGS = {
     "fr_set_model_visibility": [C.c_void_p, C.c_uint32, C.c_int],
     "fr_set_model_visibility_enqueue": [C.c_void_p, C.c_uint32],
     "fr_model_visibility": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "fr_foveation_default": [C.c_int, C.c_int, C.POINTER(fr_foveation)],
+    "fr_set_foveation": [C.c_void_p, C.POINTER(fr_foveation)],
+    "fr_get_foveation": [C.c_void_p, C.POINTER(fr_foveation)],
+    "fr_foveation_mask": [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_int, C.c_void_p,
+                          C.POINTER(C.c_uint32)],
+    "fr_foveation_status": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                            C.POINTER(C.c_uint64)],
+    "fr_set_mask_mode": [C.c_void_p, C.c_int],
+    "fr_get_mask_mode": [C.c_void_p, C.POINTER(C.c_int)],
+    "fr_sampling_mask_enable": [C.c_void_p, C.c_int],
+    "fr_set_sampling_mask": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
+    "fr_set_sampling_mask_enqueue": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "fr_sampling_mask_consumed": [C.c_void_p, C.c_void_p],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -955,6 +976,73 @@ class PathTracer:
         self._check(_lib.fr_model_visibility(self._ctx, C.byref(v)))
         return v.value
 
+    # ---- foveation control ----
+    def set_mask_mode(self, mode):
+        """fr_set_mask_mode: the sampling mask from the next sampling launch on (a MASK_* value, or a name of MASKS or
+        STEERED_MASKS). Host state; waits for nothing."""
+        self._check(_lib.fr_set_mask_mode(self._ctx, int({**MASKS, **STEERED_MASKS}.get(mode, mode))))
+
+    def mask_mode(self) -> int:
+        v = C.c_int()
+        self._check(_lib.fr_get_mask_mode(self._ctx, C.byref(v)))
+        return v.value
+
+    def foveation(self) -> dict:
+        """fr_get_foveation: the eccentricity mask's parameters in place."""
+        f = fr_foveation()
+        self._check(_lib.fr_get_foveation(self._ctx, C.byref(f)))
+        return {"radius_px": f.radius_px, "floor_ranks": f.floor_ranks, "ray_budget": f.ray_budget,
+                "tolerance": f.tolerance}
+
+    def set_foveation(self, radius_px=None, floor_ranks=None, ray_budget=None, tolerance=None):
+        """fr_set_foveation: the parameters of MASK_ECCENTRIC; an argument left None keeps its value. ray_budget > 0:
+        the device steers the radius toward that many traced pixels (foveation_status())."""
+        f = fr_foveation()
+        self._check(_lib.fr_get_foveation(self._ctx, C.byref(f)))
+        if radius_px is not None:
+            f.radius_px = float(radius_px)
+        if floor_ranks is not None:
+            f.floor_ranks = int(floor_ranks)
+        if ray_budget is not None:
+            f.ray_budget = int(ray_budget)
+        if tolerance is not None:
+            f.tolerance = float(tolerance)
+        self._check(_lib.fr_set_foveation(self._ctx, C.byref(f)))
+
+    def foveation_status(self) -> dict:
+        """fr_foveation_status (waits for pending work): the r2 the last mode-5 sampling launch used, the count the
+        budget's controller read last, and its adjusted / held launches since set_foveation."""
+        r2, n, a, h = C.c_float(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        self._check(_lib.fr_foveation_status(self._ctx, C.byref(r2), C.byref(n), C.byref(a), C.byref(h)))
+        return {"r2": r2.value, "last_count": n.value, "adjusted": a.value, "held": h.value}
+
+    def enable_sampling_mask(self, on=True):
+        """fr_sampling_mask_enable: makes the context's copy of a caller's mask (W * H bytes, at the first call)."""
+        self._check(_lib.fr_sampling_mask_enable(self._ctx, int(bool(on))))
+
+    def set_sampling_mask(self, mask, enqueue=False, ready_event=None):
+        """The mask MASK_CALLER samples with: H x W bytes, a pixel sampled when its byte is not 0. A numpy array is
+        copied from the host; a device pointer or an object with data_ptr() (16-byte aligned, W * H bytes) is read on
+        the device, and with enqueue=True in stream order without waiting for the GPU (ready_event as in
+        update_geometry_enqueue; keep the array untouched until sampling_mask_consumed())."""
+        nbytes = self.width * self.height
+        if isinstance(mask, np.ndarray):
+            if enqueue:
+                raise ValueError("an enqueued mask lives in device memory")
+            a = np.ascontiguousarray(mask, dtype=np.uint8)
+            self._check(_lib.fr_set_sampling_mask(self._ctx, C.c_void_p(a.ctypes.data), a.size, FR_MEM_HOST))
+        elif enqueue:
+            ev = getattr(ready_event, "cuda_event", ready_event)
+            self._check(_lib.fr_set_sampling_mask_enqueue(self._ctx, self._device_ptr(mask), nbytes,
+                                                          C.c_void_p(int(ev)) if ev else None))
+        else:
+            self._check(_lib.fr_set_sampling_mask(self._ctx, self._device_ptr(mask), nbytes, FR_MEM_DEVICE))
+
+    def sampling_mask_consumed(self, stream=None):
+        """fr_sampling_mask_consumed: `stream` waits on the device for the last enqueued mask's reads."""
+        s = getattr(stream, "cuda_stream", stream)
+        self._check(_lib.fr_sampling_mask_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
+
     def set_normals(self, nrm: np.ndarray):
         """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have
         normals; positions, tree, texture coordinates and flags stay."""
@@ -1196,6 +1284,31 @@ class ATrous(_Pass):
 
 def version():
     return load_library().fr_version().decode()
+
+
+def foveation_default(width, height) -> dict:
+    """fr_foveation_default (host only): the parameters a context of this size starts from."""
+    lib = load_library()
+    f = fr_foveation()
+    rc = lib.fr_foveation_default(int(width), int(height), C.byref(f))
+    if rc:
+        raise FovrtError(rc, "fr_foveation_default: bad size")
+    return {"radius_px": f.radius_px, "floor_ranks": f.floor_ranks, "ray_budget": f.ray_budget,
+            "tolerance": f.tolerance}
+
+
+def foveation_mask(width, height, gaze, r2, floor_ranks=1, count_only=False):
+    """fr_foveation_mask (host only): the MASK_ECCENTRIC mask of a screen as (H x W uint8, count), through the
+    function the kernel runs; count_only=True returns the count alone."""
+    lib = load_library()
+    m = None if count_only else np.zeros((int(height), int(width)), np.uint8)
+    n = C.c_uint32()
+    g = None if gaze is None else (C.c_float * 2)(float(gaze[0]), float(gaze[1]))
+    rc = lib.fr_foveation_mask(int(width), int(height), g, C.c_float(r2), int(floor_ranks),
+                               None if m is None else C.c_void_p(m.ctypes.data), C.byref(n))
+    if rc:
+        raise FovrtError(rc, "fr_foveation_mask: bad argument")
+    return n.value if count_only else (m, n.value)
 
 
 def shard_plan(width, height, tile, count, weights=None) -> np.ndarray:

@@ -2,10 +2,13 @@
 // facades (include/fovrt.hpp): the same object construction, camera set-up, launch order, gaze /
 // ray-count read-backs and per-stage timing line as the reference, without a window.
 //
-//   fovrt_run [W H] [--scene box|bunny|vokselia] [--mask saliency|logpolar|uniform|all|logpolar10]
+//   fovrt_run [W H] [--scene box|bunny|vokselia] [--mask saliency|logpolar|uniform|all|logpolar10|eccentric]
 //             [--spp N] [--dmd N] [--frames N] [--assets DIR] [--procedural] [--dump BUFFER FILE.pfm]
-//             [--hide NAME[,NAME]]
+//             [--hide NAME[,NAME]] [--radius PX] [--floor RANKS] [--budget PIXELS]
 //
+// --mask eccentric is the parametric eccentricity mask (fr_set_foveation): --radius its foveal radius in pixels,
+// --floor its peripheral floor in ranks of 64, --budget a ray count the device steers the radius toward; each one left
+// out keeps fr_foveation_default's value. With a budget every frame's line ends with the squared radius it used.
 // --hide takes the named models (ground, box, bunny, earth, vokselia_spawn) out of every frame, right after the
 // scene is created (fr_set_model_visibility), so a dump can leave a model out.
 // --dump writes one buffer (e.g. ATROUS, SHADING, SIBSON) after the last frame as a little-endian
@@ -52,6 +55,10 @@ int main(int argc, char** argv) {
   cfg.spp = 4; cfg.diffuse_max_depth = 3;
   int frames = 10;
   std::string dump_buf, dump_path, assets = "assets", hide;
+  bool eccentric = false;
+  float radius = 0.0f;
+  int floor_ranks = 0;
+  long budget = -1;
   int pos = 0;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -59,6 +66,7 @@ int main(int argc, char** argv) {
     if (a == "--scene") { std::string s = next(); cfg.scene = s == "box" ? FR_SCENE_BOX : s == "vokselia" ? FR_SCENE_VOKSELIA : FR_SCENE_BUNNY; }
     else if (a == "--mask") {
       std::string m = next();
+      eccentric = m == "eccentric";  // (entered with set_mask_mode once the context exists)
       cfg.mask_mode = m == "saliency" ? FR_MASK_SALIENCY : m == "logpolar" ? FR_MASK_LOGPOLAR : m == "uniform" ? FR_MASK_UNIFORM2X2
                     : m == "all" ? FR_MASK_ALL : FR_MASK_LOGPOLAR_SIGNED;
     }
@@ -69,11 +77,18 @@ int main(int argc, char** argv) {
     else if (a == "--procedural") cfg.texture_mode = 1;
     else if (a == "--dump") { dump_buf = next(); dump_path = next(); }
     else if (a == "--hide") hide = next();
+    else if (a == "--radius") radius = (float)atof(next());
+    else if (a == "--floor") floor_ranks = atoi(next());
+    else if (a == "--budget") budget = atol(next());
     else if (pos == 0) { cfg.width = atoi(a.c_str()); pos++; }
     else if (pos == 1) { cfg.height = atoi(a.c_str()); pos++; }
     else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
   cfg.asset_dir = assets.c_str();
+  if (!eccentric && (radius != 0.0f || floor_ranks != 0 || budget >= 0)) {
+    fprintf(stderr, "--radius, --floor and --budget go with --mask eccentric\n");
+    return 2;
+  }
 
   // object construction (FR/main.cpp:152-159)
   PathTracer* tracer = new PathTracer(cfg);
@@ -100,6 +115,19 @@ int main(int argc, char** argv) {
       }
       tracer->enable_model_visibility();
       tracer->set_model_visibility(visible);
+    } catch (const Error& e) {
+      fprintf(stderr, "fovrt error %d: %s\n", e.code, e.what());
+      return 1;
+    }
+  }
+  if (eccentric) {
+    try {
+      fr_foveation f = tracer->foveation();
+      if (radius != 0.0f) f.radius_px = radius;
+      if (floor_ranks != 0) f.floor_ranks = floor_ranks;
+      if (budget >= 0) f.ray_budget = (uint32_t)budget;
+      tracer->set_foveation(f);
+      tracer->set_mask_mode(FR_MASK_ECCENTRIC);
     } catch (const Error& e) {
       fprintf(stderr, "fovrt error %d: %s\n", e.code, e.what());
       return 1;
@@ -149,6 +177,10 @@ int main(int argc, char** argv) {
       text += buf;
       snprintf(buf, sizeof(buf), "JPA, %.3f, SI, %.3f, PPI, %.3f, AT, %.3f", jf / 1e6, si / 1e6, pp / 1e6, at / 1e6);
       text += buf;
+      if (eccentric && budget > 0) {
+        snprintf(buf, sizeof(buf), ", r2, %.3f", tracer->foveation_status().r2);
+        text += buf;
+      }
       printf("frame %d, %s, gaze_target, %.4f %.4f %.4f\n", f, text.c_str(), gaze_target[0], gaze_target[1],
              gaze_target[2]);
     }

@@ -48,9 +48,11 @@ typedef enum fr_mask_mode {
   FR_MASK_LOGPOLAR = 1,   /* log-polar round trip (FR/cuda/samplingStep.cu:180-182) */
   FR_MASK_UNIFORM2X2 = 2, /* x%2==0 && y%2==0 (FR/PathTracer.cpp:526-533), non-foveated */
   FR_MASK_ALL = 3,        /* every pixel traced */
-  FR_MASK_LOGPOLAR_SIGNED = 4 /* log-polar round trip with signed pixel differences: the 10% foveal
+  FR_MASK_LOGPOLAR_SIGNED = 4,/* log-polar round trip with signed pixel differences: the 10% foveal
                                * density BASELINE.json quotes (the literal uint2 arithmetic of
                                * samplingStep.cu:182 wraps negative differences, halving it) */
+  FR_MASK_ECCENTRIC = 5,      /* parametric eccentricity mask (fr_set_foveation): radius, floor, ray budget */
+  FR_MASK_CALLER = 6          /* the caller's own mask (fr_set_sampling_mask) */
 } fr_mask_mode;
 
 typedef struct fr_config {
@@ -250,6 +252,96 @@ int fr_composite_views(fr_ctx* ctx, const void* views, int nviews, void* out, si
  * replaces it too. */
 int fr_set_gaze(fr_ctx* ctx, double xpos, double ypos, int fullscreen);
 int fr_reset_gaze(fr_ctx* ctx);
+
+/* Foveation control: the sampling mask steered by the caller. Nothing here changes a context that does not use it: a
+ * context in modes 0..4 that never makes these calls launches what it always launched.
+ * fr_set_mask_mode replaces the mode fr_create took from fr_config.mask_mode (fr_create itself keeps accepting the
+ * five reference modes 0..4 only: modes 5 and 6 are entered through this call). It is host state, as fr_set_gaze is:
+ * it waits for nothing and takes effect at the next sampling launch (fr_sampling_launch, fr_frame, fr_trace_frame);
+ * the cached mask of the log-polar and eccentricity modes is invalidated. Every mode 0..6 is accepted, anything else
+ * is FR_E_INVALID. fr_get_mask_mode returns the mode in place. A snapshot carries the mode, as it always has; it carries
+ * neither the parameters below, nor the controller's radius, nor a caller's mask: after fr_restore the context keeps
+ * the ones it has.
+ *
+ * FR_MASK_ECCENTRIC: a pure function of the pixel, the gaze the kernels use (fr_set_gaze, fr_set_camera) and two
+ * parameters, with one right answer in bytes. fp32, every operation rounded on its own, no fma; for pixel (x, y):
+ *   xb = x & 7, yb = y & 7, a = xb ^ yb
+ *   rank = sum over i = 0..2 of (2 * bit_i(a) + bit_i(yb)) << (2 * (2 - i))
+ *          (an 8 x 8 ordered-dither permutation of 0..63; row y = 0: 0 32 8 40 2 34 10 42, row y = 1: 48 16 56 24 50 18 58 26)
+ *   dx = (float)x - gaze.x;  dy = (float)y - gaze.y;  d2 = dx*dx + dy*dy              (two products, one sum)
+ *   sampled  <=>  rank < floor_ranks  ||  (float)rank * d2 < 64.0f * r2
+ * Inside the radius (d2 < r2) every pixel is sampled; outside it the density falls as r2 / d2 and the dither says
+ * which pixels go. rank(0, 0) = 0, so the reference's 8 x 8 peripheral grid is always present; floor_ranks (1..64)
+ * raises that floor to floor_ranks / 64. The ownership fold of a sharded context applies as in every other mode.
+ * fr_foveation_default: radius_px = 0.07f * sqrtf((float)W*(float)W + (float)H*(float)H) (the reference's r0 of the
+ * diagonal), floor_ranks = 1, ray_budget = 0, tolerance = 0.02f; a context starts from it. r2 = radius_px * radius_px,
+ * one fp32 product on the host. fr_set_foveation is host state like fr_set_mask_mode; the mask is generated again
+ * only when gaze, parameters or mode changed. FR_E_INVALID, with the parameters in place kept: a NULL argument, a
+ * radius that is not finite or is <= 0, floor_ranks outside 1..64, a tolerance not in [0, 1), ray_budget > W * H.
+ * fr_foveation_mask states the rule on the host, without a device, through the function the kernel runs: mask (W * H
+ * bytes of 0 / 1, row y at y * W; may be NULL) and *count (the number sampled; may be NULL). A caller sizes a radius
+ * for a wanted count with it. FR_E_INVALID: a size outside 1..32767, a NULL or non-finite gaze, an r2 that is not
+ * finite or is < 0, floor_ranks outside 1..64.
+ *
+ * The ray budget (ray_budget = T > 0, mode 5 only): the radius follows the compaction's count on the device, in
+ * stream order, with no host wait. r2_0 = radius_px * radius_px is what the first sampling launch after
+ * fr_set_foveation uses. With n_k the ray count of the compaction that followed sampling launch k, launch k + 1 uses
+ *   nf = (float)max(n_k, 1);  tf = (float)T
+ *   |nf - tf| <= tolerance * tf            ->  r2_{k+1} = r2_k                                   (held)
+ *   otherwise  ratio = min(max(tf / nf, 0.5f), 2.0f);
+ *              r2_{k+1} = min(max(r2_k * ratio, 1.0f), (float)W*(float)W + (float)H*(float)H)   (adjusted)
+ *   no compaction since launch k           ->  r2_{k+1} = r2_k
+ * again fp32 with every operation rounded on its own. One lane decides, on the stream of the front stages ahead of
+ * the mask generation, so stage calls and fr_frame in both pipeline modes walk the same trajectory; while a budget is
+ * set the mask is generated at every sampling launch (the host does not know r2). The deadband keeps the mask still
+ * once the count is on target: ring edges that moved every frame would discard history there. The count is concave
+ * and increasing in r2 with a positive intercept (the floor grid), so r2 <- r2 * T / count(r2) approaches its fixed
+ * point from one side. fr_foveation_status waits for the context's pending work, as fr_geometry_update_status does,
+ * and returns the r2 the last mode-5 sampling launch used (r2_0 before the first), the count the controller read last
+ * (0: none yet) and the launches that adjusted and that held since fr_set_foveation; any pointer may be NULL.
+ * FR_E_UNSUPPORTED, parameters kept: ray_budget > 0 on a rank of a group or a sharded context (ranks with tile-local
+ * fronts count different pixels and would diverge), and on a context created with fr_config.optimize = 0. A context
+ * that becomes a rank or sharded with a budget in place has its next mode-5 sampling launch or frame refused the same
+ * way, with nothing enqueued.
+ *
+ * FR_MASK_CALLER: the caller's mask, W * H bytes, a pixel sampled when its byte is not 0. The context keeps a 0 / 1
+ * copy, made by the first fr_sampling_mask_enable(ctx, 1), which waits for the context's pending work and allocates
+ * W * H bytes (FR_E_NOMEM: nothing is kept and the feature stays off); on = 0 makes the set calls return FR_E_STATE
+ * until the next on = 1 and frees nothing. No other call of the feature allocates.
+ * fr_set_sampling_mask takes the bytes from host (FR_MEM_HOST) or device memory (FR_MEM_DEVICE) and waits for the
+ * context's pending work and for its own copy. fr_set_sampling_mask_enqueue takes device memory and copies in stream
+ * order, behind the context's pending work and ahead of the next sampling launch: no host wait, no copy to the host,
+ * no allocation. ready_event is as in fr_update_geometry_enqueue; the array must stay untouched until
+ * fr_sampling_mask_consumed(ctx, stream) has made `stream` (a hipStream_t; 0 = the null stream) wait, on the device,
+ * for the last enqueued copy's reads, as fr_geometry_consumed does for an update's. Device pointers are 16-byte
+ * aligned. Every sampling launch in mode 6 uses the copy in place at its point of the stream order.
+ * Equality: a frame whose mask came through either call equals, bit for bit, the stage calls with the same 0 / 1 mask
+ * written by fr_write_buffer(FR_BUF_MASK) between fr_sampling_launch and fr_optimize_launch: MASK, WEIGHT, the count,
+ * the active list, SHADING, the history and every reconstruction output.
+ * Refused with nothing written: a NULL context or mask, bytes != W * H, a bad where, a misaligned device pointer
+ * (FR_E_INVALID); the feature not enabled (FR_E_STATE); a sampling launch or frame in mode 6 before any mask was
+ * submitted (FR_E_STATE, nothing of the frame enqueued); the enqueued form on a rank of a group or a sharded context
+ * (FR_E_UNSUPPORTED: the synchronous form works there, and the caller gives every rank of a view the same mask, as
+ * with cameras).
+ * Not covered: a saliency-weighted eccentricity mask, a budget in milliseconds, the budget on groups and sharded
+ * contexts, elliptical or per-eye foveae, parameters and masks inside a snapshot. */
+typedef struct fr_foveation {
+  float radius_px;      /* the foveal radius in pixels, > 0 */
+  int floor_ranks;      /* 1..64: the peripheral floor density is floor_ranks / 64 */
+  uint32_t ray_budget;  /* 0: none; T > 0: the device steers the radius toward T traced pixels */
+  float tolerance;      /* the controller's deadband as a fraction of T, in [0, 1) */
+} fr_foveation;
+int fr_foveation_default(int width, int height, fr_foveation* f);
+int fr_set_foveation(fr_ctx* ctx, const fr_foveation* f);
+int fr_get_foveation(fr_ctx* ctx, fr_foveation* f);
+int fr_foveation_mask(int width, int height, const float gaze[2], float r2, int floor_ranks, uint8_t* mask, uint32_t* count);
+int fr_foveation_status(fr_ctx* ctx, float* r2, uint32_t* last_count, uint64_t* adjusted, uint64_t* held);
+int fr_set_mask_mode(fr_ctx* ctx, int mode);
+int fr_get_mask_mode(fr_ctx* ctx, int* mode);  /* (fr_mask_mode is the enum's name) */
+int fr_sampling_mask_enable(fr_ctx* ctx, int on);
+int fr_set_sampling_mask(fr_ctx* ctx, const void* mask, size_t bytes, int where);   /* FR_MEM_HOST | FR_MEM_DEVICE */
+int fr_set_sampling_mask_enqueue(fr_ctx* ctx, const void* mask, size_t bytes, void* ready_event);
+int fr_sampling_mask_consumed(fr_ctx* ctx, void* stream);
 
 /* The whole main.cpp loop body (update -> 0 -> 1 -> 2 -> 3 -> JFA -> SI -> PPI -> AT). With timing == NULL
  * nothing is synchronised and consecutive frames pipeline: frame N's reconstruction (JFA -> Sibson and

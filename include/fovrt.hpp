@@ -331,6 +331,43 @@ class PathTracer {
     check(fr_model_visibility(ctx(), &v), ctx_, "model_visibility");
     return v;
   }
+  // Foveation control (fr_set_mask_mode, fr_set_foveation, fr_set_sampling_mask). The mask mode changes at the next
+  // sampling launch; FR_MASK_ECCENTRIC takes the parameters of set_foveation (ray_budget > 0: the device steers the
+  // radius toward that many traced pixels, foveation_status waits and reports); FR_MASK_CALLER samples with the mask
+  // last submitted: W * H bytes from host or device memory, or a device array in stream order without waiting for
+  // the GPU (ready_event: a hipEvent_t or nullptr; the array stays untouched until sampling_mask_consumed has
+  // ordered a stream behind the copy).
+  void set_mask_mode(int mode) { check(fr_set_mask_mode(ctx(), mode), ctx_, "set_mask_mode"); }
+  int mask_mode() {
+    int m = 0;
+    check(fr_get_mask_mode(ctx(), &m), ctx_, "mask_mode");
+    return m;
+  }
+  fr_foveation foveation() {
+    fr_foveation f;
+    check(fr_get_foveation(ctx(), &f), ctx_, "foveation");
+    return f;
+  }
+  void set_foveation(const fr_foveation& f) { check(fr_set_foveation(ctx(), &f), ctx_, "set_foveation"); }
+  struct FoveationStatus { float r2; uint32_t last_count; uint64_t adjusted, held; };
+  FoveationStatus foveation_status() {
+    FoveationStatus s{};
+    check(fr_foveation_status(ctx(), &s.r2, &s.last_count, &s.adjusted, &s.held), ctx_, "foveation_status");
+    return s;
+  }
+  void enable_sampling_mask(bool on = true) { check(fr_sampling_mask_enable(ctx(), on ? 1 : 0), ctx_, "enable_sampling_mask"); }
+  void set_sampling_mask(const std::vector<uint8_t>& mask) {
+    check(fr_set_sampling_mask(ctx(), mask.data(), mask.size(), FR_MEM_HOST), ctx_, "set_sampling_mask");
+  }
+  void set_sampling_mask(const void* device_mask, size_t bytes) {
+    check(fr_set_sampling_mask(ctx(), device_mask, bytes, FR_MEM_DEVICE), ctx_, "set_sampling_mask");
+  }
+  void set_sampling_mask_enqueue(const void* device_mask, size_t bytes, void* ready_event = nullptr) {
+    check(fr_set_sampling_mask_enqueue(ctx(), device_mask, bytes, ready_event), ctx_, "set_sampling_mask_enqueue");
+  }
+  void sampling_mask_consumed(void* stream = nullptr) {
+    check(fr_sampling_mask_consumed(ctx(), stream), ctx_, "sampling_mask_consumed");
+  }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
