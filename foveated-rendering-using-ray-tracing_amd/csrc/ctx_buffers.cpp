@@ -125,7 +125,7 @@ int fr_get_buffer(fr_ctx* c, int id, fr_buffer_view* v) {
   if (rc == FR_OK && owed) HIP_TRY(c, hipStreamSynchronize(c->stream));
   // the caller may write the JFA outputs through the view: Sibson then derives its seeds and row prefix sums
   // from them again instead of from the JFA run's own state
-  if (rc == FR_OK && (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD)) c->sib_prefix_fresh = false;
+  if (rc == FR_OK && (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD)) retire_sibson_prefix(c);
   // ... and the history: the next frame's sample setup then reads it, not the validity bits of what the last frame left
   if (rc == FR_OK && (id == FR_BUF_HISTORY || id == FR_BUF_HISTORY_CACHE)) c->hvalid_fresh = false;
   return rc;
@@ -153,7 +153,7 @@ int fr_write_buffer(fr_ctx* c, int id, const void* host, size_t bytes) {
   HIP_TRY(c, hipMemcpyAsync(v.device_ptr, host, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // Sibson's row prefix sums (and the JFA state it reads its seeds from) no longer match these
-  if (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD) c->sib_prefix_fresh = false;
+  if (id == FR_BUF_JFA_COLOR || id == FR_BUF_JFA_COORD) retire_sibson_prefix(c);
   if (id == FR_BUF_HISTORY || id == FR_BUF_HISTORY_CACHE) c->hvalid_fresh = false;
   if (id == FR_BUF_MASK) {
     // a host-written mask must also drive the compaction: rebuild the wave ballots from it
@@ -214,6 +214,10 @@ int fr_restore(fr_ctx* c, const void* host, size_t bytes) {
   c->extra.settle(c);  // the depth pair is overwritten below: an owed EXTRA is written from the old one first
   join_recon(c);
   hipSetDevice(c->cfg.device);
+  // The next Sibson derives its seeds and row prefix sums from the JFA outputs again: a JFA_COORD the last JumpFlooding
+  // still owes is written now, from that run's final state (a restore touches neither JFA output), ahead of the
+  // synchronize below.
+  retire_sibson_prefix(c);
   const char* in = static_cast<const char*>(host);
   size_t off = sizeof(h);
   for (const SnapPart& p : snap_parts(c)) {
@@ -233,7 +237,6 @@ int fr_restore(fr_ctx* c, const void* host, size_t bytes) {
   memcpy(&c->U.gaze, h.gaze, sizeof(h.gaze));
   c->lp_gaze = f2{-1e30f, -1e30f};  // the log-polar mask cache is recomputed for the restored gaze
   c->lp_mode = -1;
-  c->sib_prefix_fresh = false;
   c->jfa_force = true;  // a snapshot carries no JFA state: the next JumpFlooding runs its passes, not what this context retained
   c->hvalid_fresh = false;
   c->moved = false;  // a snapshot carries no previous positions: the next G-buffer reprojects as over still geometry

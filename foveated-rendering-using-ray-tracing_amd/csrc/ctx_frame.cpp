@@ -277,6 +277,18 @@ static void materialize_jfa(fr_ctx* c, hipStream_t s) {
   c->jfa_coord_owed = false;
 }
 
+// The one place outside enqueue_jfa that clears sib_prefix_fresh. launch_sibson_runs takes its seeds from JFA_COORD
+// whenever the prefix sums are not fresh, so a JFA_COORD still owed is written first (on the context stream, after the
+// pending reconstruction): !sib_prefix_fresh implies !jfa_coord_owed.
+void fri::retire_sibson_prefix(fr_ctx* c) {
+  if (c->jfa_coord_owed) {
+    join_recon(c);
+    hipSetDevice(c->cfg.device);
+    materialize_jfa(c, c->stream);
+  }
+  c->sib_prefix_fresh = false;
+}
+
 // EXTRA owed by the last sampling: settled before anything reads it or, outside a frame, overwrites what k_extra reads
 void fr_ctx::ExtraDebt::record(const fr_ctx* c) {
   U = c->U;

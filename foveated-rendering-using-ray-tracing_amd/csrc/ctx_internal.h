@@ -342,8 +342,10 @@ struct fr_ctx {
   uint32_t* sib_wide = nullptr;  // Sibson run form: wide-disc pixel lists (two counts, then W*H indices)
   uint32_t* sib_strips = nullptr;  // Sibson run form: k_sibson_strip's strip list and flags (sibson_strip_words)
   f4* sib_rowp = nullptr;          // Sibson strip kernel: whole-row prefix sums (sibson_rowp_texels)
-  bool sib_prefix_fresh = false;  // the last JFA wrote them with JFA_COLOR (cleared when JFA_COLOR / JFA_COORD are
-                                  // written or handed out, fr_get_buffer)
+  // the last JFA wrote them with JFA_COLOR. Set by enqueue_jfa alone and cleared by retire_sibson_prefix alone (when
+  // JFA_COLOR / JFA_COORD are written or handed out, fr_get_buffer, and by fr_restore), which writes an owed JFA_COORD
+  // first: Sibson reads its seeds from JFA_COORD whenever this is clear, so !sib_prefix_fresh implies !jfa_coord_owed
+  bool sib_prefix_fresh = false;
   const u2* jfa_final = nullptr;  // that JFA's final state (the seeds k_sibson_runs reads while the prefix is fresh)
   // JumpFlooding leaves JFA_COORD unwritten (the run form reads the seeds from jfa_final): while jfa_coord_owed,
   // materialize_jfa writes it (k_jfa_coord, from jfa_final and JFA_COLOR) before anything reads it or writes JFA_COLOR.
@@ -419,6 +421,9 @@ int frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon);
 int enqueue_shading(fr_ctx* c);  // entry 3 alone (the FR_STAMPS probes launch it)
 int P_pos(const fr_ctx* c), P_shd(const fr_ctx* c), P_wgt(const fr_ctx* c);  // this frame slot's physical images
 int resolve(fr_ctx* c, int id, int* phys);  // buffer id -> physical image, with the lazy outputs it names written
+// Sibson's retained seeds and row prefix sums no longer describe the JFA outputs: clears sib_prefix_fresh, after
+// writing a JFA_COORD that is still owed (every caller clears the flag through this)
+void retire_sibson_prefix(fr_ctx* c);
 void kt_harvest(fr_ctx* c, int i), fc_harvest(fr_ctx* c, int i);  // one ring entry of fr_kernel_timing / fr_frame_clock
 // `waiter` waits for everything enqueued on the context stream so far (ev_stream_join). The caller keeps stream_dirty.
 void stream_join(fr_ctx* c, hipStream_t waiter);

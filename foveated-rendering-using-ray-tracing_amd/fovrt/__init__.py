@@ -472,7 +472,8 @@ class PathTracer:
     def destroy(self):
         # a group over this context goes first (fr_group_destroy reads its contexts; under garbage
         # collection of a cycle the tracers' finalisers can run before the group's)
-        for grp in getattr(self, "_groups", ()):
+        # (a copy: Group.destroy removes the group from this list, and a tracer may be a rank of several groups)
+        for grp in list(getattr(self, "_groups", ())):
             grp.destroy()  # (strong references: weak ones are cleared before a cycle's finalisers run)
         self._groups = []
         if getattr(self, "_ctx", None) is not None and _lib is not None:

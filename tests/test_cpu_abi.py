@@ -283,3 +283,18 @@ def test_sqrt_le_bound_is_the_largest_float_whose_sqrt_is_at_most_s(fovrt_mod):
     assert (np.sqrt(b) <= s).all()
     nxt = np.nextafter(b, np.float32(np.inf))
     assert (np.sqrt(nxt) > s).all()
+
+
+def test_destroying_a_tracer_destroys_every_group_it_is_a_rank_of(fovrt_mod):
+    """PathTracer.destroy goes through its groups before fr_destroy frees the context they point to. Group.destroy
+    removes the group from the tracer's list, so the loop runs over a copy: with two groups the second one was
+    skipped and outlived the context. No native object here (_ctx and _h are None): only the Python bookkeeping."""
+    t = fovrt_mod.PathTracer.__new__(fovrt_mod.PathTracer)
+    t._ctx = None
+    groups = [fovrt_mod.Group.__new__(fovrt_mod.Group) for _ in range(2)]
+    for g in groups:
+        g._h, g._comm, g._owns_comm, g.tracers = None, None, False, [t]
+    t._groups = list(groups)
+    t.destroy()
+    assert [g.tracers for g in groups] == [[], []]
+    assert t._groups == []
