@@ -85,7 +85,7 @@ int fr_synchronize(fr_ctx* c) {
   if (!c) return FR_E_INVALID;
   join_recon(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return FR_OK;
+  return present_sync(c);  // (a context that presents: the packs and copies to the host enqueued so far as well)
 }
 
 int fr_ray_count(fr_ctx* c, uint32_t* n) {

@@ -415,6 +415,7 @@ int fr_destroy(fr_ctx* c) {
   hipSetDevice(c->cfg.device);
   const hipStream_t streams[5] = {c->stream, c->atrous_stream, c->sibson_stream, c->carry_stream, c->front_stream};
   for (hipStream_t s : streams) if (s) hipStreamSynchronize(s);
+  fri::present_destroy(c);  // (waits for the present stream first)
   auto fr = [](void* p) { if (p) hipFree(p); };
   fri::tree_free(&c->tree); fri::tree_free(&c->spare);
   fr(c->d_shade); fr(c->d_pos); fr(c->spare_pos); fr(c->prev_pos); fr(c->shade_back); fr(c->vis_pos);

@@ -80,6 +80,7 @@ void join_recon(fr_ctx* c) {
   for (Fence& f : c->recon_done) f.consume(c->stream);
   c->front_done.consume(c->stream);
   join_update(c);
+  present_join(c);  // (what the caller enqueues may overwrite an image a present still reads)
 }
 
 int quiesce(fr_ctx* c) {
@@ -100,6 +101,9 @@ static int enqueue_geometry(fr_ctx* c, hipStream_t fs) {
   c->mask = c->mask_p[sl]; c->active = c->active_p[sl]; c->ray_count = c->ray_count_p[sl];
   c->recon_done[sl].consume(fs);  // entry 3 on `stream` waits for fs (front_done)
   if (fs != c->stream) c->trace_done[sl].consume(fs);
+  // a present of the slot's SHADING still reading it: entry 3, which overwrites it (the carry and the resolve), waits
+  // for these front stages
+  c->present_read_shd[sl].peek(fs);
   if (c->lat.arm) hipEventRecord(c->lat.ev[sl].front_begin, fs);
   if (c->fc_arm) {  // fr_frame_clock: where this frame's G-buffer (the first stage to read the gaze) may start
     const int i = c->fc_next;
@@ -561,6 +565,10 @@ int fri::frame_half(fr_ctx* c, fr_frame_timing* t, bool trace, bool recon) {
     hipEventRecord(c->ev_recon_fork, c->stream);
     hipStreamWaitEvent(c->sibson_stream, c->ev_recon_fork, 0);
     hipStreamWaitEvent(c->atrous_stream, c->ev_recon_fork, 0);
+    // a present still reading SIBSON, PULLPUSH or an A-Trous image (atrous_stream is ordered behind nothing else of
+    // the previous frame's than its own chain)
+    c->present_read.peek(c->sibson_stream);
+    c->present_read.peek(c->atrous_stream);
     if (t) hipEventRecord(T.chain1_begin, c->sibson_stream);
     if ((c->recon_chains & 1) && (rc = enqueue_jfa(c, FR_BUF_SHADING, c->sibson_stream))) return rc;
     if (t) hipEventRecord(T.jfa, c->sibson_stream);

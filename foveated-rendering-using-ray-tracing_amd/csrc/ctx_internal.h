@@ -11,6 +11,7 @@
 #include "../../include/fovrt.h"
 #include "fr_device.h"
 #include "k_launch.h"
+#include "present_ring.h"
 #include "scene.h"
 
 #define FR_MAX_SHARD_RANKS 64  // ranks per view (an owner is one byte of the tile map)
@@ -61,8 +62,8 @@ struct fr_ctx {
   std::string asset_dir;
   std::string err;
   int W = 0, H = 0;
-  // The five streams, in creation order (all non-blocking, priority 0). DESIGN.md §5 has the table of who records and
-  // who waits for each fence and ordering event below.
+  // The five streams, in creation order (all non-blocking, priority 0; a context that presents makes a sixth,
+  // present.stream below). DESIGN.md §5 has the table of who records and who waits for each fence and ordering event.
   hipStream_t stream = nullptr;         // the context stream: entry 3, stage calls, updates
   hipStream_t atrous_stream = nullptr;  // reconstruction chain 2: pull-push -> A-Trous
   hipStream_t sibson_stream = nullptr;  // reconstruction chain 1: JFA -> Sibson
@@ -247,6 +248,29 @@ struct fr_ctx {
   size_t rq_cap = 0;
   Fence rays_done;
   uint32_t rayq_blocks = 0;
+  // Present (fr_present_enable, ctx_present.cpp): 8-bit frames to the host in stream order. Everything here is made by
+  // the first enable and stays null on a context that never presents: present.stream, the sixth stream, runs the pack
+  // kernel and the copy to the host and nothing else; per ring slot a device staging image, a pinned host image and
+  // three timed events on that stream (begin: before the pack, packed: after it, done: after the copy; done is the
+  // one fr_present_acquire waits for); ev_fork: the context stream records, the present stream waits (what a present
+  // sees). ring: tickets and slot states, no HIP in it. made: slots that have their two images.
+  // The fences of the other direction, recorded on the present stream after a pack and only ever peeked (several
+  // streams wait for one record; fr_synchronize clears them): present_read after a pack of SIBSON, PULLPUSH or an
+  // A-Trous image, for the next writers of those (sibson_stream and atrous_stream at a frame's fork, the context stream
+  // in join_recon); present_read_shd[slot] after a pack of that slot's SHADING, for the front stages of the frame that
+  // takes the slot next (entry 3 follows them) and join_recon; present_dev after a pack into the caller's memory, for
+  // fr_present_done.
+  struct Present {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr;
+    int format = 0;
+    int made = 0;
+    fr::PresentRing ring;
+    void* stage[fr::PresentRing::MAX_SLOTS] = {};
+    void* host[fr::PresentRing::MAX_SLOTS] = {};
+    struct { hipEvent_t begin, packed, done; } ev[fr::PresentRing::MAX_SLOTS] = {};
+  } present;
+  Fence present_read, present_read_shd[MAX_SLOTS], present_dev;
   int group_refs = 0;  // fr_group objects this context is a rank of (they update it through the synchronous calls)
   fr::BvhWork* bvh_work = nullptr;
   fr::SahWork* sah_work = nullptr;  // the device SAH builder's scratch (k_bvh_sah.hip): bvh_builder 2 contexts only
@@ -457,6 +481,12 @@ int tree_numbers(fr_ctx* c);
 // budget on a context that has become a rank or sharded).
 void foveation_init(fr_ctx* c);
 int foveation_check(fr_ctx* c);
+// Present (ctx_present.cpp). present_join: the context stream waits for every pack still reading a presentable image
+// (join_recon calls it). present_sync: the host waits for the present stream, and the fences are cleared
+// (fr_synchronize). present_destroy: fr_destroy's share. All three do nothing on a context that never presented.
+void present_join(fr_ctx* c);
+int present_sync(fr_ctx* c);
+void present_destroy(fr_ctx* c);
 }  // namespace fri
 static_assert(sizeof(f3) == 3 * sizeof(float), "f3 must be three packed floats");
 

@@ -1,0 +1,257 @@
+// ctx_present.cpp — present: a reconstructed image as packed 8-bit texels, in host memory through a ring of pinned
+// images (fr_present_enable, fr_present_enqueue, fr_present_acquire, fr_present_release) or in the caller's device
+// memory (fr_present_enqueue_device, fr_present_done), in stream order; and the rule on the host (fr_present_pack).
+// The kernel is k_present_pack (k_present.hip); the ring's bookkeeping is PresentRing (present_ring.h).
+//
+// Ordering. A present reads one of the images a frame's last stages write (SIBSON on sibson_stream, PULLPUSH and the
+// A-Trous pair on atrous_stream, the slot's SHADING on the context stream; stage calls and fr_write_buffer write all
+// of them on the context stream). The pack runs on present.stream, which first waits for
+//  - the context stream as of the call (ev_fork): every stage call, write and timed frame before it, and the trace
+//    half of every pipelined frame before it, whose resolve wrote SHADING;
+//  - recon_done of every slot whose flag is still up: both chains of every reconstruction enqueued before the call
+//    (sibson_stream is in order, so the last record covers the earlier ones; a flag that is down was consumed by the
+//    context stream, by join_recon, or by front_stream ahead of a front_done the context stream has taken: either way
+//    ev_fork covers it).
+// It takes no fence down and leaves stream_dirty alone, so the frames around it keep their schedule. Whoever writes
+// the image next waits for the pack's read: present_read / present_read_shd (ctx_internal.h), recorded here, waited
+// for at a frame's reconstruction fork, in enqueue_geometry and in join_recon (ctx_frame.cpp). The copy to the host
+// reads the staging image, which nothing but this stream touches, so nothing of a frame ever waits for a copy.
+#include <cstdint>
+
+#include "ctx_internal.h"
+
+using namespace fr;
+using namespace fri;
+
+namespace {
+bool format_ok(int format) { return (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_RGBA8 || (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8; }
+size_t image_bytes(const fr_ctx* c) { return (size_t)c->W * c->H * 4; }
+
+// The physical image a presentable id names at the call; -1 for any other id.
+int presentable(fr_ctx* c, int id) {
+  switch (id) {
+    case FR_BUF_SHADING: return P_shd(c);
+    case FR_BUF_SIBSON: return P_SIBSON;
+    case FR_BUF_PULLPUSH: return P_PULLPUSH;
+    case FR_BUF_ATROUS: return c->atrous_out;
+    default: return -1;
+  }
+}
+
+void free_slots(fr_ctx::Present& P) {
+  for (int i = 0; i < PresentRing::MAX_SLOTS; i++) {
+    if (P.stage[i]) hipFree(P.stage[i]);
+    if (P.host[i]) hipHostFree(P.host[i]);
+    P.stage[i] = P.host[i] = nullptr;
+  }
+  P.made = 0;
+}
+
+// The stream, the events and the fences, once; then the images of slots made .. slots - 1. All or nothing.
+bool make_ring(fr_ctx* c, int slots) {
+  fr_ctx::Present& P = c->present;
+  bool ok = true;
+  if (!P.stream) {
+    ok = hipStreamCreateWithPriority(&P.stream, hipStreamNonBlocking, 0) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&P.ev_fork, hipEventDisableTiming) == hipSuccess;
+    for (auto& e : P.ev)
+      ok = ok && hipEventCreate(&e.begin) == hipSuccess && hipEventCreate(&e.packed) == hipSuccess &&
+           hipEventCreate(&e.done) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->present_read.ev, hipEventDisableTiming) == hipSuccess;
+    for (Fence& f : c->present_read_shd) ok = ok && hipEventCreateWithFlags(&f.ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->present_dev.ev, hipEventDisableTiming) == hipSuccess;
+  }
+  for (int i = P.made; ok && i < slots; i++) {
+    ok = hipMalloc(&P.stage[i], image_bytes(c)) == hipSuccess && hipHostMalloc(&P.host[i], image_bytes(c), hipHostMallocDefault) == hipSuccess;
+    if (ok) P.made = i + 1;
+  }
+  if (!ok) (void)hipGetLastError();
+  return ok;
+}
+
+// What both enqueue forms refuse before anything is enqueued; *phys: the image to pack.
+int check_enqueue(fr_ctx* c, const std::string& name, int id, int* phys) {
+  if ((*phys = presentable(c, id)) < 0)
+    return fail(c, FR_E_INVALID, name + ": the buffer is not FR_BUF_SHADING, FR_BUF_SIBSON, FR_BUF_PULLPUSH or FR_BUF_ATROUS");
+  if (c->group_refs > 0 || c->U.shard_count > 1)
+    return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded");
+  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
+  return FR_OK;
+}
+
+// The present stream behind what wrote the image (the head of this file), then the pack into dst, then the fence
+// its next writer waits for. begin / packed: a slot's timing events, or NULL.
+int enqueue_pack(fr_ctx* c, int phys, void* dst, hipEvent_t begin, hipEvent_t packed) {
+  fr_ctx::Present& P = c->present;
+  HIP_TRY(c, hipEventRecord(P.ev_fork, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(P.stream, P.ev_fork, 0));
+  for (const Fence& f : c->recon_done) HIP_TRY(c, f.peek(P.stream));
+  if (begin) HIP_TRY(c, hipEventRecord(begin, P.stream));
+  launch_present_pack(c->img[phys], c->W, c->H, P.format, dst, P.stream);
+  if (int rc = check_launch(c)) return rc;
+  if (packed) HIP_TRY(c, hipEventRecord(packed, P.stream));
+  Fence& read = phys == P_shd(c) ? c->present_read_shd[c->slot] : c->present_read;
+  HIP_TRY(c, read.record(P.stream));
+  return FR_OK;
+}
+}  // namespace
+
+namespace fri {
+void present_join(fr_ctx* c) {
+  c->present_read.peek(c->stream);
+  for (const Fence& f : c->present_read_shd) f.peek(c->stream);
+}
+
+int present_sync(fr_ctx* c) {
+  if (!c->present.stream) return FR_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->present.stream));
+  c->present_read.pending = false;
+  for (Fence& f : c->present_read_shd) f.pending = false;
+  return FR_OK;
+}
+
+void present_destroy(fr_ctx* c) {
+  fr_ctx::Present& P = c->present;
+  if (P.stream) hipStreamSynchronize(P.stream);
+  free_slots(P);
+  for (auto& e : P.ev)
+    for (hipEvent_t v : {e.begin, e.packed, e.done}) if (v) hipEventDestroy(v);
+  if (P.ev_fork) hipEventDestroy(P.ev_fork);
+  // (the stream has drained, so no record of a fence is in flight: the flags go down with their events)
+  if (c->present_read.ev) hipEventDestroy(c->present_read.ev);
+  for (Fence& f : c->present_read_shd) if (f.ev) hipEventDestroy(f.ev);
+  if (c->present_dev.ev) hipEventDestroy(c->present_dev.ev);
+  c->present_read = c->present_dev = Fence{};
+  for (Fence& f : c->present_read_shd) f = Fence{};
+  if (P.stream) hipStreamDestroy(P.stream);
+  P = fr_ctx::Present{};
+}
+}  // namespace fri
+
+extern "C" {
+
+int fr_present_pack(const float* rgba, int width, int height, int format, uint8_t* out) {
+  if (!rgba || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format)) return FR_E_INVALID;
+  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
+  for (int r = 0; r < height; r++) {
+    const float* in = rgba + (size_t)(top_down ? height - 1 - r : r) * width * 4;
+    uint8_t* o = out + (size_t)r * width * 4;
+    for (int x = 0; x < width; x++) {
+      const uint32_t w = present_texel(mk4(in[4 * x], in[4 * x + 1], in[4 * x + 2], in[4 * x + 3]), bgra);
+      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
+    }
+  }
+  return FR_OK;
+}
+
+int fr_present_enable(fr_ctx* c, int slots, int format) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_present_enable";
+  if (slots < 0 || slots > PresentRing::MAX_SLOTS) return fail(c, FR_E_INVALID, name + ": slots outside 0..8");
+  if (slots > 0 && !format_ok(format)) return fail(c, FR_E_INVALID, name + ": unknown format");
+  if (c->W > 32767 || c->H > 32767) return fail(c, FR_E_UNSUPPORTED, name + ": a screen above 32767 pixels a side");
+  fr_ctx::Present& P = c->present;
+  if (slots == P.ring.n && (slots == 0 || format == P.format)) return FR_OK;  // nothing changes
+  if (int rc = quiesce(c)) return rc;
+  if (int rc = present_sync(c)) return rc;
+  if (!P.ring.all_free()) return fail(c, FR_E_STATE, name + ": a ticket of the ring in place is not released");
+  if (slots > 0 && !make_ring(c, slots)) {
+    present_destroy(c);
+    return fail(c, FR_E_NOMEM, name + ": allocation failed (nothing is kept, presenting is off)");
+  }
+  if (slots > 0) P.format = format;
+  P.ring.reset(slots);
+  return FR_OK;
+}
+
+int fr_present_enqueue(fr_ctx* c, int buffer_id, uint64_t* ticket) {
+  if (!c || !ticket) return FR_E_INVALID;
+  const std::string name = "fr_present_enqueue";
+  int phys;
+  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  fr_ctx::Present& P = c->present;
+  uint64_t t = 0;
+  const int s = P.ring.enqueue(&t);
+  if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
+  hipSetDevice(c->cfg.device);
+  // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
+  int rc = enqueue_pack(c, phys, P.stage[s], P.ev[s].begin, P.ev[s].packed);
+  if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], image_bytes(c), hipMemcpyDeviceToHost, P.stream) != hipSuccess)
+    rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
+  if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
+  if (rc != FR_OK) {
+    P.ring.release(s);
+    return rc;
+  }
+  *ticket = t;
+  return FR_OK;
+}
+
+int fr_present_acquire(fr_ctx* c, uint64_t ticket, int wait, const void** host) {
+  if (!c || !host) return FR_E_INVALID;
+  const std::string name = "fr_present_acquire";
+  fr_ctx::Present& P = c->present;
+  if (P.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
+  const int s = P.ring.find(ticket);
+  if (s < 0) return fail(c, FR_E_INVALID, name + ": unknown or released ticket");
+  if (P.ring.state[s] != PresentRing::HELD) {
+    hipSetDevice(c->cfg.device);
+    const hipError_t e = wait ? hipEventSynchronize(P.ev[s].done) : hipEventQuery(P.ev[s].done);
+    if (e == hipErrorNotReady) return FR_PRESENT_PENDING;
+    if (e != hipSuccess) return fail(c, FR_E_HIP, name + ": " + hipGetErrorString(e));
+    P.ring.acquired(s);
+  }
+  *host = P.host[s];
+  return FR_OK;
+}
+
+int fr_present_release(fr_ctx* c, uint64_t ticket) {
+  if (!c) return FR_E_INVALID;
+  fr_ctx::Present& P = c->present;
+  if (P.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_release: presenting is not enabled (fr_present_enable)");
+  const int s = P.ring.find(ticket);
+  if (s < 0) return fail(c, FR_E_INVALID, "fr_present_release: unknown or released ticket");
+  P.ring.release(s);
+  return FR_OK;
+}
+
+int fr_present_times(fr_ctx* c, uint64_t ticket, float* pack_ms, float* copy_ms) {
+  if (!c) return FR_E_INVALID;
+  fr_ctx::Present& P = c->present;
+  if (P.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_times: presenting is not enabled (fr_present_enable)");
+  const int s = P.ring.find(ticket);
+  if (s < 0) return fail(c, FR_E_INVALID, "fr_present_times: unknown or released ticket");
+  if (P.ring.state[s] != PresentRing::HELD) return fail(c, FR_E_STATE, "fr_present_times: the ticket is not acquired");
+  hipSetDevice(c->cfg.device);
+  float a = 0.0f, b = 0.0f;
+  HIP_TRY(c, hipEventElapsedTime(&a, P.ev[s].begin, P.ev[s].packed));
+  HIP_TRY(c, hipEventElapsedTime(&b, P.ev[s].packed, P.ev[s].done));
+  if (pack_ms) *pack_ms = a;
+  if (copy_ms) *copy_ms = b;
+  return FR_OK;
+}
+
+int fr_present_enqueue_device(fr_ctx* c, int buffer_id, void* device_dst, size_t bytes) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_present_enqueue_device";
+  if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
+    return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
+  if (bytes != image_bytes(c)) return fail(c, FR_E_INVALID, name + ": bytes != W * H * 4");
+  int phys;
+  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  hipSetDevice(c->cfg.device);
+  if (int rc = enqueue_pack(c, phys, device_dst, nullptr, nullptr)) return rc;
+  HIP_TRY(c, c->present_dev.record(c->present.stream));
+  return FR_OK;
+}
+
+int fr_present_done(fr_ctx* c, void* stream) {
+  if (!c) return FR_E_INVALID;
+  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_done: presenting is not enabled (fr_present_enable)");
+  if (!c->present_dev.pending) return FR_OK;
+  hipSetDevice(c->cfg.device);
+  HIP_TRY(c, c->present_dev.peek(static_cast<hipStream_t>(stream)));
+  return FR_OK;
+}
+
+}  // extern "C"

@@ -90,6 +90,10 @@ void launch_shard_unpack(const FrameUniforms& U, int rank, const f4* slab, f4* b
 void launch_logpolar(const f4* in, f4* fwd, f4* inv, int W, int H, f2 gaze, hipStream_t stream);
 void launch_composite(const f4* views, int nviews, int W, int H, f4* out, hipStream_t stream);
 
+// k_present.hip: src (W x H RGBA32F) to W * H packed 8-bit texels at out (16-byte aligned), by present_texel
+// (fr_math.h); format: FR_PRESENT_RGBA8 or FR_PRESENT_BGRA8, FR_PRESENT_TOP_DOWN or-ed in (checked by the caller)
+void launch_present_pack(const f4* src, int W, int H, int format, void* out, hipStream_t stream);
+
 // k_jfa.hip, k_sibson.hip
 // A context's JumpFlooding state: G, H the passes' ping-pong, F the final state (retained while the seed set stays),
 // seeds the seed bitmap of the last launch (jfa_seed_words), ctl the JFA_CTL_* words. gen: the launch's generation

@@ -1,0 +1,61 @@
+// k_present.hip — present: one RGBA32F image to packed 8-bit texels (fr_present_enqueue, fr_present_enqueue_device).
+// The rule is present_unorm8 / present_texel in fr_math.h, the text fr_present_pack runs on the host. The kernel is
+// bound by memory (20 B moved per texel, a dozen operations): no LDS, no atomics, a grid sized to the image, one lane
+// per four consecutive texels of one output row (four 16-byte loads, one 16-byte store), so a wave reads 4 KiB and
+// writes 1 KiB of one row, both contiguous.
+#include <hip/hip_runtime.h>
+
+#include "fr_device.h"
+#include "k_launch.h"
+
+namespace fr {
+
+#define PRESENT_BX 64  // lanes along a row: one wave per block row
+#define PRESENT_BY 4   // rows per block
+
+// lanes = ceil(W / 4). Output row r is image row r, or H - 1 - r (top_down); out is tight, W words per row. A lane
+// whose four texels are all inside the row writes them with one 16-byte store when W is a multiple of four (ALIGNED:
+// every row of `out`, itself 16-byte aligned, then starts on a 16-byte boundary) and with word stores otherwise; the
+// last lane of a row whose width is no multiple of four writes the W & 3 texels that are left. (Two instances, not a
+// branch on W & 3: the compiler sank the fourth word's store out of both arms and left 12 + 4 bytes in each. The
+// alpha float is never used, so the loads come out as 12 bytes of each 16-byte texel.)
+template <bool ALIGNED>
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_pack(const f4* __restrict__ src, int W, int H, int lanes,
+                                                                         bool bgra, bool top_down,
+                                                                         uint32_t* __restrict__ out) {
+  const int j = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int r = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
+  if (j >= lanes || r >= H) return;
+  const int x = 4 * j;
+  const int sr = top_down ? H - 1 - r : r;
+  const f4* in = src + (size_t)sr * W + x;
+  uint32_t* o = out + (size_t)r * W + x;
+  if (x + 4 <= W) {
+    const f4 t0 = in[0], t1 = in[1], t2 = in[2], t3 = in[3];
+    const uint4 q = make_uint4(present_texel(t0, bgra), present_texel(t1, bgra), present_texel(t2, bgra),
+                               present_texel(t3, bgra));
+    if (ALIGNED) {
+      *reinterpret_cast<uint4*>(o) = q;
+    } else {
+      o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    }
+  } else {
+    for (int k = 0; x + k < W; k++) o[k] = present_texel(in[k], bgra);
+  }
+}
+
+// format: FR_PRESENT_RGBA8 (0) or FR_PRESENT_BGRA8 (1), FR_PRESENT_TOP_DOWN (0x100) or-ed in; the callers have checked
+// it and the size (1..32767 each way, so the grid's y extent is at most 8192). out: W * H words, 16-byte aligned.
+void launch_present_pack(const f4* src, int W, int H, int format, void* out, hipStream_t stream) {
+  const int lanes = (W + 3) / 4;
+  const dim3 grid((unsigned)((lanes + PRESENT_BX - 1) / PRESENT_BX), (unsigned)((H + PRESENT_BY - 1) / PRESENT_BY));
+  const bool bgra = (format & 0xFF) == 1, top_down = (format & 0x100) != 0;
+  if ((W & 3) == 0)
+    hipLaunchKernelGGL(k_present_pack<true>, grid, dim3(PRESENT_BX, PRESENT_BY), 0, stream, src, W, H, lanes, bgra, top_down,
+                       static_cast<uint32_t*>(out));
+  else
+    hipLaunchKernelGGL(k_present_pack<false>, grid, dim3(PRESENT_BX, PRESENT_BY), 0, stream, src, W, H, lanes, bgra, top_down,
+                       static_cast<uint32_t*>(out));
+}
+
+}  // namespace fr

@@ -43,6 +43,9 @@ MASK_SALIENCY, MASK_LOGPOLAR, MASK_UNIFORM2X2, MASK_ALL, MASK_LOGPOLAR_SIGNED = 
 MASK_ECCENTRIC, MASK_CALLER = 5, 6  # fr_set_foveation / fr_set_sampling_mask
 # fr_set_pipeline_mode
 PIPELINE_THROUGHPUT, PIPELINE_LATENCY = 0, 1
+# fr_present_enable: the byte order of a presented texel; TOP_DOWN is or-ed in (row 0 of the output = the top row)
+FR_PRESENT_RGBA8, FR_PRESENT_BGRA8, FR_PRESENT_TOP_DOWN = 0, 1, 0x100
+FR_PRESENT_PENDING = 1  # fr_present_acquire without waiting: the frame is not there yet
 SCENES = {"box": SCENE_BOX, "bunny": SCENE_BUNNY, "vokselia": SCENE_VOKSELIA}
 MASKS = {"saliency": MASK_SALIENCY, "logpolar": MASK_LOGPOLAR, "uniform": MASK_UNIFORM2X2, "all": MASK_ALL,
          "logpolar10": MASK_LOGPOLAR_SIGNED}
@@ -256,6 +259,14 @@ _SIGS = {
     "fr_set_sampling_mask": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_set_sampling_mask_enqueue": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     "fr_sampling_mask_consumed": [C.c_void_p, C.c_void_p],
+    "fr_present_pack": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "fr_present_enable": [C.c_void_p, C.c_int, C.c_int],
+    "fr_present_enqueue": [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)],
+    "fr_present_acquire": [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)],
+    "fr_present_release": [C.c_void_p, C.c_uint64],
+    "fr_present_times": [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "fr_present_enqueue_device": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
+    "fr_present_done": [C.c_void_p, C.c_void_p],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -1044,6 +1055,56 @@ class PathTracer:
         s = getattr(stream, "cuda_stream", stream)
         self._check(_lib.fr_sampling_mask_consumed(self._ctx, C.c_void_p(int(s)) if s else None))
 
+    # Present: 8-bit frames in stream order (fr_present_enable and the calls beside it in include/fovrt.h)
+    def present_enable(self, slots, format=FR_PRESENT_RGBA8):
+        """fr_present_enable: a ring of `slots` (1..8) pinned host images of H x W x 4 bytes in `format`
+        (FR_PRESENT_RGBA8 or FR_PRESENT_BGRA8, FR_PRESENT_TOP_DOWN or-ed in); slots=0 turns presenting off."""
+        self._check(_lib.fr_present_enable(self._ctx, int(slots), int(format)))
+
+    def present(self, buffer) -> int:
+        """fr_present_enqueue: the buffer (SHADING, SIBSON, PULLPUSH or ATROUS) as it stands at this place of the
+        stream order, on its way to the host without waiting for the GPU; returns the ticket. FovrtError with
+        FR_E_STATE when every slot is held."""
+        t = C.c_uint64()
+        self._check(_lib.fr_present_enqueue(self._ctx, int(buffer), C.byref(t)))
+        return t.value
+
+    def present_acquire(self, ticket, wait=True):
+        """fr_present_acquire: the frame of `ticket` as an (H, W, 4) uint8 view over the slot's pinned image, valid
+        until present_release(ticket); None while the frame is pending (wait=False only)."""
+        p = C.c_void_p()
+        rc = _lib.fr_present_acquire(self._ctx, int(ticket), int(bool(wait)), C.byref(p))
+        if rc == FR_PRESENT_PENDING:
+            return None
+        self._check(rc)
+        buf = (C.c_uint8 * (self.width * self.height * 4)).from_address(p.value)
+        a = np.frombuffer(buf, np.uint8).reshape(self.height, self.width, 4)
+        a.flags.writeable = False
+        return a
+
+    def present_release(self, ticket):
+        """fr_present_release: the slot of `ticket` is free again (acquired or not); its view is no longer valid."""
+        self._check(_lib.fr_present_release(self._ctx, int(ticket)))
+
+    def present_times(self, ticket) -> dict:
+        """fr_present_times: the pack kernel's and the host copy's time of an acquired ticket, in ms."""
+        a, b = C.c_float(), C.c_float()
+        self._check(_lib.fr_present_times(self._ctx, int(ticket), C.byref(a), C.byref(b)))
+        return {"pack_ms": a.value, "copy_ms": b.value}
+
+    def present_to(self, buffer, tensor):
+        """fr_present_enqueue_device: the same pack straight into device memory, H * W * 4 bytes, 16-byte aligned
+        (a torch uint8 tensor or anything with data_ptr() and numel() * element_size()); read it on a stream that
+        present_done() has ordered behind the pack."""
+        nbytes = tensor.numel() * tensor.element_size()
+        self._check(_lib.fr_present_enqueue_device(self._ctx, int(buffer), self._device_ptr(tensor), nbytes))
+
+    def present_done(self, stream=None):
+        """fr_present_done: `stream` (a torch stream, a raw hipStream_t, or None for the null stream) waits on the
+        device for the last present_to(). Does not block the host."""
+        s = getattr(stream, "cuda_stream", stream)
+        self._check(_lib.fr_present_done(self._ctx, C.c_void_p(int(s)) if s else None))
+
     def set_normals(self, nrm: np.ndarray):
         """New shading normals (ntris x 3 x 3 float32, scene triangle order) for the triangles that have
         normals; positions, tree, texture coordinates and flags stay."""
@@ -1310,6 +1371,20 @@ def foveation_mask(width, height, gaze, r2, floor_ranks=1, count_only=False):
     if rc:
         raise FovrtError(rc, "fr_foveation_mask: bad argument")
     return n.value if count_only else (m, n.value)
+
+
+def present_pack(rgba, format=FR_PRESENT_RGBA8) -> np.ndarray:
+    """fr_present_pack (host only): an (H, W, 4) float32 image as (H, W, 4) uint8 by the present rule, through the
+    function the kernel runs."""
+    lib = load_library()
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("present_pack: an (H, W, 4) float32 image")
+    out = np.empty(a.shape, np.uint8)
+    rc = lib.fr_present_pack(C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], int(format), C.c_void_p(out.ctypes.data))
+    if rc:
+        raise FovrtError(rc, "fr_present_pack: bad size or format")
+    return out
 
 
 def shard_plan(width, height, tile, count, weights=None) -> np.ndarray:

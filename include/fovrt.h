@@ -945,6 +945,70 @@ int fr_snapshot_bytes(fr_ctx* ctx, size_t* bytes);
 int fr_snapshot(fr_ctx* ctx, void* host, size_t bytes);
 int fr_restore(fr_ctx* ctx, const void* host, size_t bytes);
 
+/* Present: a reconstructed image as packed 8-bit texels, delivered in stream order without draining the context (the
+ * reference's last step: renderAll draws the float textures into an 8-bit framebuffer, FR/main.cpp:26-113, which
+ * saveBMP24 reads back as BGRA bytes, bottom row first, FR/gui.cpp:315-355). Nothing here changes a context that does
+ * not use it: a context that never calls fr_present_enable creates the streams it created and enqueues what it enqueued.
+ *
+ * The rule, with one right answer in bytes. For a channel value x (fp32), every operation rounded on its own, no fma:
+ *   v = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f)        NaN -> 0, -Inf -> 0, +Inf -> 1, -0 -> 0
+ *   q = (uint8_t)(uint32_t)(v * 255.0f + 0.5f)               one product, one sum, truncation
+ * GL's float -> UNORM8 conversion with round half up; k / 255 gives k. The stored values are display values already
+ * (the tone map and its power are applied in the shading resolve), so there is no transfer curve. r, g and b are
+ * converted, the alpha byte is always 255. FR_PRESENT_RGBA8: bytes r g b a per texel; FR_PRESENT_BGRA8: b g r a. Row 0
+ * of the output is the bottom row, as in every buffer of the engine (BGRA8 is then the payload saveBMP24 writes);
+ * with FR_PRESENT_TOP_DOWN or-ed into the format, output row r is image row H - 1 - r. The output is tight: W * 4
+ * bytes per row, W * H * 4 in all. fr_present_pack states the rule on the host, without a device, through the function
+ * the kernel runs (rgba: W * H * 4 floats); FR_E_INVALID: a NULL pointer, a size outside 1..32767, an unknown format.
+ *
+ * fr_present_enable(ctx, slots, format), slots 1..8: the first call waits for the context's pending work and makes
+ * everything the feature needs: one more stream (the present stream), per slot a device staging image and a pinned
+ * host image of W * H * 4 bytes with their events, and the fences that order later frames behind a present's read.
+ * FR_E_NOMEM keeps nothing and leaves the feature off. A later call with other arguments waits, requires every ticket
+ * to be released (FR_E_STATE otherwise) and remakes the ring (tickets keep counting); with the same arguments it does
+ * nothing. slots = 0 turns the feature off under the same condition: the other calls then return FR_E_STATE; nothing
+ * is freed before fr_destroy. No other call of the feature allocates.
+ *
+ * What a present sees: the buffer as it stands at the call's place in the stream order, behind every frame, stage call
+ * and write made or enqueued before the call and ahead of every one after it. FR_BUF_SHADING, FR_BUF_SIBSON,
+ * FR_BUF_PULLPUSH and FR_BUF_ATROUS are accepted and resolved at the call (SHADING is this frame's, ATROUS the last
+ * A-Trous output). fr_present_enqueue makes no host wait and no copy to the host that anything waits for: the present
+ * stream waits, on the device, for what writes the image, packs it into the next free slot's staging image and copies
+ * that to the slot's pinned image; frames enqueued afterwards run meanwhile, and whatever overwrites the image next
+ * waits for the pack's read only. *ticket counts from 1. When every slot is held (enqueued and not yet released) the
+ * call returns FR_E_STATE and enqueues nothing: that is the backpressure.
+ * fr_present_acquire(ctx, ticket, wait, &host): wait = 1 blocks until that slot's copy has landed, and on nothing else
+ * (not on the context: later frames keep running); wait = 0 returns FR_PRESENT_PENDING or FR_OK. *host is the slot's
+ * pinned image, borrowed until fr_present_release. Tickets are acquired and released in any order; a ticket may be
+ * released without ever being acquired (the slot's next use is ordered behind its copy on the present stream); an
+ * unknown or already released ticket is FR_E_INVALID. fr_present_times gives, for an acquired ticket, the pack
+ * kernel's and the copy's time from the slot's events on the present stream (either pointer may be NULL; FR_E_STATE:
+ * not acquired yet).
+ * fr_present_enqueue_device is the same pack straight into the caller's device memory (16-byte aligned, bytes ==
+ * W * H * 4): no slot, no host copy. fr_present_done(ctx, stream) makes `stream` (a hipStream_t; 0 = the null stream)
+ * wait, on the device, for the last such pack, as fr_rays_consumed does for a query.
+ * fr_synchronize and fr_destroy also wait for the present stream. A snapshot carries nothing of the ring, and
+ * fr_restore leaves it alone.
+ * Refused with nothing enqueued and nothing written: a NULL context or out-pointer, another buffer id, slots outside
+ * 0..8, an unknown format, a wrong bytes, a misaligned or NULL device_dst (FR_E_INVALID); the feature not enabled, or
+ * the ring full (FR_E_STATE); either enqueue on a rank of a group or on a sharded context (FR_E_UNSUPPORTED, as with
+ * every other enqueued call).
+ * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; cropped or variable-rate (foveated)
+ * readback; a gaze-contingent blend of Sibson and A-Trous; the G-buffer channels and EXTRA; a group's composite; the
+ * ring in a snapshot. */
+#define FR_PRESENT_RGBA8    0
+#define FR_PRESENT_BGRA8    1
+#define FR_PRESENT_TOP_DOWN 0x100   /* or-ed into the format */
+#define FR_PRESENT_PENDING  1       /* fr_present_acquire, wait = 0: not there yet */
+int fr_present_pack(const float* rgba, int width, int height, int format, uint8_t* out);
+int fr_present_enable(fr_ctx* ctx, int slots, int format);
+int fr_present_enqueue(fr_ctx* ctx, int buffer_id, uint64_t* ticket);
+int fr_present_acquire(fr_ctx* ctx, uint64_t ticket, int wait, const void** host);
+int fr_present_release(fr_ctx* ctx, uint64_t ticket);
+int fr_present_times(fr_ctx* ctx, uint64_t ticket, float* pack_ms, float* copy_ms);
+int fr_present_enqueue_device(fr_ctx* ctx, int buffer_id, void* device_dst, size_t bytes);
+int fr_present_done(fr_ctx* ctx, void* stream);
+
 int fr_get_stats(fr_ctx* ctx, fr_stats* stats);
 int fr_reset_stats(fr_ctx* ctx);
 /* JumpFlooding launches of this context, in frames and stage calls alike, whose passes were skipped because the

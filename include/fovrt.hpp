@@ -37,6 +37,14 @@ inline void check(int rc, fr_ctx* ctx, const char* what) {
   }
 }
 
+// fr_present_pack: the present rule on the host, without a device; rgba holds width * height * 4 floats
+inline std::vector<uint8_t> present_pack(const std::vector<float>& rgba, int width, int height, int format = FR_PRESENT_RGBA8) {
+  if (width < 1 || height < 1 || rgba.size() != (size_t)width * height * 4) throw Error(FR_E_INVALID, "present_pack: size");
+  std::vector<uint8_t> out(rgba.size());
+  if (int rc = fr_present_pack(rgba.data(), width, height, format, out.data())) throw Error(rc, "present_pack: bad size or format");
+  return out;
+}
+
 // A GL texture name of the reference = a buffer id of the context here.
 struct Texture {
   int id = -1;
@@ -368,6 +376,38 @@ class PathTracer {
   void sampling_mask_consumed(void* stream = nullptr) {
     check(fr_sampling_mask_consumed(ctx(), stream), ctx_, "sampling_mask_consumed");
   }
+  // Present (fr_present_enable and the calls beside it): 8-bit frames in stream order. present() takes the buffer
+  // (FR_BUF_SHADING, FR_BUF_SIBSON, FR_BUF_PULLPUSH or FR_BUF_ATROUS) as it stands at the call's place in the stream
+  // order and returns its ticket without waiting for the GPU (Error with FR_E_STATE: every slot is held);
+  // present_acquire gives the slot's pinned image, W * H * 4 bytes borrowed until present_release, or nullptr while
+  // the frame is pending (wait = false only). present_to packs straight into device memory (16-byte aligned, W * H * 4
+  // bytes); present_done orders a stream (a hipStream_t; nullptr: the null stream) behind the last such pack.
+  void present_enable(int slots, int format = FR_PRESENT_RGBA8) {
+    check(fr_present_enable(ctx(), slots, format), ctx_, "present_enable");
+  }
+  uint64_t present(int buffer) {
+    uint64_t t = 0;
+    check(fr_present_enqueue(ctx(), buffer, &t), ctx_, "present");
+    return t;
+  }
+  const uint8_t* present_acquire(uint64_t ticket, bool wait = true) {
+    const void* p = nullptr;
+    const int rc = fr_present_acquire(ctx(), ticket, wait ? 1 : 0, &p);
+    if (rc == FR_PRESENT_PENDING) return nullptr;
+    check(rc, ctx_, "present_acquire");
+    return static_cast<const uint8_t*>(p);
+  }
+  void present_release(uint64_t ticket) { check(fr_present_release(ctx(), ticket), ctx_, "present_release"); }
+  struct PresentTimes { float pack_ms, copy_ms; };
+  PresentTimes present_times(uint64_t ticket) {
+    PresentTimes t{};
+    check(fr_present_times(ctx(), ticket, &t.pack_ms, &t.copy_ms), ctx_, "present_times");
+    return t;
+  }
+  void present_to(int buffer, void* device_dst, size_t bytes) {
+    check(fr_present_enqueue_device(ctx(), buffer, device_dst, bytes), ctx_, "present_to");
+  }
+  void present_done(void* stream = nullptr) { check(fr_present_done(ctx(), stream), ctx_, "present_done"); }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
