@@ -1,6 +1,8 @@
 // ctx_camera.cpp — the camera calls of include/fovrt.h: glm-compatible math (FR/Camera.cpp; glm 0.9.x,
-// GLM_FORCE_RADIANS). Pure host code: no context, no device.
+// GLM_FORCE_RADIANS), and the homography between two poses that a warped present takes
+// (fr_present_warp_from_poses). Pure host code: no context, no device.
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/fovrt.h"
 #include "scene.h"
@@ -83,10 +85,11 @@ void to_rowmajor(const M4& a, float out[16]) {
   for (int r = 0; r < 4; r++)
     for (int c = 0; c < 4; c++) out[r * 4 + c] = a.m[c][r];
 }
-bool invert_rowmajor(const float in[16], float out[16]) {  // Gauss-Jordan in f64, rounded once
+template <class T>
+bool invert_rowmajor(const T in[16], T out[16]) {  // Gauss-Jordan in f64, rounded once
   double a[4][8];
   for (int r = 0; r < 4; r++)
-    for (int c = 0; c < 8; c++) a[r][c] = c < 4 ? in[r * 4 + c] : (c - 4 == r ? 1.0 : 0.0);
+    for (int c = 0; c < 8; c++) a[r][c] = c < 4 ? (double)in[r * 4 + c] : (c - 4 == r ? 1.0 : 0.0);
   for (int c = 0; c < 4; c++) {
     int piv = c;
     for (int r = c + 1; r < 4; r++) if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
@@ -101,8 +104,19 @@ bool invert_rowmajor(const float in[16], float out[16]) {  // Gauss-Jordan in f6
     }
   }
   for (int r = 0; r < 4; r++)
-    for (int c = 0; c < 4; c++) out[r * 4 + c] = (float)a[r][c + 4];
+    for (int c = 0; c < 4; c++) out[r * 4 + c] = (T)a[r][c + 4];
   return true;
+}
+// proj * view of a pose, row-major, the fp32 matrices of fr_camera_matrices multiplied in f64
+void pose_pv_f64(const fr_camera_pose* p, double out[16]) {
+  M4 V, P;
+  pose_matrices(p, V, P);
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) {
+      double s = 0.0;
+      for (int k = 0; k < 4; k++) s += (double)P.m[k][r] * (double)V.m[c][k];
+      out[r * 4 + c] = s;
+    }
 }
 
 }  // namespace
@@ -161,6 +175,57 @@ int fr_camera_uniforms(const fr_camera_pose* cur, const fr_camera_pose* prev, in
   // g_gaze = (w/2, h/2) ints (FR/gui.cpp:34-35); gaze = (g_gaze.x, H - g_gaze.y) (FR/PathTracer.cpp:795)
   out->gaze[0] = (float)(width / 2);
   out->gaze[1] = (float)(height - height / 2);
+  return FR_OK;
+}
+
+// The homography of a late reprojection (include/fovrt.h, "Present"): output texel centres of the display camera's
+// viewport to source texel coordinates of the rendered camera's image, through the points at one NDC depth of the
+// display camera. f64 from the fp32 matrices of fr_camera_matrices on, rounded once at the end.
+int fr_present_warp_from_poses(const fr_camera_pose* rendered, const fr_camera_pose* display, int width, int height,
+                               int out_width, int out_height, float ndc_depth, fr_present_warp* warp) {
+  if (!rendered || !display || !warp) return FR_E_INVALID;
+  for (int v : {width, height, out_width, out_height}) if (v < 1 || v > 32767) return FR_E_INVALID;
+  if (!std::isfinite(ndc_depth)) return FR_E_INVALID;
+  double Mr[16], Md[16], inv[16];
+  pose_pv_f64(rendered, Mr);
+  pose_pv_f64(display, Md);
+  for (int k = 0; k < 16; k++) if (!std::isfinite(Mr[k]) || !std::isfinite(Md[k])) return FR_E_INVALID;
+  if (!invert_rowmajor(Md, inv)) return FR_E_INVALID;
+  // A = M_r M_d^-1, formed as I + (M_r - M_d) M_d^-1: the identity exactly for equal poses
+  double A[16];
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) {
+      double s = 0.0;
+      for (int k = 0; k < 4; k++) s += (Mr[r * 4 + k] - Md[r * 4 + k]) * inv[k * 4 + c];
+      A[r * 4 + c] = (r == c ? 1.0 : 0.0) + s;
+    }
+  // The rendered camera's clip coordinate i of the display camera's NDC point (nx, ny, z, 1), nx = 2 px / ow - 1:
+  // (2 A_i0 / ow) px + (2 A_i1 / oh) py + (A_i2 z + A_i3 - A_i0 - A_i1). Source texel x = (clip_x / clip_w + 1) W / 2 =
+  // (clip_x + clip_w) (W / 2) / clip_w, the same for y; W / ow is formed by one division, so equal sizes give 1.
+  const double z = (double)ndc_depth, W = width, H = height, ow = out_width, oh = out_height;
+  double cx[3], cy[3], cw[3];
+  const auto clip_row = [&A, z](int i, double g[3]) {
+    g[0] = A[i * 4];
+    g[1] = A[i * 4 + 1];
+    g[2] = A[i * 4 + 2] * z + A[i * 4 + 3] - A[i * 4] - A[i * 4 + 1];
+  };
+  clip_row(0, cx); clip_row(1, cy); clip_row(3, cw);
+  const double g[9] = {(cx[0] + cw[0]) * W / ow, (cx[1] + cw[1]) * W / oh, (cx[2] + cw[2]) * W / 2.0,
+                       (cy[0] + cw[0]) * H / ow, (cy[1] + cw[1]) * H / oh, (cy[2] + cw[2]) * H / 2.0,
+                       cw[0] * 2.0 / ow,         cw[1] * 2.0 / oh,         cw[2]};
+  for (double v : g) if (!std::isfinite(v)) return FR_E_INVALID;
+  // g[8] is clip w at output corner (0, 0): it must be positive (in front of the rendered camera's eye plane) and not
+  // lost against the change of w across the output
+  const double span = std::max(std::max(fabs(g[6]) * ow, fabs(g[7]) * oh), fabs(g[8]));
+  if (!(g[8] > span * (1.0 / 1048576.0))) return FR_E_INVALID;
+  fr_present_warp out;
+  for (int k = 0; k < 9; k++) {
+    out.h[k] = (float)(g[k] / g[8]);
+    if (!std::isfinite(out.h[k])) return FR_E_INVALID;
+  }
+  out.out_width = out_width;
+  out.out_height = out_height;
+  *warp = out;
   return FR_OK;
 }
 

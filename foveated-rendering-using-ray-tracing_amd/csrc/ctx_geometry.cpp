@@ -660,7 +660,10 @@ int fr_model_pose_enable(fr_ctx* c, int on) {
     f3** const arrays[4] = {&c->pose_rest_pos, &c->pose_rest_nrm, &c->pose_stage_pos, &c->pose_stage_nrm};
     const size_t bytes = pose_array_bytes(std::max(nt, 1));
     bool ok = true;
-    for (f3** p : arrays) ok = ok && hipMalloc((void**)p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess;
+    // (cleared on the context stream, ahead of the capture below: the streams are non-blocking, so a clear on the
+    // null stream is ordered against none of them and could land on top of the captured rest geometry)
+    for (f3** p : arrays)
+      ok = ok && hipMalloc((void**)p, bytes) == hipSuccess && hipMemsetAsync(*p, 0, bytes, c->stream) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
       for (f3** p : arrays) { if (*p) hipFree(*p); *p = nullptr; }
@@ -744,7 +747,8 @@ int fr_model_visibility_enable(fr_ctx* c, int on) {
   if (int rc = quiesce(c)) return rc;
   if (!c->vis_pos) {
     const size_t bytes = pose_array_bytes(std::max(c->scene.num_tris(), 1));
-    if (hipMalloc((void**)&c->vis_pos, bytes) != hipSuccess || hipMemset(c->vis_pos, 0, bytes) != hipSuccess) {
+    // (cleared on the context stream, ahead of the copy below, for the reason given in fr_model_pose_enable)
+    if (hipMalloc((void**)&c->vis_pos, bytes) != hipSuccess || hipMemsetAsync(c->vis_pos, 0, bytes, c->stream) != hipSuccess) {
       (void)hipGetLastError();
       if (c->vis_pos) hipFree(c->vis_pos);
       c->vis_pos = nullptr;

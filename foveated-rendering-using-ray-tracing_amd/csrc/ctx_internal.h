@@ -500,5 +500,8 @@ template <class T>
 inline hipError_t dalloc(T** p, size_t count) {
   hipError_t e = hipMalloc((void**)p, count * sizeof(T) + 16);
   if (e != hipSuccess) return e;
-  return hipMemset(*p, 0, count * sizeof(T) + 16);
+  // The clear runs on the null stream, which is ordered against none of the context's streams (all non-blocking): the
+  // host waits for it here, or it could land on top of what a stream writes into the new array next.
+  e = hipMemset(*p, 0, count * sizeof(T) + 16);
+  return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }

@@ -2,6 +2,10 @@
 // images (fr_present_enable, fr_present_enqueue, fr_present_acquire, fr_present_release) or in the caller's device
 // memory (fr_present_enqueue_device, fr_present_done), in stream order; and the rule on the host (fr_present_pack).
 // The kernel is k_present_pack (k_present.hip); the ring's bookkeeping is PresentRing (present_ring.h).
+// fr_present_enqueue_warped and fr_present_enqueue_warped_device are the same two calls with k_present_warp in the
+// pack's place (a homography between the image and the texels: late reprojection, crop, scale), and
+// fr_present_warp_pack is that rule on the host; the ordering below is theirs unchanged. A warped slot carries
+// ow * oh * 4 bytes to the host, no more.
 //
 // Ordering. A present reads one of the images a frame's last stages write (SIBSON on sibson_stream, PULLPUSH and the
 // A-Trous pair on atrous_stream, the slot's SHADING on the context stream; stage calls and fr_write_buffer write all
@@ -16,6 +20,7 @@
 // the image next waits for the pack's read: present_read / present_read_shd (ctx_internal.h), recorded here, waited
 // for at a frame's reconstruction fork, in enqueue_geometry and in join_recon (ctx_frame.cpp). The copy to the host
 // reads the staging image, which nothing but this stream touches, so nothing of a frame ever waits for a copy.
+#include <cmath>
 #include <cstdint>
 
 #include "ctx_internal.h"
@@ -45,6 +50,17 @@ void free_slots(fr_ctx::Present& P) {
     P.stage[i] = P.host[i] = nullptr;
   }
   P.made = 0;
+}
+
+// A warp as the host rule and both warped enqueues take it: nine finite coefficients and an output no larger than the
+// W x H source either way (0, 0: the source's size). *ow, *oh: the size to produce.
+bool warp_ok(const fr_present_warp* warp, int W, int H, int* ow, int* oh) {
+  if (!warp) return false;
+  for (float v : warp->h) if (!std::isfinite(v)) return false;
+  const bool whole = warp->out_width == 0 && warp->out_height == 0;
+  *ow = whole ? W : warp->out_width;
+  *oh = whole ? H : warp->out_height;
+  return *ow >= 1 && *ow <= W && *oh >= 1 && *oh <= H;
 }
 
 // The stream, the events and the fences, once; then the images of slots made .. slots - 1. All or nothing.
@@ -80,18 +96,67 @@ int check_enqueue(fr_ctx* c, const std::string& name, int id, int* phys) {
 }
 
 // The present stream behind what wrote the image (the head of this file), then the pack into dst, then the fence
-// its next writer waits for. begin / packed: a slot's timing events, or NULL.
-int enqueue_pack(fr_ctx* c, int phys, void* dst, hipEvent_t begin, hipEvent_t packed) {
+// its next writer waits for. begin / packed: a slot's timing events, or NULL. warp: NULL for the plain pack, else the
+// checked homography with its output size ow x oh (k_present_warp takes them by value: nothing is read after the call).
+int enqueue_pack(fr_ctx* c, int phys, const fr_present_warp* warp, int ow, int oh, void* dst, hipEvent_t begin,
+                 hipEvent_t packed) {
   fr_ctx::Present& P = c->present;
   HIP_TRY(c, hipEventRecord(P.ev_fork, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(P.stream, P.ev_fork, 0));
   for (const Fence& f : c->recon_done) HIP_TRY(c, f.peek(P.stream));
   if (begin) HIP_TRY(c, hipEventRecord(begin, P.stream));
-  launch_present_pack(c->img[phys], c->W, c->H, P.format, dst, P.stream);
+  if (warp)
+    launch_present_warp(c->img[phys], c->W, c->H, P.format, warp->h, ow, oh, dst, P.stream);
+  else
+    launch_present_pack(c->img[phys], c->W, c->H, P.format, dst, P.stream);
   if (int rc = check_launch(c)) return rc;
   if (packed) HIP_TRY(c, hipEventRecord(packed, P.stream));
   Fence& read = phys == P_shd(c) ? c->present_read_shd[c->slot] : c->present_read;
   HIP_TRY(c, read.record(P.stream));
+  return FR_OK;
+}
+
+// fr_present_enqueue (warp NULL) and fr_present_enqueue_warped: into the next free slot and on to its pinned image.
+int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_warp* warp, bool warped, uint64_t* ticket) {
+  if (!c || !ticket) return FR_E_INVALID;
+  int ow = c->W, oh = c->H;
+  if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
+    return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
+  int phys;
+  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  fr_ctx::Present& P = c->present;
+  uint64_t t = 0;
+  const int s = P.ring.enqueue(&t);
+  if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
+  hipSetDevice(c->cfg.device);
+  // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
+  int rc = enqueue_pack(c, phys, warped ? warp : nullptr, ow, oh, P.stage[s], P.ev[s].begin, P.ev[s].packed);
+  if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], (size_t)ow * oh * 4, hipMemcpyDeviceToHost, P.stream) != hipSuccess)
+    rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
+  if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
+  if (rc != FR_OK) {
+    P.ring.release(s);
+    return rc;
+  }
+  *ticket = t;
+  return FR_OK;
+}
+
+// fr_present_enqueue_device (warp NULL) and fr_present_enqueue_warped_device: straight into the caller's memory.
+int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_warp* warp, bool warped, void* device_dst,
+                   size_t bytes) {
+  if (!c) return FR_E_INVALID;
+  int ow = c->W, oh = c->H;
+  if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
+    return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
+  if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
+    return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
+  if (bytes != (size_t)ow * oh * 4) return fail(c, FR_E_INVALID, name + ": bytes != the output's width * height * 4");
+  int phys;
+  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  hipSetDevice(c->cfg.device);
+  if (int rc = enqueue_pack(c, phys, warped ? warp : nullptr, ow, oh, device_dst, nullptr, nullptr)) return rc;
+  HIP_TRY(c, c->present_dev.record(c->present.stream));
   return FR_OK;
 }
 }  // namespace
@@ -144,6 +209,26 @@ int fr_present_pack(const float* rgba, int width, int height, int format, uint8_
   return FR_OK;
 }
 
+int fr_present_warp_pack(const float* rgba, int width, int height, int format, const fr_present_warp* warp, uint8_t* out) {
+  if (!rgba || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format)) return FR_E_INVALID;
+  int ow, oh;
+  if (!warp_ok(warp, width, height, &ow, &oh)) return FR_E_INVALID;
+  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
+  const auto fetch = [rgba, width](int i, int row) {
+    const float* t = rgba + ((size_t)row * width + i) * 4;
+    return mk4(t[0], t[1], t[2], t[3]);
+  };
+  for (int r = 0; r < oh; r++) {
+    const int y = top_down ? oh - 1 - r : r;
+    uint8_t* o = out + (size_t)r * ow * 4;
+    for (int x = 0; x < ow; x++) {
+      const uint32_t w = present_warp_texel(fetch, width, height, warp->h, x, y, bgra);
+      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
+    }
+  }
+  return FR_OK;
+}
+
 int fr_present_enable(fr_ctx* c, int slots, int format) {
   if (!c) return FR_E_INVALID;
   const std::string name = "fr_present_enable";
@@ -165,26 +250,11 @@ int fr_present_enable(fr_ctx* c, int slots, int format) {
 }
 
 int fr_present_enqueue(fr_ctx* c, int buffer_id, uint64_t* ticket) {
-  if (!c || !ticket) return FR_E_INVALID;
-  const std::string name = "fr_present_enqueue";
-  int phys;
-  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
-  fr_ctx::Present& P = c->present;
-  uint64_t t = 0;
-  const int s = P.ring.enqueue(&t);
-  if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
-  hipSetDevice(c->cfg.device);
-  // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
-  int rc = enqueue_pack(c, phys, P.stage[s], P.ev[s].begin, P.ev[s].packed);
-  if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], image_bytes(c), hipMemcpyDeviceToHost, P.stream) != hipSuccess)
-    rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
-  if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
-  if (rc != FR_OK) {
-    P.ring.release(s);
-    return rc;
-  }
-  *ticket = t;
-  return FR_OK;
+  return enqueue_host(c, "fr_present_enqueue", buffer_id, nullptr, false, ticket);
+}
+
+int fr_present_enqueue_warped(fr_ctx* c, int buffer_id, const fr_present_warp* warp, uint64_t* ticket) {
+  return enqueue_host(c, "fr_present_enqueue_warped", buffer_id, warp, true, ticket);
 }
 
 int fr_present_acquire(fr_ctx* c, uint64_t ticket, int wait, const void** host) {
@@ -232,17 +302,11 @@ int fr_present_times(fr_ctx* c, uint64_t ticket, float* pack_ms, float* copy_ms)
 }
 
 int fr_present_enqueue_device(fr_ctx* c, int buffer_id, void* device_dst, size_t bytes) {
-  if (!c) return FR_E_INVALID;
-  const std::string name = "fr_present_enqueue_device";
-  if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
-    return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
-  if (bytes != image_bytes(c)) return fail(c, FR_E_INVALID, name + ": bytes != W * H * 4");
-  int phys;
-  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
-  hipSetDevice(c->cfg.device);
-  if (int rc = enqueue_pack(c, phys, device_dst, nullptr, nullptr)) return rc;
-  HIP_TRY(c, c->present_dev.record(c->present.stream));
-  return FR_OK;
+  return enqueue_device(c, "fr_present_enqueue_device", buffer_id, nullptr, false, device_dst, bytes);
+}
+
+int fr_present_enqueue_warped_device(fr_ctx* c, int buffer_id, const fr_present_warp* warp, void* device_dst, size_t bytes) {
+  return enqueue_device(c, "fr_present_enqueue_warped_device", buffer_id, warp, true, device_dst, bytes);
 }
 
 int fr_present_done(fr_ctx* c, void* stream) {

@@ -93,6 +93,10 @@ void launch_composite(const f4* views, int nviews, int W, int H, f4* out, hipStr
 // k_present.hip: src (W x H RGBA32F) to W * H packed 8-bit texels at out (16-byte aligned), by present_texel
 // (fr_math.h); format: FR_PRESENT_RGBA8 or FR_PRESENT_BGRA8, FR_PRESENT_TOP_DOWN or-ed in (checked by the caller)
 void launch_present_pack(const f4* src, int W, int H, int format, void* out, hipStream_t stream);
+// The same through a homography (present_warp_texel, fr_math.h): h[9] row-major, output texel centres to source texel
+// centres, copied into the kernel's arguments by the call; 1 <= ow <= W, 1 <= oh <= H; out: ow * oh words
+void launch_present_warp(const f4* src, int W, int H, int format, const float* h, int ow, int oh, void* out,
+                         hipStream_t stream);
 
 // k_jfa.hip, k_sibson.hip
 // A context's JumpFlooding state: G, H the passes' ping-pong, F the final state (retained while the seed set stays),

@@ -58,4 +58,59 @@ void launch_present_pack(const f4* src, int W, int H, int format, void* out, hip
                        static_cast<uint32_t*>(out));
 }
 
+// k_present_warp: the same output side on an ow x oh image, each texel sampled from the W x H source through a
+// homography by present_warp_texel (fr_math.h), the function fr_present_warp_pack runs on the host. Everything the call
+// gives travels by value in the kernel arguments (the coefficients sit in scalar registers), so the launch is ordered
+// by its stream alone and keeps nothing of the caller's alive. Input side: plain per-lane 16-byte gathers, no LDS. For
+// the maps this is made for (a timewarp, a crop, a scale) a lane's four points lie along one source row or close to
+// it and neighbouring lanes read neighbouring texels, so the taps a wave shares come out of L1 / L2; a tap of weight
+// zero is never loaded (the identity reads what k_present_pack reads). No atomics, no scratch.
+struct WarpArgs {
+  float h[9];
+  int W, H, ow, oh, lanes;  // lanes = ceil(ow / 4)
+  bool bgra, top_down;
+};
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_warp(const f4* __restrict__ src, const WarpArgs a,
+                                                                         uint32_t* __restrict__ out) {
+  const int j = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int r = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
+  if (j >= a.lanes || r >= a.oh) return;
+  const int x = 4 * j;
+  const int y = a.top_down ? a.oh - 1 - r : r;
+  const int W = a.W;
+  // (present_warp_texel calls it with 0 <= i < W and 0 <= row < H only)
+  const auto fetch = [src, W](int i, int row) { return src[(size_t)row * W + i]; };
+  uint32_t* o = out + (size_t)r * a.ow + x;
+  if (x + 4 <= a.ow) {
+    const uint4 q = make_uint4(present_warp_texel(fetch, W, a.H, a.h, x, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 1, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 2, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 3, y, a.bgra));
+    if (ALIGNED) {
+      *reinterpret_cast<uint4*>(o) = q;
+    } else {
+      o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    }
+  } else {
+    for (int k = 0; x + k < a.ow; k++) o[k] = present_warp_texel(fetch, W, a.H, a.h, x + k, y, a.bgra);
+  }
+}
+
+// As launch_present_pack, with the homography h[9] and the output size (1 <= ow <= W, 1 <= oh <= H, checked by the
+// callers with the coefficients); out: ow * oh words, 16-byte aligned.
+void launch_present_warp(const f4* src, int W, int H, int format, const float* h, int ow, int oh, void* out,
+                         hipStream_t stream) {
+  WarpArgs a;
+  for (int k = 0; k < 9; k++) a.h[k] = h[k];
+  a.W = W; a.H = H; a.ow = ow; a.oh = oh; a.lanes = (ow + 3) / 4;
+  a.bgra = (format & 0xFF) == 1; a.top_down = (format & 0x100) != 0;
+  const dim3 grid((unsigned)((a.lanes + PRESENT_BX - 1) / PRESENT_BX), (unsigned)((oh + PRESENT_BY - 1) / PRESENT_BY));
+  if ((ow & 3) == 0)
+    hipLaunchKernelGGL(k_present_warp<true>, grid, dim3(PRESENT_BX, PRESENT_BY), 0, stream, src, a, static_cast<uint32_t*>(out));
+  else
+    hipLaunchKernelGGL(k_present_warp<false>, grid, dim3(PRESENT_BX, PRESENT_BY), 0, stream, src, a, static_cast<uint32_t*>(out));
+}
+
 }  // namespace fr

@@ -120,6 +120,10 @@ class fr_foveation(C.Structure):
                 ("tolerance", C.c_float)]
 
 
+class fr_present_warp(C.Structure):
+    _fields_ = [("h", C.c_float * 9), ("out_width", C.c_int), ("out_height", C.c_int)]
+
+
 class fr_ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
 
@@ -267,6 +271,11 @@ _SIGS = {
     "fr_present_times": [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "fr_present_enqueue_device": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
     "fr_present_done": [C.c_void_p, C.c_void_p],
+    "fr_present_warp_pack": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fr_present_warp), C.c_void_p],
+    "fr_present_warp_from_poses": [C.POINTER(fr_camera_pose), C.POINTER(fr_camera_pose), C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_float, C.POINTER(fr_present_warp)],
+    "fr_present_enqueue_warped": [C.c_void_p, C.c_int, C.POINTER(fr_present_warp), C.POINTER(C.c_uint64)],
+    "fr_present_enqueue_warped_device": [C.c_void_p, C.c_int, C.POINTER(fr_present_warp), C.c_void_p, C.c_size_t],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -1077,14 +1086,31 @@ class PathTracer:
         if rc == FR_PRESENT_PENDING:
             return None
         self._check(rc)
-        buf = (C.c_uint8 * (self.width * self.height * 4)).from_address(p.value)
-        a = np.frombuffer(buf, np.uint8).reshape(self.height, self.width, 4)
+        h, w = self.__dict__.get("_warped_shapes", {}).get(int(ticket), (self.height, self.width))
+        buf = (C.c_uint8 * (w * h * 4)).from_address(p.value)
+        a = np.frombuffer(buf, np.uint8).reshape(h, w, 4)
         a.flags.writeable = False
         return a
 
     def present_release(self, ticket):
         """fr_present_release: the slot of `ticket` is free again (acquired or not); its view is no longer valid."""
         self._check(_lib.fr_present_release(self._ctx, int(ticket)))
+        self.__dict__.get("_warped_shapes", {}).pop(int(ticket), None)
+
+    def present_warped(self, buffer, warp) -> int:
+        """fr_present_enqueue_warped: as present(), through the homography `warp` (a PresentWarp): late reprojection,
+        crop or scale. present_acquire gives the ticket's image in the warp's output shape."""
+        t = C.c_uint64()
+        self._check(_lib.fr_present_enqueue_warped(self._ctx, int(buffer), C.byref(warp.c_struct()), C.byref(t)))
+        self.__dict__.setdefault("_warped_shapes", {})[t.value] = warp.shape(self.width, self.height)
+        return t.value
+
+    def present_warped_to(self, buffer, warp, tensor):
+        """fr_present_enqueue_warped_device: as present_to(), through `warp`; the tensor holds the output's
+        height * width * 4 bytes."""
+        nbytes = tensor.numel() * tensor.element_size()
+        self._check(_lib.fr_present_enqueue_warped_device(self._ctx, int(buffer), C.byref(warp.c_struct()),
+                                                          self._device_ptr(tensor), nbytes))
 
     def present_times(self, ticket) -> dict:
         """fr_present_times: the pack kernel's and the host copy's time of an acquired ticket, in ms."""
@@ -1384,6 +1410,77 @@ def present_pack(rgba, format=FR_PRESENT_RGBA8) -> np.ndarray:
     rc = lib.fr_present_pack(C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], int(format), C.c_void_p(out.ctypes.data))
     if rc:
         raise FovrtError(rc, "fr_present_pack: bad size or format")
+    return out
+
+
+class PresentWarp:
+    """fr_present_warp: a homography h (9 float32, row-major) from output texel centres to source texel coordinates,
+    and the output size (0, 0: the source's). include/fovrt.h, "Present", has the rule."""
+
+    def __init__(self, h, out_width=0, out_height=0):
+        self.h = np.asarray(h, np.float32).reshape(9).copy()
+        self.out_width, self.out_height = int(out_width), int(out_height)
+
+    def c_struct(self) -> fr_present_warp:
+        w = fr_present_warp()
+        C.memmove(w.h, self.h.ctypes.data, 36)  # the bits as they are: a float() round trip would change no value
+        w.out_width, w.out_height = self.out_width, self.out_height
+        return w
+
+    def shape(self, width, height):
+        """(rows, columns) of the output over a width x height source."""
+        if self.out_width == 0 and self.out_height == 0:
+            return int(height), int(width)
+        return self.out_height, self.out_width
+
+    @staticmethod
+    def identity():
+        return PresentWarp([1, 0, 0, 0, 1, 0, 0, 0, 1])
+
+    @staticmethod
+    def crop(x0, y0, out_width, out_height):
+        """The out_width x out_height texels whose lower left texel is (x0, y0) (rows bottom-up)."""
+        return PresentWarp([1, 0, x0, 0, 1, y0, 0, 0, 1], out_width, out_height)
+
+    @staticmethod
+    def scale(width, height, out_width, out_height):
+        """The whole width x height image as out_width x out_height texels."""
+        return PresentWarp([np.float32(width) / np.float32(out_width), 0, 0,
+                            0, np.float32(height) / np.float32(out_height), 0, 0, 0, 1], out_width, out_height)
+
+    @staticmethod
+    def from_poses(rendered, display, width, height, out_width=None, out_height=None, ndc_depth=1.0):
+        return present_warp_from_poses(rendered, display, width, height, out_width, out_height, ndc_depth)
+
+
+def present_warp_from_poses(rendered, display, width, height, out_width=None, out_height=None, ndc_depth=1.0) -> PresentWarp:
+    """fr_present_warp_from_poses (host only): the late reprojection from the camera a frame was rendered for to the
+    one it is displayed for (each a Camera or an fr_camera_pose), through the points at `ndc_depth` of the display
+    camera; with equal eye positions (a rotation) the depth does not matter."""
+    lib = load_library()
+    r, d = (p._pose() if isinstance(p, Camera) else p for p in (rendered, display))
+    w = fr_present_warp()
+    rc = lib.fr_present_warp_from_poses(C.byref(r), C.byref(d), int(width), int(height),
+                                        int(width if out_width is None else out_width),
+                                        int(height if out_height is None else out_height), C.c_float(ndc_depth), C.byref(w))
+    if rc:
+        raise FovrtError(rc, "fr_present_warp_from_poses: bad size or depth, a singular matrix, or the output's corner "
+                             "is not in front of the rendered camera")
+    return PresentWarp(np.array(w.h[:], np.float32), w.out_width, w.out_height)
+
+
+def present_warp_pack(rgba, warp, format=FR_PRESENT_RGBA8) -> np.ndarray:
+    """fr_present_warp_pack (host only): an (H, W, 4) float32 image through `warp` as (oh, ow, 4) uint8 by the warped
+    present rule, through the function the kernel runs."""
+    lib = load_library()
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("present_warp_pack: an (H, W, 4) float32 image")
+    out = np.empty(warp.shape(a.shape[1], a.shape[0]) + (4,), np.uint8)
+    rc = lib.fr_present_warp_pack(C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], int(format), C.byref(warp.c_struct()),
+                                  C.c_void_p(out.ctypes.data))
+    if rc:
+        raise FovrtError(rc, "fr_present_warp_pack: bad size, format or warp")
     return out
 
 

@@ -993,9 +993,60 @@ int fr_restore(fr_ctx* ctx, const void* host, size_t bytes);
  * 0..8, an unknown format, a wrong bytes, a misaligned or NULL device_dst (FR_E_INVALID); the feature not enabled, or
  * the ring full (FR_E_STATE); either enqueue on a rank of a group or on a sharded context (FR_E_UNSUPPORTED, as with
  * every other enqueued call).
- * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; cropped or variable-rate (foveated)
- * readback; a gaze-contingent blend of Sibson and A-Trous; the G-buffer channels and EXTRA; a group's composite; the
- * ring in a snapshot. */
+ *
+ * Present through a homography: late reprojection ("timewarp"), crop and scale, in the same place and the same order.
+ * fr_present_enqueue_warped and fr_present_enqueue_warped_device are the two enqueue calls above with a projective map
+ * between the image and the texels: the same buffers, resolved at the call; the same waits of the present stream; the
+ * same fence behind the kernel's read; the same ring, tickets, acquire, release, times and fr_present_done. Plain and
+ * warped presents may be mixed freely. The output is ow x oh texels, tight, 1 <= ow <= W and 1 <= oh <= H
+ * (out_width = out_height = 0 means W x H), so a slot's images hold it; only ow * oh * 4 bytes are copied to the host,
+ * and `bytes` of the device form must equal that. The warp is read during the call and travels in the kernel's
+ * arguments: nothing of the caller's is kept.
+ * The rule, with one right answer in bytes. S is the W x H source, row 0 at the bottom; h[0..8] is row-major and takes
+ * the centre of an output texel to a source texel coordinate (texel i covers [i, i + 1), its centre is i + 0.5). For
+ * output column x and output row r, y = r, or oh - 1 - r with FR_PRESENT_TOP_DOWN. All fp32, every operation rounded
+ * on its own, no fma, '/' correctly rounded, subnormal results kept:
+ *   px = (float)x + 0.5f                 py = (float)y + 0.5f
+ *   u  = (h[0]*px + h[1]*py) + h[2]
+ *   v  = (h[3]*px + h[4]*py) + h[5]
+ *   w  = (h[6]*px + h[7]*py) + h[8]
+ *   if !(w > 0)                                  -> border
+ *   iw = 1.0f / w
+ *   fx = u*iw - 0.5f                     fy = v*iw - 0.5f
+ *   if !(fx >= -0.5f && fx < (float)W - 0.5f &&
+ *        fy >= -0.5f && fy < (float)H - 0.5f)    -> border     (false for NaN and +-Inf)
+ *   x0 = floorf(fx)   tx = fx - x0   xa = max((int)x0, 0)   xb = min((int)x0 + 1, W - 1)      (the same for y)
+ *   row(j)   = (tx == 0) ? S[j][xa] : S[j][xa]*(1 - tx) + S[j][xb]*tx        per channel r, g, b
+ *   value    = (ty == 0) ? row(ya) : row(ya)*(1 - ty) + row(yb)*ty
+ *   byte     = the rule above of value;  alpha 255;  a border texel is 0, 0, 0, 255
+ * A tap of weight 0 is not read. So the identity with ow x oh = W x H gives the plain present's bytes for every source
+ * value, NaN and Inf next door included; h = [1 0 dx; 0 1 dy; 0 0 1] with integers dx, dy is an exact crop or shift
+ * with border texels where it leaves the image; and where w <= 0 or the quotient overflows (a display camera turned
+ * past the source's horizon) the texel is border. Within half a texel outside the source the edge texels repeat.
+ * The two maps a caller writes by hand: the crop of ow x oh texels whose lower left texel is (x0, y0),
+ * [1 0 x0; 0 1 y0; 0 0 1], and the scale of the whole image to ow x oh, [W/ow 0 0; 0 H/oh 0; 0 0 1].
+ * fr_present_warp_pack states the rule on the host, without a device, through the function the kernel runs (out:
+ * out_width * out_height * 4 bytes); FR_E_INVALID as fr_present_pack, and for a NULL warp, a non-finite coefficient or
+ * an output size outside those limits.
+ * fr_present_warp_from_poses (host only, f64 throughout, rounded once to fp32) builds the map for a late reprojection:
+ * the output is out_width x out_height texels over the display camera's whole viewport, rows bottom-up; the source is
+ * the width x height image the rendered camera produced; a texel centre maps to where the rendered camera sees the
+ * point that lies on the display camera's ray at NDC depth ndc_depth (fr_camera_matrices' projection: z in [-1, 1],
+ * +1 the far plane). With M = proj * view of fr_camera_matrices, that is S (M_r M_d^-1) restricted to z = ndc_depth
+ * T, with T from output texel coordinates to the display camera's NDC and S from the rendered camera's NDC to source
+ * texel coordinates, scaled so that h[8] = 1. With equal eye positions the map does not depend on ndc_depth (pure
+ * rotation: exact for any scene depth); equal poses give [W/ow 0 0; 0 H/oh 0; 0 0 1] exactly, the identity for
+ * out = width x height. FR_E_INVALID, with *warp untouched: a NULL pointer, a size outside 1..32767, a non-finite
+ * depth, a singular or non-finite matrix, or an h[8] that cannot be normalised: before scaling, h[8] is the rendered
+ * camera's clip w of output corner (0, 0) and must exceed 2^-20 * max(|h[6]| * out_width, |h[7]| * out_height, |h[8]|)
+ * (at or below zero that corner lies on or behind the rendered camera's eye plane, and no positive scale exists).
+ * Refused with nothing enqueued, nothing written and no ticket taken, beside the refusals above with their codes: a
+ * NULL warp, a non-finite coefficient, an output size outside the limits, a wrong bytes, a NULL or misaligned
+ * device_dst (FR_E_INVALID).
+ * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; a gaze-contingent blend of Sibson and
+ * A-Trous; the G-buffer channels and EXTRA; a group's composite; the ring in a snapshot; of the warp: depth-aware
+ * (positional) reprojection from POSITION; a homography latched from device memory at kernel time; edge clamping
+ * beyond half a texel and filters other than bilinear; lens distortion; outputs larger than the screen; groups. */
 #define FR_PRESENT_RGBA8    0
 #define FR_PRESENT_BGRA8    1
 #define FR_PRESENT_TOP_DOWN 0x100   /* or-ed into the format */
@@ -1008,6 +1059,12 @@ int fr_present_release(fr_ctx* ctx, uint64_t ticket);
 int fr_present_times(fr_ctx* ctx, uint64_t ticket, float* pack_ms, float* copy_ms);
 int fr_present_enqueue_device(fr_ctx* ctx, int buffer_id, void* device_dst, size_t bytes);
 int fr_present_done(fr_ctx* ctx, void* stream);
+typedef struct fr_present_warp { float h[9]; int out_width, out_height; } fr_present_warp;   /* 0, 0 = W, H */
+int fr_present_warp_pack(const float* rgba, int width, int height, int format, const fr_present_warp* warp, uint8_t* out);
+int fr_present_warp_from_poses(const fr_camera_pose* rendered, const fr_camera_pose* display, int width, int height,
+                               int out_width, int out_height, float ndc_depth, fr_present_warp* warp);
+int fr_present_enqueue_warped(fr_ctx* ctx, int buffer_id, const fr_present_warp* warp, uint64_t* ticket);
+int fr_present_enqueue_warped_device(fr_ctx* ctx, int buffer_id, const fr_present_warp* warp, void* device_dst, size_t bytes);
 
 int fr_get_stats(fr_ctx* ctx, fr_stats* stats);
 int fr_reset_stats(fr_ctx* ctx);

@@ -45,6 +45,46 @@ inline std::vector<uint8_t> present_pack(const std::vector<float>& rgba, int wid
   return out;
 }
 
+// fr_present_warp with its constructors: the homography of a warped present (the rule is in fovrt.h under "Present")
+struct PresentWarp : fr_present_warp {
+  PresentWarp() : fr_present_warp{{1, 0, 0, 0, 1, 0, 0, 0, 1}, 0, 0} {}
+  static PresentWarp identity() { return PresentWarp(); }
+  // the out_width x out_height texels whose lower left texel is (x0, y0), rows bottom-up
+  static PresentWarp crop(int x0, int y0, int out_width, int out_height) {
+    PresentWarp w;
+    w.h[2] = (float)x0; w.h[5] = (float)y0;
+    w.out_width = out_width; w.out_height = out_height;
+    return w;
+  }
+  // the whole width x height image as out_width x out_height texels
+  static PresentWarp scale(int width, int height, int out_width, int out_height) {
+    PresentWarp w;
+    w.h[0] = (float)width / (float)out_width; w.h[4] = (float)height / (float)out_height;
+    w.out_width = out_width; w.out_height = out_height;
+    return w;
+  }
+  // fr_present_warp_from_poses: the late reprojection from the rendered camera to the display camera
+  static PresentWarp from_poses(const fr_camera_pose& rendered, const fr_camera_pose& display, int width, int height,
+                                int out_width, int out_height, float ndc_depth = 1.0f) {
+    PresentWarp w;
+    if (int rc = fr_present_warp_from_poses(&rendered, &display, width, height, out_width, out_height, ndc_depth, &w))
+      throw Error(rc, "present_warp_from_poses: bad size or depth, a singular matrix, or a corner behind the rendered camera");
+    return w;
+  }
+};
+
+// fr_present_warp_pack: the warped present rule on the host; the result holds out_width * out_height * 4 bytes
+inline std::vector<uint8_t> present_warp_pack(const std::vector<float>& rgba, int width, int height, const fr_present_warp& warp,
+                                              int format = FR_PRESENT_RGBA8) {
+  if (width < 1 || height < 1 || rgba.size() != (size_t)width * height * 4) throw Error(FR_E_INVALID, "present_warp_pack: size");
+  const bool whole = warp.out_width == 0 && warp.out_height == 0;
+  const int ow = whole ? width : warp.out_width, oh = whole ? height : warp.out_height;
+  if (ow < 1 || oh < 1 || ow > width || oh > height) throw Error(FR_E_INVALID, "present_warp_pack: output size");
+  std::vector<uint8_t> out((size_t)ow * oh * 4);
+  if (int rc = fr_present_warp_pack(rgba.data(), width, height, format, &warp, out.data())) throw Error(rc, "present_warp_pack: bad format or warp");
+  return out;
+}
+
 // A GL texture name of the reference = a buffer id of the context here.
 struct Texture {
   int id = -1;
@@ -408,6 +448,16 @@ class PathTracer {
     check(fr_present_enqueue_device(ctx(), buffer, device_dst, bytes), ctx_, "present_to");
   }
   void present_done(void* stream = nullptr) { check(fr_present_done(ctx(), stream), ctx_, "present_done"); }
+  // The same through a homography (fr_present_enqueue_warped, fr_present_enqueue_warped_device): late reprojection,
+  // crop, scale. The ticket's image, and `bytes` of the device form, are the warp's out_width * out_height * 4 bytes.
+  uint64_t present_warped(int buffer, const fr_present_warp& warp) {
+    uint64_t t = 0;
+    check(fr_present_enqueue_warped(ctx(), buffer, &warp, &t), ctx_, "present_warped");
+    return t;
+  }
+  void present_warped_to(int buffer, const fr_present_warp& warp, void* device_dst, size_t bytes) {
+    check(fr_present_enqueue_warped_device(ctx(), buffer, &warp, device_dst, bytes), ctx_, "present_warped_to");
+  }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
   }
