@@ -5,7 +5,10 @@
 // fr_present_enqueue_warped and fr_present_enqueue_warped_device are the same two calls with k_present_warp in the
 // pack's place (a homography between the image and the texels: late reprojection, crop, scale), and
 // fr_present_warp_pack is that rule on the host; the ordering below is theirs unchanged. A warped slot carries
-// ow * oh * 4 bytes to the host, no more.
+// ow * oh * 4 bytes to the host, no more. fr_present_enqueue_blended and fr_present_enqueue_blended_device are the same
+// again over a virtual image that mixes two of the images around a gaze point (k_present_blend, k_present_blend_warp;
+// fr_present_blend_pack on the host): the present stream waits as for one image, and the fence of each source is
+// recorded behind the kernel.
 //
 // Ordering. A present reads one of the images a frame's last stages write (SIBSON on sibson_stream, PULLPUSH and the
 // A-Trous pair on atrous_stream, the slot's SHADING on the context stream; stage calls and fr_write_buffer write all
@@ -63,6 +66,29 @@ bool warp_ok(const fr_present_warp* warp, int W, int H, int* ow, int* oh) {
   return *ow >= 1 && *ow <= W && *oh >= 1 && *oh <= H;
 }
 
+// A blend as the host rule and both blended enqueues take it: finite gaze and radii, 0 <= inner <= outer, and a finite
+// outer * outer. *b: the blend as the kernels take it, the squared radii one fp32 product each.
+bool blend_ok(const fr_present_blend* blend, PresentBlend* b) {
+  if (!blend) return false;
+  const float r0 = blend->inner_radius_px, r1 = blend->outer_radius_px;
+  if (!std::isfinite(blend->gaze[0]) || !std::isfinite(blend->gaze[1]) || !std::isfinite(r0) || !std::isfinite(r1)) return false;
+  if (!(r0 >= 0.0f && r0 <= r1)) return false;
+  const float r0sq = r0 * r0, r1sq = r1 * r1;
+  if (!std::isfinite(r1sq)) return false;
+  *b = PresentBlend{blend->gaze[0], blend->gaze[1], r0sq, r1sq};
+  return true;
+}
+const char* const kBadBlend =
+    ": the blend is NULL, has a non-finite gaze or radius, a negative radius, inner > outer, or an outer radius whose "
+    "square is not finite";
+
+// What a present packs: one image, or (blended) the virtual image that mixes `phys` (inner) and `outer` by `blend`.
+struct Source {
+  int phys = -1, outer = -1;
+  bool blended = false;
+  PresentBlend blend{};
+};
+
 // The stream, the events and the fences, once; then the images of slots made .. slots - 1. All or nothing.
 bool make_ring(fr_ctx* c, int slots) {
   fr_ctx::Present& P = c->present;
@@ -85,9 +111,12 @@ bool make_ring(fr_ctx* c, int slots) {
   return ok;
 }
 
-// What both enqueue forms refuse before anything is enqueued; *phys: the image to pack.
-int check_enqueue(fr_ctx* c, const std::string& name, int id, int* phys) {
-  if ((*phys = presentable(c, id)) < 0)
+// What both enqueue forms refuse before anything is enqueued. src: the image to pack, resolved here from buffer_id, or
+// (blend given: blended, with its parameters checked by the caller) the two images from the blend's ids.
+int check_enqueue(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, Source* src) {
+  src->phys = presentable(c, blend ? blend->inner_buffer : buffer_id);
+  src->outer = blend ? presentable(c, blend->outer_buffer) : src->phys;
+  if (src->phys < 0 || src->outer < 0)
     return fail(c, FR_E_INVALID, name + ": the buffer is not FR_BUF_SHADING, FR_BUF_SIBSON, FR_BUF_PULLPUSH or FR_BUF_ATROUS");
   if (c->group_refs > 0 || c->U.shard_count > 1)
     return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded");
@@ -96,41 +125,49 @@ int check_enqueue(fr_ctx* c, const std::string& name, int id, int* phys) {
 }
 
 // The present stream behind what wrote the image (the head of this file), then the pack into dst, then the fence
-// its next writer waits for. begin / packed: a slot's timing events, or NULL. warp: NULL for the plain pack, else the
-// checked homography with its output size ow x oh (k_present_warp takes them by value: nothing is read after the call).
-int enqueue_pack(fr_ctx* c, int phys, const fr_present_warp* warp, int ow, int oh, void* dst, hipEvent_t begin,
+// its next writer waits for: of each source, when the present blends two. begin / packed: a slot's timing events, or
+// NULL. warp: NULL for the plain pack, else the checked homography with its output size ow x oh (the kernels take warp
+// and blend by value: nothing is read after the call).
+int enqueue_pack(fr_ctx* c, const Source& src, const fr_present_warp* warp, int ow, int oh, void* dst, hipEvent_t begin,
                  hipEvent_t packed) {
   fr_ctx::Present& P = c->present;
   HIP_TRY(c, hipEventRecord(P.ev_fork, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(P.stream, P.ev_fork, 0));
   for (const Fence& f : c->recon_done) HIP_TRY(c, f.peek(P.stream));
   if (begin) HIP_TRY(c, hipEventRecord(begin, P.stream));
-  if (warp)
-    launch_present_warp(c->img[phys], c->W, c->H, P.format, warp->h, ow, oh, dst, P.stream);
+  if (src.blended)
+    launch_present_blend(c->img[src.phys], c->img[src.outer], c->W, c->H, P.format, src.blend, warp ? warp->h : nullptr, ow, oh,
+                         dst, P.stream);
+  else if (warp)
+    launch_present_warp(c->img[src.phys], c->W, c->H, P.format, warp->h, ow, oh, dst, P.stream);
   else
-    launch_present_pack(c->img[phys], c->W, c->H, P.format, dst, P.stream);
+    launch_present_pack(c->img[src.phys], c->W, c->H, P.format, dst, P.stream);
   if (int rc = check_launch(c)) return rc;
   if (packed) HIP_TRY(c, hipEventRecord(packed, P.stream));
-  Fence& read = phys == P_shd(c) ? c->present_read_shd[c->slot] : c->present_read;
-  HIP_TRY(c, read.record(P.stream));
+  const int shd = P_shd(c);
+  if (src.phys == shd || src.outer == shd) HIP_TRY(c, c->present_read_shd[c->slot].record(P.stream));
+  if (src.phys != shd || src.outer != shd) HIP_TRY(c, c->present_read.record(P.stream));
   return FR_OK;
 }
 
-// fr_present_enqueue (warp NULL) and fr_present_enqueue_warped: into the next free slot and on to its pinned image.
-int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_warp* warp, bool warped, uint64_t* ticket) {
+// fr_present_enqueue (warp NULL), fr_present_enqueue_warped and (blended: the sources are the blend's, buffer_id is not
+// used) fr_present_enqueue_blended: into the next free slot and on to its pinned image.
+int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
+                 const fr_present_warp* warp, bool warped, uint64_t* ticket) {
   if (!c || !ticket) return FR_E_INVALID;
   int ow = c->W, oh = c->H;
   if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
     return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
-  int phys;
-  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  Source src;
+  if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
+  if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
   fr_ctx::Present& P = c->present;
   uint64_t t = 0;
   const int s = P.ring.enqueue(&t);
   if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
   hipSetDevice(c->cfg.device);
   // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
-  int rc = enqueue_pack(c, phys, warped ? warp : nullptr, ow, oh, P.stage[s], P.ev[s].begin, P.ev[s].packed);
+  int rc = enqueue_pack(c, src, warped ? warp : nullptr, ow, oh, P.stage[s], P.ev[s].begin, P.ev[s].packed);
   if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], (size_t)ow * oh * 4, hipMemcpyDeviceToHost, P.stream) != hipSuccess)
     rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
   if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
@@ -142,9 +179,10 @@ int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_pre
   return FR_OK;
 }
 
-// fr_present_enqueue_device (warp NULL) and fr_present_enqueue_warped_device: straight into the caller's memory.
-int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_warp* warp, bool warped, void* device_dst,
-                   size_t bytes) {
+// fr_present_enqueue_device (warp NULL), fr_present_enqueue_warped_device and (blended) fr_present_enqueue_blended_device:
+// straight into the caller's memory.
+int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
+                   const fr_present_warp* warp, bool warped, void* device_dst, size_t bytes) {
   if (!c) return FR_E_INVALID;
   int ow = c->W, oh = c->H;
   if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
@@ -152,10 +190,11 @@ int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_p
   if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
     return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
   if (bytes != (size_t)ow * oh * 4) return fail(c, FR_E_INVALID, name + ": bytes != the output's width * height * 4");
-  int phys;
-  if (int rc = check_enqueue(c, name, buffer_id, &phys)) return rc;
+  Source src;
+  if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
+  if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
   hipSetDevice(c->cfg.device);
-  if (int rc = enqueue_pack(c, phys, warped ? warp : nullptr, ow, oh, device_dst, nullptr, nullptr)) return rc;
+  if (int rc = enqueue_pack(c, src, warped ? warp : nullptr, ow, oh, device_dst, nullptr, nullptr)) return rc;
   HIP_TRY(c, c->present_dev.record(c->present.stream));
   return FR_OK;
 }
@@ -250,11 +289,11 @@ int fr_present_enable(fr_ctx* c, int slots, int format) {
 }
 
 int fr_present_enqueue(fr_ctx* c, int buffer_id, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue", buffer_id, nullptr, false, ticket);
+  return enqueue_host(c, "fr_present_enqueue", buffer_id, nullptr, false, nullptr, false, ticket);
 }
 
 int fr_present_enqueue_warped(fr_ctx* c, int buffer_id, const fr_present_warp* warp, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue_warped", buffer_id, warp, true, ticket);
+  return enqueue_host(c, "fr_present_enqueue_warped", buffer_id, nullptr, false, warp, true, ticket);
 }
 
 int fr_present_acquire(fr_ctx* c, uint64_t ticket, int wait, const void** host) {
@@ -302,11 +341,59 @@ int fr_present_times(fr_ctx* c, uint64_t ticket, float* pack_ms, float* copy_ms)
 }
 
 int fr_present_enqueue_device(fr_ctx* c, int buffer_id, void* device_dst, size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_device", buffer_id, nullptr, false, device_dst, bytes);
+  return enqueue_device(c, "fr_present_enqueue_device", buffer_id, nullptr, false, nullptr, false, device_dst, bytes);
 }
 
 int fr_present_enqueue_warped_device(fr_ctx* c, int buffer_id, const fr_present_warp* warp, void* device_dst, size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_warped_device", buffer_id, warp, true, device_dst, bytes);
+  return enqueue_device(c, "fr_present_enqueue_warped_device", buffer_id, nullptr, false, warp, true, device_dst, bytes);
+}
+
+int fr_present_blend_default(fr_ctx* c, fr_present_blend* blend) {
+  if (!c || !blend) return FR_E_INVALID;
+  blend->inner_buffer = FR_BUF_SIBSON;
+  blend->outer_buffer = FR_BUF_ATROUS;
+  blend->gaze[0] = c->U.gaze.x;
+  blend->gaze[1] = c->U.gaze.y;
+  blend->inner_radius_px = c->fov.radius_px;
+  blend->outer_radius_px = 2.0f * blend->inner_radius_px;
+  return FR_OK;
+}
+
+int fr_present_blend_pack(const float* inner, const float* outer, int width, int height, int format,
+                          const fr_present_blend* blend, const fr_present_warp* warp, uint8_t* out) {
+  if (!inner || !outer || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format))
+    return FR_E_INVALID;
+  int ow = width, oh = height;
+  if (warp && !warp_ok(warp, width, height, &ow, &oh)) return FR_E_INVALID;
+  PresentBlend b;
+  if (!blend_ok(blend, &b)) return FR_E_INVALID;
+  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
+  const auto texel = [width](const float* img) {
+    return [img, width](int i, int row) {
+      const float* t = img + ((size_t)row * width + i) * 4;
+      return mk4(t[0], t[1], t[2], t[3]);
+    };
+  };
+  const auto fi = texel(inner), fo = texel(outer);
+  const auto fetch = [&fi, &fo, &b](int i, int row) { return present_blend_fetch(fi, fo, i, row, b); };
+  for (int r = 0; r < oh; r++) {
+    const int y = top_down ? oh - 1 - r : r;
+    uint8_t* o = out + (size_t)r * ow * 4;
+    for (int x = 0; x < ow; x++) {
+      const uint32_t w = warp ? present_warp_texel(fetch, width, height, warp->h, x, y, bgra) : present_texel(fetch(x, y), bgra);
+      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
+    }
+  }
+  return FR_OK;
+}
+
+int fr_present_enqueue_blended(fr_ctx* c, const fr_present_blend* blend, const fr_present_warp* warp, uint64_t* ticket) {
+  return enqueue_host(c, "fr_present_enqueue_blended", 0, blend, true, warp, warp != nullptr, ticket);
+}
+
+int fr_present_enqueue_blended_device(fr_ctx* c, const fr_present_blend* blend, const fr_present_warp* warp, void* device_dst,
+                                      size_t bytes) {
+  return enqueue_device(c, "fr_present_enqueue_blended_device", 0, blend, true, warp, warp != nullptr, device_dst, bytes);
 }
 
 int fr_present_done(fr_ctx* c, void* stream) {

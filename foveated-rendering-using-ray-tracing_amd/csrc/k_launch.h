@@ -97,6 +97,10 @@ void launch_present_pack(const f4* src, int W, int H, int format, void* out, hip
 // centres, copied into the kernel's arguments by the call; 1 <= ow <= W, 1 <= oh <= H; out: ow * oh words
 void launch_present_warp(const f4* src, int W, int H, int format, const float* h, int ow, int oh, void* out,
                          hipStream_t stream);
+// Either of the two over the virtual image present_blend_fetch (fr_math.h) makes of two W x H sources, which may be
+// one image; the blend is copied into the kernel's arguments. h NULL: the plain form (ow x oh = W x H)
+void launch_present_blend(const f4* inner, const f4* outer, int W, int H, int format, const PresentBlend& blend,
+                          const float* h, int ow, int oh, void* out, hipStream_t stream);
 
 // k_jfa.hip, k_sibson.hip
 // A context's JumpFlooding state: G, H the passes' ping-pong, F the final state (retained while the seed set stays),

@@ -113,4 +113,113 @@ void launch_present_warp(const f4* src, int W, int H, int format, const float* h
     hipLaunchKernelGGL(k_present_warp<false>, grid, dim3(PRESENT_BX, PRESENT_BY), 0, stream, src, a, static_cast<uint32_t*>(out));
 }
 
+// k_present_blend: k_present_pack's shape (lanes, rows, stores, the tail lane) over the virtual image of
+// present_blend_fetch (fr_math.h), the function fr_present_blend_pack runs on the host: each texel is `inner` inside
+// the gaze's disc, `outer` beyond the ring, their smoothstep mix between. The blend travels by value in the kernel
+// arguments. A texel reads `inner` only where s < 1 and `outer` only where s > 0, behind branches on s: a wave that
+// lies wholly inside the disc or wholly beyond the ring (one row of 256 texels: all of them outside a ring zone)
+// skips the other source's loads and moves the pack's 20 B per texel, and the division of the ramp is behind the
+// ring's branch. A lane forms its four weights first and issues its loads together. No LDS, no atomics, no scratch.
+template <bool ALIGNED>
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_blend(const f4* __restrict__ inner,
+                                                                          const f4* __restrict__ outer, int W, int H,
+                                                                          int lanes, bool bgra, bool top_down,
+                                                                          const PresentBlend blend,
+                                                                          uint32_t* __restrict__ out) {
+  const int j = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int r = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
+  if (j >= lanes || r >= H) return;
+  const int x = 4 * j;
+  const int sr = top_down ? H - 1 - r : r;
+  // (called with 0 <= i < W and row = sr < H only)
+  const auto fi = [inner, W](int i, int row) { return inner[(size_t)row * W + i]; };
+  const auto fo = [outer, W](int i, int row) { return outer[(size_t)row * W + i]; };
+  uint32_t* o = out + (size_t)r * W + x;
+  if (x + 4 <= W) {
+    // present_blend_fetch's steps, each for the four texels: the weights, then every load, then the mixes
+    const f4* in = inner + (size_t)sr * W + x;
+    const f4* ou = outer + (size_t)sr * W + x;
+    const float s0 = present_blend_weight(x, sr, blend), s1 = present_blend_weight(x + 1, sr, blend),
+                s2 = present_blend_weight(x + 2, sr, blend), s3 = present_blend_weight(x + 3, sr, blend);
+    const f4 z = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    f4 a0 = z, a1 = z, a2 = z, a3 = z, b0 = z, b1 = z, b2 = z, b3 = z;
+    if (s0 < 1.0f) a0 = in[0];
+    if (s1 < 1.0f) a1 = in[1];
+    if (s2 < 1.0f) a2 = in[2];
+    if (s3 < 1.0f) a3 = in[3];
+    if (s0 > 0.0f) b0 = ou[0];
+    if (s1 > 0.0f) b1 = ou[1];
+    if (s2 > 0.0f) b2 = ou[2];
+    if (s3 > 0.0f) b3 = ou[3];
+    const uint4 q = make_uint4(present_texel(present_blend_mix(a0, b0, s0), bgra), present_texel(present_blend_mix(a1, b1, s1), bgra),
+                               present_texel(present_blend_mix(a2, b2, s2), bgra), present_texel(present_blend_mix(a3, b3, s3), bgra));
+    if (ALIGNED) {
+      *reinterpret_cast<uint4*>(o) = q;
+    } else {
+      o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    }
+  } else {
+    for (int k = 0; x + k < W; k++) o[k] = present_texel(present_blend_fetch(fi, fo, x + k, sr, blend), bgra);
+  }
+}
+
+// k_present_blend_warp: k_present_warp whose fetch is the blended one, so the blend is evaluated at each source tap,
+// before the bilinear filter.
+template <bool ALIGNED>
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_blend_warp(const f4* __restrict__ inner,
+                                                                               const f4* __restrict__ outer,
+                                                                               const WarpArgs a, const PresentBlend blend,
+                                                                               uint32_t* __restrict__ out) {
+  const int j = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int r = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
+  if (j >= a.lanes || r >= a.oh) return;
+  const int x = 4 * j;
+  const int y = a.top_down ? a.oh - 1 - r : r;
+  const int W = a.W;
+  // (present_warp_texel calls it with 0 <= i < W and 0 <= row < H only)
+  const auto fi = [inner, W](int i, int row) { return inner[(size_t)row * W + i]; };
+  const auto fo = [outer, W](int i, int row) { return outer[(size_t)row * W + i]; };
+  const auto fetch = [&fi, &fo, &blend](int i, int row) { return present_blend_fetch(fi, fo, i, row, blend); };
+  uint32_t* o = out + (size_t)r * a.ow + x;
+  if (x + 4 <= a.ow) {
+    const uint4 q = make_uint4(present_warp_texel(fetch, W, a.H, a.h, x, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 1, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 2, y, a.bgra),
+                               present_warp_texel(fetch, W, a.H, a.h, x + 3, y, a.bgra));
+    if (ALIGNED) {
+      *reinterpret_cast<uint4*>(o) = q;
+    } else {
+      o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    }
+  } else {
+    for (int k = 0; x + k < a.ow; k++) o[k] = present_warp_texel(fetch, W, a.H, a.h, x + k, y, a.bgra);
+  }
+}
+
+// As launch_present_pack (h NULL) or launch_present_warp over the blend of two W x H sources; inner and outer may be
+// the same image.
+void launch_present_blend(const f4* inner, const f4* outer, int W, int H, int format, const PresentBlend& blend,
+                          const float* h, int ow, int oh, void* out, hipStream_t stream) {
+  const bool bgra = (format & 0xFF) == 1, top_down = (format & 0x100) != 0;
+  const int lanes = (ow + 3) / 4;
+  const dim3 grid((unsigned)((lanes + PRESENT_BX - 1) / PRESENT_BX), (unsigned)((oh + PRESENT_BY - 1) / PRESENT_BY));
+  const dim3 block(PRESENT_BX, PRESENT_BY);
+  uint32_t* o = static_cast<uint32_t*>(out);
+  if (!h) {  // ow x oh is W x H
+    if ((W & 3) == 0)
+      hipLaunchKernelGGL(k_present_blend<true>, grid, block, 0, stream, inner, outer, W, H, lanes, bgra, top_down, blend, o);
+    else
+      hipLaunchKernelGGL(k_present_blend<false>, grid, block, 0, stream, inner, outer, W, H, lanes, bgra, top_down, blend, o);
+    return;
+  }
+  WarpArgs a;
+  for (int k = 0; k < 9; k++) a.h[k] = h[k];
+  a.W = W; a.H = H; a.ow = ow; a.oh = oh; a.lanes = lanes;
+  a.bgra = bgra; a.top_down = top_down;
+  if ((ow & 3) == 0)
+    hipLaunchKernelGGL(k_present_blend_warp<true>, grid, block, 0, stream, inner, outer, a, blend, o);
+  else
+    hipLaunchKernelGGL(k_present_blend_warp<false>, grid, block, 0, stream, inner, outer, a, blend, o);
+}
+
 }  // namespace fr

@@ -124,6 +124,11 @@ class fr_present_warp(C.Structure):
     _fields_ = [("h", C.c_float * 9), ("out_width", C.c_int), ("out_height", C.c_int)]
 
 
+class fr_present_blend(C.Structure):
+    _fields_ = [("inner_buffer", C.c_int), ("outer_buffer", C.c_int), ("gaze", C.c_float * 2),
+                ("inner_radius_px", C.c_float), ("outer_radius_px", C.c_float)]
+
+
 class fr_ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
 
@@ -276,6 +281,13 @@ _SIGS = {
                                    C.c_int, C.c_float, C.POINTER(fr_present_warp)],
     "fr_present_enqueue_warped": [C.c_void_p, C.c_int, C.POINTER(fr_present_warp), C.POINTER(C.c_uint64)],
     "fr_present_enqueue_warped_device": [C.c_void_p, C.c_int, C.POINTER(fr_present_warp), C.c_void_p, C.c_size_t],
+    "fr_present_blend_default": [C.c_void_p, C.POINTER(fr_present_blend)],
+    "fr_present_blend_pack": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fr_present_blend),
+                              C.POINTER(fr_present_warp), C.c_void_p],
+    "fr_present_enqueue_blended": [C.c_void_p, C.POINTER(fr_present_blend), C.POINTER(fr_present_warp),
+                                   C.POINTER(C.c_uint64)],
+    "fr_present_enqueue_blended_device": [C.c_void_p, C.POINTER(fr_present_blend), C.POINTER(fr_present_warp),
+                                          C.c_void_p, C.c_size_t],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "fr_recompute_normals": [C.c_void_p, C.POINTER(C.c_float)],
     "fr_normal_groups": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int)],
@@ -1112,6 +1124,31 @@ class PathTracer:
         self._check(_lib.fr_present_enqueue_warped_device(self._ctx, int(buffer), C.byref(warp.c_struct()),
                                                           self._device_ptr(tensor), nbytes))
 
+    def present_blend_default(self) -> "PresentBlend":
+        """fr_present_blend_default: SIBSON inside, ATROUS outside, around the gaze the next launch uses, from the
+        foveation radius to twice that. Host state only."""
+        b = fr_present_blend()
+        self._check(_lib.fr_present_blend_default(self._ctx, C.byref(b)))
+        return PresentBlend.from_c(b)
+
+    def present_blended(self, blend, warp=None) -> int:
+        """fr_present_enqueue_blended: as present(), of the virtual image that is blend.inner_buffer around the gaze,
+        blend.outer_buffer in the periphery and their smoothstep mix between the radii (a PresentBlend); through
+        `warp` (a PresentWarp) when one is given. Returns the ticket."""
+        t = C.c_uint64()
+        self._check(_lib.fr_present_enqueue_blended(self._ctx, C.byref(blend.c_struct()),
+                                                    None if warp is None else C.byref(warp.c_struct()), C.byref(t)))
+        if warp is not None:
+            self.__dict__.setdefault("_warped_shapes", {})[t.value] = warp.shape(self.width, self.height)
+        return t.value
+
+    def present_blended_to(self, blend, tensor, warp=None):
+        """fr_present_enqueue_blended_device: as present_to() / present_warped_to(), of the blended image."""
+        nbytes = tensor.numel() * tensor.element_size()
+        self._check(_lib.fr_present_enqueue_blended_device(self._ctx, C.byref(blend.c_struct()),
+                                                           None if warp is None else C.byref(warp.c_struct()),
+                                                           self._device_ptr(tensor), nbytes))
+
     def present_times(self, ticket) -> dict:
         """fr_present_times: the pack kernel's and the host copy's time of an acquired ticket, in ms."""
         a, b = C.c_float(), C.c_float()
@@ -1481,6 +1518,46 @@ def present_warp_pack(rgba, warp, format=FR_PRESENT_RGBA8) -> np.ndarray:
                                   C.c_void_p(out.ctypes.data))
     if rc:
         raise FovrtError(rc, "fr_present_warp_pack: bad size, format or warp")
+    return out
+
+
+class PresentBlend:
+    """fr_present_blend: two presentable buffers, a gaze point (texels, row 0 at the bottom) and the two radii between
+    which the image goes from `inner_buffer` to `outer_buffer` by a smoothstep of the squared distance. The gaze and
+    the radii are kept as float32. include/fovrt.h, "Present", has the rule."""
+
+    def __init__(self, gaze, inner_radius_px, outer_radius_px, inner_buffer=TextureName.SIBSON,
+                 outer_buffer=TextureName.ATROUS):
+        self.inner_buffer, self.outer_buffer = int(inner_buffer), int(outer_buffer)
+        self.gaze = np.asarray(gaze, np.float32).reshape(2).copy()
+        self.inner_radius_px, self.outer_radius_px = np.float32(inner_radius_px), np.float32(outer_radius_px)
+
+    def c_struct(self) -> fr_present_blend:
+        b = fr_present_blend()
+        b.inner_buffer, b.outer_buffer = self.inner_buffer, self.outer_buffer
+        b.gaze[0], b.gaze[1] = float(self.gaze[0]), float(self.gaze[1])
+        b.inner_radius_px, b.outer_radius_px = float(self.inner_radius_px), float(self.outer_radius_px)
+        return b
+
+    @staticmethod
+    def from_c(b) -> "PresentBlend":
+        return PresentBlend((b.gaze[0], b.gaze[1]), b.inner_radius_px, b.outer_radius_px, b.inner_buffer, b.outer_buffer)
+
+
+def present_blend_pack(inner, outer, blend, warp=None, format=FR_PRESENT_RGBA8) -> np.ndarray:
+    """fr_present_blend_pack (host only): two (H, W, 4) float32 images blended by `blend` (a PresentBlend; its buffer
+    ids are not used) as (H, W, 4) uint8, or through `warp` as (oh, ow, 4), through the functions the kernels run."""
+    lib = load_library()
+    a, b = (np.ascontiguousarray(x, dtype=np.float32) for x in (inner, outer))
+    if a.ndim != 3 or a.shape[2] != 4 or b.shape != a.shape:
+        raise ValueError("present_blend_pack: two (H, W, 4) float32 images of one size")
+    shape = (a.shape[0], a.shape[1]) if warp is None else warp.shape(a.shape[1], a.shape[0])
+    out = np.empty(shape + (4,), np.uint8)
+    rc = lib.fr_present_blend_pack(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), a.shape[1], a.shape[0], int(format),
+                                   C.byref(blend.c_struct()), None if warp is None else C.byref(warp.c_struct()),
+                                   C.c_void_p(out.ctypes.data))
+    if rc:
+        raise FovrtError(rc, "fr_present_blend_pack: bad size, format, blend or warp")
     return out
 
 

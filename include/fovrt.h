@@ -1043,10 +1043,54 @@ int fr_restore(fr_ctx* ctx, const void* host, size_t bytes);
  * Refused with nothing enqueued, nothing written and no ticket taken, beside the refusals above with their codes: a
  * NULL warp, a non-finite coefficient, an output size outside the limits, a wrong bytes, a NULL or misaligned
  * device_dst (FR_E_INVALID).
- * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; a gaze-contingent blend of Sibson and
- * A-Trous; the G-buffer channels and EXTRA; a group's composite; the ring in a snapshot; of the warp: depth-aware
- * (positional) reprojection from POSITION; a homography latched from device memory at kernel time; edge clamping
- * beyond half a texel and filters other than bilinear; lens distortion; outputs larger than the screen; groups. */
+ *
+ * Blended present: one image that is one reconstruction where the user looks and another in the periphery (the
+ * reference draws SIBSON and ATROUS side by side, FR/main.cpp:26-113; a foveated display wants the sharp one at the
+ * gaze, the denoised one around it, and no visible seam). fr_present_enqueue_blended and
+ * fr_present_enqueue_blended_device are the enqueue calls above whose source is a virtual image: each of its texels
+ * is a mix of two presentable buffers, weighted by the texel's squared distance from a gaze point. Everything after
+ * that texel is what is described above: the 8-bit rule, formats and row orders, the ring, tickets, acquire, release,
+ * times and fr_present_done; with a warp (NULL: none, the output is W x H) the virtual image is the S of the warped
+ * rule, so the blend is evaluated at each source tap, before the bilinear filter. Plain, warped and blended presents
+ * may be mixed freely.
+ * The rule, with one right answer in bytes. fp32, every operation rounded on its own, no fma, '/' correctly rounded,
+ * subnormal results kept. gaze is in fr_camera.gaze's coordinates (texels, row 0 at the bottom) and may lie off
+ * screen; r0sq = inner_radius_px * inner_radius_px and r1sq = outer_radius_px * outer_radius_px, one fp32 product
+ * each, formed on the host. For source texel (i, j):
+ *   dx = (float)i - gaze[0]      dy = (float)j - gaze[1]      d2 = dx*dx + dy*dy
+ *   d2 <= r0sq     -> s = 0
+ *   !(d2 < r1sq)   -> s = 1      (d2 >= r1sq, +Inf included; and a d2 that is not a number, which fails both tests)
+ *   otherwise         t = (d2 - r0sq) / (r1sq - r0sq)     a = 2.0f*t     b = 3.0f - a     c = t*t     s = c*b
+ *   s == 0 -> texel = inner[j][i]          outer is not read
+ *   s == 1 -> texel = outer[j][i]          inner is not read
+ *   else      texel.c = inner.c*(1.0f - s) + outer.c*s          per channel r, g, b: two products, one sum
+ * d2 is FR_MASK_ECCENTRIC's, so with inner_radius_px = fr_foveation.radius_px the disc that shows `inner` alone is the
+ * disc that mask samples fully. s is the smoothstep of t and never exceeds 1. The select is on s itself, not on the
+ * zone: inside the ramp s is exactly 0 where t is tiny (t*t underflows) and exactly 1 where t is within about 2^-13
+ * of 1, and there too the source of weight zero is not read, so a NaN in it does not reach the texel. With a finite
+ * gaze d2 is never NaN (it is +Inf where dx*dx overflows: s = 1); the rule gives a NaN d2 s = 1 all the same.
+ * inner_radius_px == outer_radius_px is a hard edge at d2 <= r0sq. inner_buffer == outer_buffer is allowed.
+ * fr_present_blend_default (host state only, waits for nothing) fills: inner_buffer = FR_BUF_SIBSON, outer_buffer =
+ * FR_BUF_ATROUS, gaze = the gaze the kernels use from the next launch on (fr_set_camera, fr_set_gaze), inner_radius_px
+ * = the radius_px fr_get_foveation returns, outer_radius_px = 2.0f * inner_radius_px (one fp32 product).
+ * fr_present_blend_pack states the rule on the host, without a device, through the functions the kernels run (inner,
+ * outer: width * height * 4 floats each; warp NULL: out holds width * height * 4 bytes, else out_width * out_height *
+ * 4); it ignores the two buffer ids. FR_E_INVALID as fr_present_warp_pack (a NULL warp excepted) and as below.
+ * The two enqueues resolve both buffers at the call, read the blend and the warp during the call (they travel in the
+ * kernel's arguments: nothing of the caller's is kept), wait for nothing on the host and allocate nothing. The present
+ * stream waits as for one image; behind the kernel the fence of each source is recorded, so the next writer of either
+ * image waits for this read.
+ * Refused with nothing enqueued, nothing written and no ticket taken: everything the enqueues above refuse, with the
+ * same codes (a warp is checked only when one is given); a NULL blend, an inner_buffer or outer_buffer that is not
+ * presentable, a non-finite gaze or radius, a negative radius, inner_radius_px > outer_radius_px, an outer_radius_px
+ * whose fp32 square is not finite (FR_E_INVALID).
+ *
+ * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; the G-buffer channels and EXTRA; a
+ * group's composite; the ring in a snapshot; of the warp: depth-aware (positional) reprojection from POSITION; a
+ * homography latched from device memory at kernel time; edge clamping beyond half a texel and filters other than
+ * bilinear; lens distortion; outputs larger than the screen; groups; of the blend: radii latched on the device from
+ * the ray budget controller's r2; elliptical or per-eye zones; more than two sources; curves other than smoothstep;
+ * groups. */
 #define FR_PRESENT_RGBA8    0
 #define FR_PRESENT_BGRA8    1
 #define FR_PRESENT_TOP_DOWN 0x100   /* or-ed into the format */
@@ -1065,6 +1109,18 @@ int fr_present_warp_from_poses(const fr_camera_pose* rendered, const fr_camera_p
                                int out_width, int out_height, float ndc_depth, fr_present_warp* warp);
 int fr_present_enqueue_warped(fr_ctx* ctx, int buffer_id, const fr_present_warp* warp, uint64_t* ticket);
 int fr_present_enqueue_warped_device(fr_ctx* ctx, int buffer_id, const fr_present_warp* warp, void* device_dst, size_t bytes);
+typedef struct fr_present_blend {
+  int inner_buffer, outer_buffer;          /* any two of SHADING, SIBSON, PULLPUSH, ATROUS; may be equal */
+  float gaze[2];                           /* finite; may lie off screen */
+  float inner_radius_px, outer_radius_px;  /* finite, 0 <= inner <= outer, outer * outer finite in fp32 */
+} fr_present_blend;
+int fr_present_blend_default(fr_ctx* ctx, fr_present_blend* blend);
+int fr_present_blend_pack(const float* inner, const float* outer, int width, int height, int format,
+                          const fr_present_blend* blend, const fr_present_warp* warp /* NULL: plain */, uint8_t* out);
+int fr_present_enqueue_blended(fr_ctx* ctx, const fr_present_blend* blend, const fr_present_warp* warp /* NULL: plain */,
+                               uint64_t* ticket);
+int fr_present_enqueue_blended_device(fr_ctx* ctx, const fr_present_blend* blend, const fr_present_warp* warp,
+                                      void* device_dst, size_t bytes);
 
 int fr_get_stats(fr_ctx* ctx, fr_stats* stats);
 int fr_reset_stats(fr_ctx* ctx);

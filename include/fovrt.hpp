@@ -85,6 +85,30 @@ inline std::vector<uint8_t> present_warp_pack(const std::vector<float>& rgba, in
   return out;
 }
 
+// fr_present_blend: the two sources, the gaze and the two radii of a blended present (the rule is in fovrt.h under
+// "Present"); PathTracer::present_blend_default gives a context's own
+struct PresentBlend : fr_present_blend {
+  PresentBlend() : fr_present_blend{FR_BUF_SIBSON, FR_BUF_ATROUS, {0, 0}, 0, 0} {}
+  PresentBlend(float gx, float gy, float inner_radius, float outer_radius, int inner = FR_BUF_SIBSON, int outer = FR_BUF_ATROUS)
+      : fr_present_blend{inner, outer, {gx, gy}, inner_radius, outer_radius} {}
+};
+
+// fr_present_blend_pack: the blended present rule on the host; warp nullptr: width * height * 4 bytes, else the
+// warp's out_width * out_height * 4
+inline std::vector<uint8_t> present_blend_pack(const std::vector<float>& inner, const std::vector<float>& outer, int width,
+                                               int height, const fr_present_blend& blend, const fr_present_warp* warp = nullptr,
+                                               int format = FR_PRESENT_RGBA8) {
+  if (width < 1 || height < 1 || inner.size() != (size_t)width * height * 4 || outer.size() != inner.size())
+    throw Error(FR_E_INVALID, "present_blend_pack: size");
+  const bool whole = !warp || (warp->out_width == 0 && warp->out_height == 0);
+  const int ow = whole ? width : warp->out_width, oh = whole ? height : warp->out_height;
+  if (ow < 1 || oh < 1 || ow > width || oh > height) throw Error(FR_E_INVALID, "present_blend_pack: output size");
+  std::vector<uint8_t> out((size_t)ow * oh * 4);
+  if (int rc = fr_present_blend_pack(inner.data(), outer.data(), width, height, format, &blend, warp, out.data()))
+    throw Error(rc, "present_blend_pack: bad format, blend or warp");
+  return out;
+}
+
 // A GL texture name of the reference = a buffer id of the context here.
 struct Texture {
   int id = -1;
@@ -457,6 +481,21 @@ class PathTracer {
   }
   void present_warped_to(int buffer, const fr_present_warp& warp, void* device_dst, size_t bytes) {
     check(fr_present_enqueue_warped_device(ctx(), buffer, &warp, device_dst, bytes), ctx_, "present_warped_to");
+  }
+  // A blended present (fr_present_enqueue_blended, fr_present_enqueue_blended_device): blend.inner_buffer around the
+  // gaze, blend.outer_buffer in the periphery, their smoothstep mix between the radii; through `warp` when one is given.
+  PresentBlend present_blend_default() {
+    PresentBlend b;
+    check(fr_present_blend_default(ctx(), &b), ctx_, "present_blend_default");
+    return b;
+  }
+  uint64_t present_blended(const fr_present_blend& blend, const fr_present_warp* warp = nullptr) {
+    uint64_t t = 0;
+    check(fr_present_enqueue_blended(ctx(), &blend, warp, &t), ctx_, "present_blended");
+    return t;
+  }
+  void present_blended_to(const fr_present_blend& blend, void* device_dst, size_t bytes, const fr_present_warp* warp = nullptr) {
+    check(fr_present_enqueue_blended_device(ctx(), &blend, warp, device_dst, bytes), ctx_, "present_blended_to");
   }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
