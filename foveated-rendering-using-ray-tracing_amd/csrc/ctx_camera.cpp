@@ -229,4 +229,22 @@ int fr_present_warp_from_poses(const fr_camera_pose* rendered, const fr_camera_p
   return FR_OK;
 }
 
+// The reprojected present's parameters for the same two poses: vp, the display camera's proj * view (the fp32 matrices
+// of fr_camera_matrices multiplied in f64, rounded once), and the homography above for the places nothing reaches.
+int fr_present_reproject_from_poses(const fr_camera_pose* rendered, const fr_camera_pose* display, int width, int height,
+                                    int out_width, int out_height, float ndc_depth, fr_present_reproject* rp) {
+  if (!rp) return FR_E_INVALID;
+  fr_present_reproject out;
+  if (int rc = fr_present_warp_from_poses(rendered, display, width, height, out_width, out_height, ndc_depth, &out.fallback))
+    return rc;
+  double Md[16];
+  pose_pv_f64(display, Md);  // (finite: the warp checked it)
+  for (int k = 0; k < 16; k++) {
+    out.vp[k] = (float)Md[k];
+    if (!std::isfinite(out.vp[k])) return FR_E_INVALID;
+  }
+  *rp = out;
+  return FR_OK;
+}
+
 }  // extern "C"

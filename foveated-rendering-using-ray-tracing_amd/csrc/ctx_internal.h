@@ -253,7 +253,9 @@ struct fr_ctx {
   // kernel and the copy to the host and nothing else; per ring slot a device staging image, a pinned host image and
   // three timed events on that stream (begin: before the pack, packed: after it, done: after the copy; done is the
   // one fr_present_acquire waits for); ev_fork: the context stream records, the present stream waits (what a present
-  // sees). ring: tickets and slot states, no HIP in it. made: slots that have their two images.
+  // sees). ring: tickets and slot states, no HIP in it. made: slots that have their two images. keys: the W x H 64-bit
+  // key image of the reprojected present (fr_present_reproject_enable makes it; null until then), used by the present
+  // stream alone; reproject: those presents are on.
   // The fences of the other direction, recorded on the present stream after a pack and only ever peeked (several
   // streams wait for one record; fr_synchronize clears them): present_read after a pack of SIBSON, PULLPUSH or an
   // A-Trous image, for the next writers of those (sibson_stream and atrous_stream at a frame's fork, the context stream
@@ -265,6 +267,8 @@ struct fr_ctx {
     hipEvent_t ev_fork = nullptr;
     int format = 0;
     int made = 0;
+    unsigned long long* keys = nullptr;
+    bool reproject = false;
     fr::PresentRing ring;
     void* stage[fr::PresentRing::MAX_SLOTS] = {};
     void* host[fr::PresentRing::MAX_SLOTS] = {};

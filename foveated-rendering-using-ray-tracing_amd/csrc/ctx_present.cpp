@@ -8,7 +8,12 @@
 // ow * oh * 4 bytes to the host, no more. fr_present_enqueue_blended and fr_present_enqueue_blended_device are the same
 // again over a virtual image that mixes two of the images around a gaze point (k_present_blend, k_present_blend_warp;
 // fr_present_blend_pack on the host): the present stream waits as for one image, and the fence of each source is
-// recorded behind the kernel.
+// recorded behind the kernel. fr_present_enqueue_reprojected and fr_present_enqueue_reprojected_device are the warped
+// calls with three launches in the kernel's place (launch_present_reproject, k_present_reproject.hip: a clear of the
+// context's key image, a scatter of the source by the frame slot's POSITION, a resolve that falls back to the
+// homography), and fr_present_reproject_pack is that rule on the host. They read POSITION beside the source, so the
+// slot's present_read_shd is recorded behind them whatever the source is: POSITION's next writers (the front stages of
+// the frame that takes the slot next; a stage call, a write or a restore through join_recon) wait for it already.
 //
 // Ordering. A present reads one of the images a frame's last stages write (SIBSON on sibson_stream, PULLPUSH and the
 // A-Trous pair on atrous_stream, the slot's SHADING on the context stream; stage calls and fr_write_buffer write all
@@ -25,6 +30,7 @@
 // reads the staging image, which nothing but this stream touches, so nothing of a frame ever waits for a copy.
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "ctx_internal.h"
 
@@ -78,6 +84,17 @@ bool blend_ok(const fr_present_blend* blend, PresentBlend* b) {
   *b = PresentBlend{blend->gaze[0], blend->gaze[1], r0sq, r1sq};
   return true;
 }
+// A reprojection as the host rule and both reprojected enqueues take it: sixteen finite coefficients and a fallback
+// that is a warp.
+bool reproject_ok(const fr_present_reproject* rp, int W, int H, int* ow, int* oh) {
+  if (!rp) return false;
+  for (float v : rp->vp) if (!std::isfinite(v)) return false;
+  return warp_ok(&rp->fallback, W, H, ow, oh);
+}
+const char* const kBadReproject =
+    ": the reprojection is NULL, has a non-finite coefficient, or its fallback has one or an output size outside 1..W x 1..H";
+
+const char* const kReprojectOff = ": reprojected presents are not enabled (fr_present_reproject_enable)";
 const char* const kBadBlend =
     ": the blend is NULL, has a non-finite gaze or radius, a negative radius, inner > outer, or an outer radius whose "
     "square is not finite";
@@ -127,15 +144,18 @@ int check_enqueue(fr_ctx* c, const std::string& name, int buffer_id, const fr_pr
 // The present stream behind what wrote the image (the head of this file), then the pack into dst, then the fence
 // its next writer waits for: of each source, when the present blends two. begin / packed: a slot's timing events, or
 // NULL. warp: NULL for the plain pack, else the checked homography with its output size ow x oh (the kernels take warp
-// and blend by value: nothing is read after the call).
-int enqueue_pack(fr_ctx* c, const Source& src, const fr_present_warp* warp, int ow, int oh, void* dst, hipEvent_t begin,
-                 hipEvent_t packed) {
+// and blend by value: nothing is read after the call). rp: the checked reprojection, whose fallback `warp` then is.
+int enqueue_pack(fr_ctx* c, const Source& src, const fr_present_reproject* rp, const fr_present_warp* warp, int ow, int oh,
+                 void* dst, hipEvent_t begin, hipEvent_t packed) {
   fr_ctx::Present& P = c->present;
   HIP_TRY(c, hipEventRecord(P.ev_fork, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(P.stream, P.ev_fork, 0));
   for (const Fence& f : c->recon_done) HIP_TRY(c, f.peek(P.stream));
   if (begin) HIP_TRY(c, hipEventRecord(begin, P.stream));
-  if (src.blended)
+  if (rp)
+    launch_present_reproject(c->img[src.phys], c->img[P_pos(c)], c->W, c->H, P.format, rp->vp, warp->h, ow, oh, P.keys, dst,
+                             P.stream);
+  else if (src.blended)
     launch_present_blend(c->img[src.phys], c->img[src.outer], c->W, c->H, P.format, src.blend, warp ? warp->h : nullptr, ow, oh,
                          dst, P.stream);
   else if (warp)
@@ -145,29 +165,36 @@ int enqueue_pack(fr_ctx* c, const Source& src, const fr_present_warp* warp, int 
   if (int rc = check_launch(c)) return rc;
   if (packed) HIP_TRY(c, hipEventRecord(packed, P.stream));
   const int shd = P_shd(c);
-  if (src.phys == shd || src.outer == shd) HIP_TRY(c, c->present_read_shd[c->slot].record(P.stream));
+  if (rp || src.phys == shd || src.outer == shd) HIP_TRY(c, c->present_read_shd[c->slot].record(P.stream));
   if (src.phys != shd || src.outer != shd) HIP_TRY(c, c->present_read.record(P.stream));
   return FR_OK;
 }
 
 // fr_present_enqueue (warp NULL), fr_present_enqueue_warped and (blended: the sources are the blend's, buffer_id is not
-// used) fr_present_enqueue_blended: into the next free slot and on to its pinned image.
+// used) fr_present_enqueue_blended: into the next free slot and on to its pinned image. reproject:
+// fr_present_enqueue_reprojected, the warp is rp's fallback.
 int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
-                 const fr_present_warp* warp, bool warped, uint64_t* ticket) {
+                 const fr_present_warp* warp, bool warped, uint64_t* ticket, const fr_present_reproject* rp = nullptr,
+                 bool reproject = false) {
   if (!c || !ticket) return FR_E_INVALID;
   int ow = c->W, oh = c->H;
-  if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
+  if (reproject) {
+    if (!reproject_ok(rp, c->W, c->H, &ow, &oh)) return fail(c, FR_E_INVALID, name + kBadReproject);
+    warp = &rp->fallback;
+  } else if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
     return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
   Source src;
   if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
   if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
   fr_ctx::Present& P = c->present;
+  if (reproject && !P.reproject) return fail(c, FR_E_STATE, name + kReprojectOff);
   uint64_t t = 0;
   const int s = P.ring.enqueue(&t);
   if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
   hipSetDevice(c->cfg.device);
   // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
-  int rc = enqueue_pack(c, src, warped ? warp : nullptr, ow, oh, P.stage[s], P.ev[s].begin, P.ev[s].packed);
+  int rc = enqueue_pack(c, src, reproject ? rp : nullptr, warped || reproject ? warp : nullptr, ow, oh, P.stage[s],
+                        P.ev[s].begin, P.ev[s].packed);
   if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], (size_t)ow * oh * 4, hipMemcpyDeviceToHost, P.stream) != hipSuccess)
     rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
   if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
@@ -180,12 +207,16 @@ int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_pre
 }
 
 // fr_present_enqueue_device (warp NULL), fr_present_enqueue_warped_device and (blended) fr_present_enqueue_blended_device:
-// straight into the caller's memory.
+// straight into the caller's memory. reproject: fr_present_enqueue_reprojected_device, the warp is rp's fallback.
 int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
-                   const fr_present_warp* warp, bool warped, void* device_dst, size_t bytes) {
+                   const fr_present_warp* warp, bool warped, void* device_dst, size_t bytes,
+                   const fr_present_reproject* rp = nullptr, bool reproject = false) {
   if (!c) return FR_E_INVALID;
   int ow = c->W, oh = c->H;
-  if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
+  if (reproject) {
+    if (!reproject_ok(rp, c->W, c->H, &ow, &oh)) return fail(c, FR_E_INVALID, name + kBadReproject);
+    warp = &rp->fallback;
+  } else if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
     return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
   if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
     return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
@@ -193,8 +224,11 @@ int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_p
   Source src;
   if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
   if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
+  if (reproject && !c->present.reproject) return fail(c, FR_E_STATE, name + kReprojectOff);
   hipSetDevice(c->cfg.device);
-  if (int rc = enqueue_pack(c, src, warped ? warp : nullptr, ow, oh, device_dst, nullptr, nullptr)) return rc;
+  if (int rc = enqueue_pack(c, src, reproject ? rp : nullptr, warped || reproject ? warp : nullptr, ow, oh, device_dst, nullptr,
+                            nullptr))
+    return rc;
   HIP_TRY(c, c->present_dev.record(c->present.stream));
   return FR_OK;
 }
@@ -218,6 +252,7 @@ void present_destroy(fr_ctx* c) {
   fr_ctx::Present& P = c->present;
   if (P.stream) hipStreamSynchronize(P.stream);
   free_slots(P);
+  if (P.keys) hipFree(P.keys);
   for (auto& e : P.ev)
     for (hipEvent_t v : {e.begin, e.packed, e.done}) if (v) hipEventDestroy(v);
   if (P.ev_fork) hipEventDestroy(P.ev_fork);
@@ -394,6 +429,77 @@ int fr_present_enqueue_blended(fr_ctx* c, const fr_present_blend* blend, const f
 int fr_present_enqueue_blended_device(fr_ctx* c, const fr_present_blend* blend, const fr_present_warp* warp, void* device_dst,
                                       size_t bytes) {
   return enqueue_device(c, "fr_present_enqueue_blended_device", 0, blend, true, warp, warp != nullptr, device_dst, bytes);
+}
+
+int fr_present_reproject_pack(const float* rgba, const float* position, int width, int height, int format,
+                              const fr_present_reproject* rp, uint8_t* out) {
+  if (!rgba || !position || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format))
+    return FR_E_INVALID;
+  int ow, oh;
+  if (!reproject_ok(rp, width, height, &ow, &oh)) return FR_E_INVALID;
+  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
+  const auto texel = [width](const float* img) {
+    return [img, width](int i, int row) {
+      const float* t = img + ((size_t)row * width + i) * 4;
+      return mk4(t[0], t[1], t[2], t[3]);
+    };
+  };
+  const auto fetch = texel(rgba), fpos = texel(position);
+  std::vector<uint64_t> keys((size_t)ow * oh, PRESENT_KEY_EMPTY);  // the clear
+  for (int j = 0; j < height; j++)                                   // the splat
+    for (int i = 0; i < width; i++) {
+      int ox, oy;
+      uint32_t depth;
+      if (!present_splat_place(fpos(i, j), rp->vp, ow, oh, &ox, &oy, &depth)) continue;
+      const uint64_t key = present_splat_key(depth, present_texel(fetch(i, j), bgra));
+      uint64_t& k = keys[(size_t)oy * ow + ox];
+      if (key < k) k = key;
+    }
+  const auto key = [&keys, ow](int i, int row) { return keys[(size_t)row * ow + i]; };
+  for (int r = 0; r < oh; r++) {  // the resolve
+    const int y = top_down ? oh - 1 - r : r;
+    uint8_t* o = out + (size_t)r * ow * 4;
+    for (int x = 0; x < ow; x++) {
+      uint32_t w;
+      if (!present_resolve_word(key(x, y), key, ow, oh, x, y, &w)) w = present_warp_texel(fetch, width, height, rp->fallback.h, x, y, bgra);
+      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
+    }
+  }
+  return FR_OK;
+}
+
+int fr_present_reproject_enable(fr_ctx* c, int on) {
+  if (!c) return FR_E_INVALID;
+  const std::string name = "fr_present_reproject_enable";
+  fr_ctx::Present& P = c->present;
+  if (!on) {
+    P.reproject = false;
+    return FR_OK;
+  }
+  if (P.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
+  if (!P.keys) {
+    if (int rc = quiesce(c)) return rc;
+    if (int rc = present_sync(c)) return rc;
+    hipSetDevice(c->cfg.device);
+    void* k = nullptr;
+    if (hipMalloc(&k, (size_t)c->W * c->H * sizeof(unsigned long long)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, FR_E_NOMEM, name + ": allocation failed (nothing is kept, reprojected presents are off)");
+    }
+    P.keys = static_cast<unsigned long long*>(k);
+  }
+  P.reproject = true;
+  return FR_OK;
+}
+
+int fr_present_enqueue_reprojected(fr_ctx* c, int buffer_id, const fr_present_reproject* rp, uint64_t* ticket) {
+  return enqueue_host(c, "fr_present_enqueue_reprojected", buffer_id, nullptr, false, nullptr, false, ticket, rp, true);
+}
+
+int fr_present_enqueue_reprojected_device(fr_ctx* c, int buffer_id, const fr_present_reproject* rp, void* device_dst,
+                                          size_t bytes) {
+  return enqueue_device(c, "fr_present_enqueue_reprojected_device", buffer_id, nullptr, false, nullptr, false, device_dst,
+                        bytes, rp, true);
 }
 
 int fr_present_done(fr_ctx* c, void* stream) {

@@ -101,6 +101,12 @@ void launch_present_warp(const f4* src, int W, int H, int format, const float* h
 // one image; the blend is copied into the kernel's arguments. h NULL: the plain form (ow x oh = W x H)
 void launch_present_blend(const f4* inner, const f4* outer, int W, int H, int format, const PresentBlend& blend,
                           const float* h, int ow, int oh, void* out, hipStream_t stream);
+// k_present_reproject.hip: the reprojected present (present_splat_place, present_resolve_word, fr_math.h). keys: room
+// for W * H 64-bit keys, of which the first ow * oh are cleared, splatted into (every texel of src whose pos lands in
+// the ow x oh output under vp[16], the smallest key winning) and resolved to ow * oh words at out; h[9]: the
+// homography of the places nothing reaches. vp and h are copied into the kernels' arguments. Three launches on stream.
+void launch_present_reproject(const f4* src, const f4* pos, int W, int H, int format, const float* vp, const float* h,
+                              int ow, int oh, unsigned long long* keys, void* out, hipStream_t stream);
 
 // k_jfa.hip, k_sibson.hip
 // A context's JumpFlooding state: G, H the passes' ping-pong, F the final state (retained while the seed set stays),

@@ -129,6 +129,10 @@ class fr_present_blend(C.Structure):
                 ("inner_radius_px", C.c_float), ("outer_radius_px", C.c_float)]
 
 
+class fr_present_reproject(C.Structure):
+    _fields_ = [("vp", C.c_float * 16), ("fallback", fr_present_warp)]
+
+
 class fr_ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
 
@@ -286,6 +290,14 @@ _SIGS = {
                               C.POINTER(fr_present_warp), C.c_void_p],
     "fr_present_enqueue_blended": [C.c_void_p, C.POINTER(fr_present_blend), C.POINTER(fr_present_warp),
                                    C.POINTER(C.c_uint64)],
+    "fr_present_reproject_from_poses": [C.POINTER(fr_camera_pose), C.POINTER(fr_camera_pose), C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_float, C.POINTER(fr_present_reproject)],
+    "fr_present_reproject_pack": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fr_present_reproject),
+                                  C.c_void_p],
+    "fr_present_reproject_enable": [C.c_void_p, C.c_int],
+    "fr_present_enqueue_reprojected": [C.c_void_p, C.c_int, C.POINTER(fr_present_reproject), C.POINTER(C.c_uint64)],
+    "fr_present_enqueue_reprojected_device": [C.c_void_p, C.c_int, C.POINTER(fr_present_reproject), C.c_void_p,
+                                              C.c_size_t],
     "fr_present_enqueue_blended_device": [C.c_void_p, C.POINTER(fr_present_blend), C.POINTER(fr_present_warp),
                                           C.c_void_p, C.c_size_t],
     "fr_set_normals": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
@@ -1149,6 +1161,25 @@ class PathTracer:
                                                            None if warp is None else C.byref(warp.c_struct()),
                                                            self._device_ptr(tensor), nbytes))
 
+    def present_reproject_enable(self, on=True):
+        """fr_present_reproject_enable: the key image of the reprojected present (W * H * 8 bytes, made by the first
+        call, which waits for the context's pending work); after present_enable. on=False turns the calls off."""
+        self._check(_lib.fr_present_reproject_enable(self._ctx, int(bool(on))))
+
+    def present_reprojected(self, buffer, rp) -> int:
+        """fr_present_enqueue_reprojected: as present_warped(), with every texel moved to where the display camera of
+        `rp` (a PresentReproject) sees its POSITION; rp.fallback fills where nothing lands. Returns the ticket."""
+        t = C.c_uint64()
+        self._check(_lib.fr_present_enqueue_reprojected(self._ctx, int(buffer), C.byref(rp.c_struct()), C.byref(t)))
+        self.__dict__.setdefault("_warped_shapes", {})[t.value] = rp.fallback.shape(self.width, self.height)
+        return t.value
+
+    def present_reprojected_to(self, buffer, rp, tensor):
+        """fr_present_enqueue_reprojected_device: as present_warped_to(), reprojected by `rp`."""
+        nbytes = tensor.numel() * tensor.element_size()
+        self._check(_lib.fr_present_enqueue_reprojected_device(self._ctx, int(buffer), C.byref(rp.c_struct()),
+                                                               self._device_ptr(tensor), nbytes))
+
     def present_times(self, ticket) -> dict:
         """fr_present_times: the pack kernel's and the host copy's time of an acquired ticket, in ms."""
         a, b = C.c_float(), C.c_float()
@@ -1558,6 +1589,60 @@ def present_blend_pack(inner, outer, blend, warp=None, format=FR_PRESENT_RGBA8) 
                                    C.c_void_p(out.ctypes.data))
     if rc:
         raise FovrtError(rc, "fr_present_blend_pack: bad size, format, blend or warp")
+    return out
+
+
+class PresentReproject:
+    """fr_present_reproject: vp (16 float32, row-major: a world point to the display camera's clip space) and the
+    fallback homography (a PresentWarp, whose output size is the output's). include/fovrt.h, "Present", has the rule."""
+
+    def __init__(self, vp, fallback=None):
+        self.vp = np.asarray(vp, np.float32).reshape(16).copy()
+        self.fallback = PresentWarp.identity() if fallback is None else fallback
+
+    def c_struct(self) -> fr_present_reproject:
+        r = fr_present_reproject()
+        C.memmove(r.vp, self.vp.ctypes.data, 64)  # the bits as they are
+        r.fallback = self.fallback.c_struct()
+        return r
+
+    @staticmethod
+    def from_poses(rendered, display, width, height, out_width=None, out_height=None, ndc_depth=1.0):
+        return present_reproject_from_poses(rendered, display, width, height, out_width, out_height, ndc_depth)
+
+
+def present_reproject_from_poses(rendered, display, width, height, out_width=None, out_height=None,
+                                 ndc_depth=1.0) -> PresentReproject:
+    """fr_present_reproject_from_poses (host only): `rendered` is the camera the frame was traced with, `display` the
+    one it is shown for (each a Camera or an fr_camera_pose): the display camera's proj * view, and the homography of
+    present_warp_from_poses for the same arguments as the fallback."""
+    lib = load_library()
+    r, d = (p._pose() if isinstance(p, Camera) else p for p in (rendered, display))
+    rp = fr_present_reproject()
+    rc = lib.fr_present_reproject_from_poses(C.byref(r), C.byref(d), int(width), int(height),
+                                             int(width if out_width is None else out_width),
+                                             int(height if out_height is None else out_height), C.c_float(ndc_depth),
+                                             C.byref(rp))
+    if rc:
+        raise FovrtError(rc, "fr_present_reproject_from_poses: bad size or depth, a singular matrix, or the output's "
+                             "corner is not in front of the rendered camera")
+    return PresentReproject(np.array(rp.vp[:], np.float32),
+                            PresentWarp(np.array(rp.fallback.h[:], np.float32), rp.fallback.out_width, rp.fallback.out_height))
+
+
+def present_reproject_pack(rgba, position, rp, format=FR_PRESENT_RGBA8) -> np.ndarray:
+    """fr_present_reproject_pack (host only): an (H, W, 4) float32 image and its (H, W, 4) float32 POSITION through
+    `rp` (a PresentReproject) as (oh, ow, 4) uint8 by the reprojected present rule, through the functions the kernels
+    run."""
+    lib = load_library()
+    a, p = (np.ascontiguousarray(x, dtype=np.float32) for x in (rgba, position))
+    if a.ndim != 3 or a.shape[2] != 4 or p.shape != a.shape:
+        raise ValueError("present_reproject_pack: two (H, W, 4) float32 images of one size")
+    out = np.empty(rp.fallback.shape(a.shape[1], a.shape[0]) + (4,), np.uint8)
+    rc = lib.fr_present_reproject_pack(C.c_void_p(a.ctypes.data), C.c_void_p(p.ctypes.data), a.shape[1], a.shape[0],
+                                       int(format), C.byref(rp.c_struct()), C.c_void_p(out.ctypes.data))
+    if rc:
+        raise FovrtError(rc, "fr_present_reproject_pack: bad size, format or reprojection")
     return out
 
 

@@ -1085,12 +1085,74 @@ int fr_restore(fr_ctx* ctx, const void* host, size_t bytes);
  * presentable, a non-finite gaze or radius, a negative radius, inner_radius_px > outer_radius_px, an outer_radius_px
  * whose fp32 square is not finite (FR_E_INVALID).
  *
+ * Present with positional reprojection: a depth-aware splat of POSITION. The homography is exact for a rotation of the
+ * head only; a translation is right at ndc_depth and wrong everywhere else, so near objects swim against far ones.
+ * fr_present_enqueue_reprojected and fr_present_enqueue_reprojected_device are the two warped enqueue calls with the
+ * frame's world-space hit points beside the image: every texel moves to where the display camera sees its hit point,
+ * the nearest texel wins where several land in one place, and the homography fills where nothing lands (sky,
+ * disocclusions). They are the warped enqueues in every respect of ordering: the same buffers, resolved at the call;
+ * the same waits of the present stream; the same ring, tickets, acquire, release, times and fr_present_done; only
+ * ow * oh * 4 bytes go to the host; rp is read during the call and travels in the kernels' arguments. POSITION is the
+ * frame slot's at the call, as fr_read_buffer(FR_BUF_POSITION) would resolve it there; behind the kernels the fence
+ * its next writer waits for is recorded beside the source's. Plain, warped, blended and reprojected presents may be
+ * mixed freely.
+ * The rule, with one right answer in bytes. fp32, every operation rounded on its own, no fma, '/' correctly rounded.
+ * S is the W x H source image and P the W x H POSITION image, row 0 at the bottom; the output is ow x oh, 1 <= ow <= W
+ * and 1 <= oh <= H (0, 0 means W x H): the fallback's output size. vp[0..15] is row-major and takes a world point to
+ * the display camera's clip space. K is an ow x oh image of 64-bit keys; its row 0 is the bottom row, whatever the
+ * output's row order.
+ *   1. Clear. Every K[y][x] = 0xFFFFFFFFFFFFFFFF.
+ *   2. Splat. For every source texel (i, j), with p = P[j][i]:
+ *        if p.x == 0 && p.y == 0 && p.z == 0                      -> skip   (the G-buffer writes exactly 0, 0, 0, 1
+ *                                                                           for a miss: sky has no depth)
+ *        cx = ((vp[0]*p.x + vp[1]*p.y) + vp[2]*p.z) + vp[3]       cy alike from row 1, cw from row 3; row 2 is not used
+ *        if !(cw > 0)                                             -> skip
+ *        iw = 1.0f / cw
+ *        sx = ((cx*iw)*0.5f + 0.5f) * (float)ow                   sy = ((cy*iw)*0.5f + 0.5f) * (float)oh
+ *        if !(sx >= 0 && sx < (float)ow && sy >= 0 && sy < (float)oh)  -> skip   (false for NaN and +-Inf: non-finite
+ *                                                                                positions fall out here)
+ *        ox = (int)sx      oy = (int)sy
+ *        q   = the packed 8-bit word of S[j][i] by the rule at the top, in the ring's format (byte 0 lowest)
+ *        key = ((uint64)bits(cw) << 32) | q
+ *        K[oy][ox] = min(K[oy][ox], key)                          as unsigned 64-bit
+ *      cw > 0, so its bits order as its value: the nearest point wins; equal depths go to the smaller word. The
+ *      minimum does not depend on the order of arrival, which is why the scatter has one right answer.
+ *   3. Resolve. For output column x and output row r, y = r, or oh - 1 - r with FR_PRESENT_TOP_DOWN:
+ *        K[y][x] is not all ones                                  -> the texel is its low word
+ *        else, the crack rule: (left and right are both inside the image and both covered) or (below and above are
+ *        both inside the image and both covered), in K as the splat left it
+ *                                                                 -> the low word of the smallest key among the
+ *                                                                    covered 4-neighbours
+ *        else                                                     -> the warped rule's texel of the fallback
+ *                                                                    homography at (x, y), unchanged, border texels
+ *                                                                    included
+ *      A one-texel crack opens wherever the display camera is closer than the rendered one.
+ * fr_present_reproject_from_poses (host only, f64 throughout, rounded once to fp32): vp = proj * view of
+ * fr_camera_matrices(display); fallback is what fr_present_warp_from_poses gives for the same arguments, with the same
+ * refusals, *rp untouched on refusal. Equal poses give the rendered camera's vp and the exact scale or identity
+ * fallback. The late-reprojection recipe: `rendered` is the pose the frame was traced with, `display` the pose sampled
+ * just before the present.
+ * fr_present_reproject_pack states the rule on the host, without a device, through the functions the kernels run
+ * (rgba, position: width * height * 4 floats each; out: the output's width * height * 4 bytes), with K in a temporary
+ * of its own; FR_E_INVALID as fr_present_warp_pack with the fallback as its warp, and for a NULL position or rp or a
+ * non-finite vp coefficient.
+ * fr_present_reproject_enable(ctx, 1): the first call waits for the context's pending work and allocates the key
+ * image, W * H * 8 bytes; it needs fr_present_enable first (FR_E_STATE otherwise); FR_E_NOMEM keeps nothing and leaves
+ * the feature off. on = 0 makes the two enqueues return FR_E_STATE and frees nothing before fr_destroy. No other call
+ * of the feature allocates, and a context that never calls it creates the streams and enqueues the work it always did.
+ * Refused with nothing enqueued, nothing written and no ticket taken: everything the warped enqueues refuse, with their
+ * codes, the fallback being checked as a warp is; a NULL rp, a non-finite vp coefficient (FR_E_INVALID); the feature or
+ * the ring not enabled, or the ring full (FR_E_STATE); a rank of a group or a sharded context (FR_E_UNSUPPORTED).
+ *
  * Not covered: a transfer curve or dithering; NV12 / YUV and 10-bit outputs; the G-buffer channels and EXTRA; a
- * group's composite; the ring in a snapshot; of the warp: depth-aware (positional) reprojection from POSITION; a
+ * group's composite; the ring in a snapshot; of the warp: a
  * homography latched from device memory at kernel time; edge clamping beyond half a texel and filters other than
  * bilinear; lens distortion; outputs larger than the screen; groups; of the blend: radii latched on the device from
  * the ray budget controller's r2; elliptical or per-eye zones; more than two sources; curves other than smoothstep;
- * groups. */
+ * groups; of the positional reprojection: a blended source; splats larger than one texel or bilinear weights;
+ * motion-vector (moving geometry) extrapolation; a second layer behind glass (POSITION is the primary hit, so what is
+ * seen through the refractive box moves with the box's surface); outputs larger than the screen; groups; the key image
+ * in a snapshot. */
 #define FR_PRESENT_RGBA8    0
 #define FR_PRESENT_BGRA8    1
 #define FR_PRESENT_TOP_DOWN 0x100   /* or-ed into the format */
@@ -1121,6 +1183,18 @@ int fr_present_enqueue_blended(fr_ctx* ctx, const fr_present_blend* blend, const
                                uint64_t* ticket);
 int fr_present_enqueue_blended_device(fr_ctx* ctx, const fr_present_blend* blend, const fr_present_warp* warp,
                                       void* device_dst, size_t bytes);
+typedef struct fr_present_reproject {
+  float vp[16];              /* world -> display clip, row-major */
+  fr_present_warp fallback;  /* where nothing lands; its out size is the output's */
+} fr_present_reproject;
+int fr_present_reproject_from_poses(const fr_camera_pose* rendered, const fr_camera_pose* display, int width, int height,
+                                    int out_width, int out_height, float ndc_depth, fr_present_reproject* rp);
+int fr_present_reproject_pack(const float* rgba, const float* position, int width, int height, int format,
+                              const fr_present_reproject* rp, uint8_t* out);
+int fr_present_reproject_enable(fr_ctx* ctx, int on);
+int fr_present_enqueue_reprojected(fr_ctx* ctx, int buffer_id, const fr_present_reproject* rp, uint64_t* ticket);
+int fr_present_enqueue_reprojected_device(fr_ctx* ctx, int buffer_id, const fr_present_reproject* rp,
+                                          void* device_dst, size_t bytes);
 
 int fr_get_stats(fr_ctx* ctx, fr_stats* stats);
 int fr_reset_stats(fr_ctx* ctx);

@@ -109,6 +109,35 @@ inline std::vector<uint8_t> present_blend_pack(const std::vector<float>& inner, 
   return out;
 }
 
+// fr_present_reproject: the display camera's proj * view and the fallback homography of a reprojected present (the
+// rule is in fovrt.h under "Present")
+struct PresentReproject : fr_present_reproject {
+  PresentReproject() : fr_present_reproject{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, PresentWarp()} {}
+  // fr_present_reproject_from_poses: `rendered` is the pose the frame was traced with, `display` the one it is shown for
+  static PresentReproject from_poses(const fr_camera_pose& rendered, const fr_camera_pose& display, int width, int height,
+                                     int out_width, int out_height, float ndc_depth = 1.0f) {
+    PresentReproject r;
+    if (int rc = fr_present_reproject_from_poses(&rendered, &display, width, height, out_width, out_height, ndc_depth, &r))
+      throw Error(rc, "present_reproject_from_poses: bad size or depth, a singular matrix, or a corner behind the rendered camera");
+    return r;
+  }
+};
+
+// fr_present_reproject_pack: the reprojected present rule on the host; the result holds the fallback's
+// out_width * out_height * 4 bytes (0, 0: width * height * 4)
+inline std::vector<uint8_t> present_reproject_pack(const std::vector<float>& rgba, const std::vector<float>& position, int width,
+                                                   int height, const fr_present_reproject& rp, int format = FR_PRESENT_RGBA8) {
+  if (width < 1 || height < 1 || rgba.size() != (size_t)width * height * 4 || position.size() != rgba.size())
+    throw Error(FR_E_INVALID, "present_reproject_pack: size");
+  const bool whole = rp.fallback.out_width == 0 && rp.fallback.out_height == 0;
+  const int ow = whole ? width : rp.fallback.out_width, oh = whole ? height : rp.fallback.out_height;
+  if (ow < 1 || oh < 1 || ow > width || oh > height) throw Error(FR_E_INVALID, "present_reproject_pack: output size");
+  std::vector<uint8_t> out((size_t)ow * oh * 4);
+  if (int rc = fr_present_reproject_pack(rgba.data(), position.data(), width, height, format, &rp, out.data()))
+    throw Error(rc, "present_reproject_pack: bad format or reprojection");
+  return out;
+}
+
 // A GL texture name of the reference = a buffer id of the context here.
 struct Texture {
   int id = -1;
@@ -496,6 +525,19 @@ class PathTracer {
   }
   void present_blended_to(const fr_present_blend& blend, void* device_dst, size_t bytes, const fr_present_warp* warp = nullptr) {
     check(fr_present_enqueue_blended_device(ctx(), &blend, warp, device_dst, bytes), ctx_, "present_blended_to");
+  }
+  // A reprojected present (fr_present_reproject_enable, fr_present_enqueue_reprojected, _device): every texel moved to
+  // where the display camera sees its POSITION, the fallback homography where nothing lands. After present_enable.
+  void present_reproject_enable(bool on = true) {
+    check(fr_present_reproject_enable(ctx(), on ? 1 : 0), ctx_, "present_reproject_enable");
+  }
+  uint64_t present_reprojected(int buffer, const fr_present_reproject& rp) {
+    uint64_t t = 0;
+    check(fr_present_enqueue_reprojected(ctx(), buffer, &rp, &t), ctx_, "present_reprojected");
+    return t;
+  }
+  void present_reprojected_to(int buffer, const fr_present_reproject& rp, void* device_dst, size_t bytes) {
+    check(fr_present_enqueue_reprojected_device(ctx(), buffer, &rp, device_dst, bytes), ctx_, "present_reprojected_to");
   }
   void set_normals(const void* nrm, size_t ntris, int where) {  // normals alone; positions and tree stay
     check(fr_set_normals(ctx(), nrm, ntris, where), ctx_, "set_normals");
