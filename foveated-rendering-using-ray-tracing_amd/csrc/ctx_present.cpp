@@ -1,19 +1,19 @@
-// ctx_present.cpp — present: a reconstructed image as packed 8-bit texels, in host memory through a ring of pinned
-// images (fr_present_enable, fr_present_enqueue, fr_present_acquire, fr_present_release) or in the caller's device
-// memory (fr_present_enqueue_device, fr_present_done), in stream order; and the rule on the host (fr_present_pack).
-// The kernel is k_present_pack (k_present.hip); the ring's bookkeeping is PresentRing (present_ring.h).
-// fr_present_enqueue_warped and fr_present_enqueue_warped_device are the same two calls with k_present_warp in the
-// pack's place (a homography between the image and the texels: late reprojection, crop, scale), and
-// fr_present_warp_pack is that rule on the host; the ordering below is theirs unchanged. A warped slot carries
-// ow * oh * 4 bytes to the host, no more. fr_present_enqueue_blended and fr_present_enqueue_blended_device are the same
-// again over a virtual image that mixes two of the images around a gaze point (k_present_blend, k_present_blend_warp;
-// fr_present_blend_pack on the host): the present stream waits as for one image, and the fence of each source is
-// recorded behind the kernel. fr_present_enqueue_reprojected and fr_present_enqueue_reprojected_device are the warped
-// calls with three launches in the kernel's place (launch_present_reproject, k_present_reproject.hip: a clear of the
-// context's key image, a scatter of the source by the frame slot's POSITION, a resolve that falls back to the
-// homography), and fr_present_reproject_pack is that rule on the host. They read POSITION beside the source, so the
-// slot's present_read_shd is recorded behind them whatever the source is: POSITION's next writers (the front stages of
-// the frame that takes the slot next; a stage call, a write or a restore through join_recon) wait for it already.
+// ctx_present.cpp — present: a reconstructed image as packed 8-bit texels, in stream order. Every form goes to host
+// memory through a ring of pinned images (fr_present_enable, fr_present_enqueue*, fr_present_acquire,
+// fr_present_release; the ring's bookkeeping is PresentRing, present_ring.h; a slot carries ow * oh * 4 bytes to the
+// host, no more) or into the caller's device memory (fr_present_enqueue*_device, fr_present_done). One checked Request
+// (check_request) says what to pack, enqueue_pack launches it, and each form's rule runs on the host as well.
+//
+//   form         kernels (k_present.hip, k_present_reproject.hip)         reads                        host rule
+//   Plain        k_present_pack                                           one image                    fr_present_pack
+//   Warped       k_present_warp (late reprojection, crop, scale)          one image                    fr_present_warp_pack
+//   Blended      k_present_blend; k_present_blend_warp with a warp        two, mixed around a gaze     fr_present_blend_pack
+//   Reprojected  a clear of the key image, k_present_splat, _resolve      one image and POSITION       fr_present_reproject_pack
+//
+// The fence recorded behind the kernels is present_read_shd of the frame slot for a source that is the slot's SHADING
+// and present_read for any other; Blended records the fence of each of its sources. Reprojected records
+// present_read_shd whatever the source is: POSITION's next writers (the front stages of the frame that takes the slot
+// next; a stage call, a write or a restore through join_recon) wait for it already.
 //
 // Ordering. A present reads one of the images a frame's last stages write (SIBSON on sibson_stream, PULLPUSH and the
 // A-Trous pair on atrous_stream, the slot's SHADING on the context stream; stage calls and fr_write_buffer write all
@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "ctx_internal.h"
+#include "k_present.h"
 
 using namespace fr;
 using namespace fri;
@@ -93,18 +94,26 @@ bool reproject_ok(const fr_present_reproject* rp, int W, int H, int* ow, int* oh
 }
 const char* const kBadReproject =
     ": the reprojection is NULL, has a non-finite coefficient, or its fallback has one or an output size outside 1..W x 1..H";
-
+const char* const kBadWarp = ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H";
 const char* const kReprojectOff = ": reprojected presents are not enabled (fr_present_reproject_enable)";
 const char* const kBadBlend =
     ": the blend is NULL, has a non-finite gaze or radius, a negative radius, inner > outer, or an outer radius whose "
     "square is not finite";
+const char* const kRingOff = ": presenting is not enabled (fr_present_enable)";
 
-// What a present packs: one image, or (blended) the virtual image that mixes `phys` (inner) and `outer` by `blend`.
-struct Source {
+enum class Form { Plain, Warped, Blended, Reprojected };
+
+// A checked present: the physical image to pack, or (Blended) the two that `blend` mixes, `phys` inside; h: the
+// homography (Warped, Reprojected: the fallback; Blended: when a warp was given), else NULL; vp: Reprojected only;
+// ow x oh: the output. h and vp point into the caller's structs: the launches copy them, nothing is read after the call.
+struct Request {
+  Form form = Form::Plain;
   int phys = -1, outer = -1;
-  bool blended = false;
   PresentBlend blend{};
+  const float *h = nullptr, *vp = nullptr;
+  int ow = 0, oh = 0;
 };
+struct DeviceDst { void* ptr; size_t bytes; };  // where a device form writes; the host forms have none
 
 // The stream, the events and the fences, once; then the images of slots made .. slots - 1. All or nothing.
 bool make_ring(fr_ctx* c, int slots) {
@@ -128,74 +137,84 @@ bool make_ring(fr_ctx* c, int slots) {
   return ok;
 }
 
-// What both enqueue forms refuse before anything is enqueued. src: the image to pack, resolved here from buffer_id, or
-// (blend given: blended, with its parameters checked by the caller) the two images from the blend's ids.
-int check_enqueue(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, Source* src) {
-  src->phys = presentable(c, blend ? blend->inner_buffer : buffer_id);
-  src->outer = blend ? presentable(c, blend->outer_buffer) : src->phys;
-  if (src->phys < 0 || src->outer < 0)
+// What every enqueue refuses before anything is enqueued, and *req from what it takes. The order of the refusals is
+// part of the interface, the same for the eight entry points: 1. a NULL context or ticket (the callers, before this);
+// 2. the reprojection (Reprojected) or the warp (Warped; Blended when one is given); 3. device forms only (dev):
+// device_dst, then bytes; 4. the blend (Blended; buffer_id is not used, the images are the blend's); 5. the buffer
+// ids; 6. a rank of a group, or sharded; 7. the ring is off; 8. reprojected presents are not enabled (Reprojected);
+// 9. every slot of the ring is held (enqueue_host, after this).
+int check_request(fr_ctx* c, const std::string& name, Form form, int buffer_id, const fr_present_blend* blend,
+                  const fr_present_warp* warp, const fr_present_reproject* rp, const DeviceDst* dev, Request* req) {
+  req->form = form;
+  req->ow = c->W;
+  req->oh = c->H;
+  if (form == Form::Reprojected) {
+    if (!reproject_ok(rp, c->W, c->H, &req->ow, &req->oh)) return fail(c, FR_E_INVALID, name + kBadReproject);
+    req->vp = rp->vp;
+    req->h = rp->fallback.h;
+  } else if (form == Form::Warped || (form == Form::Blended && warp)) {
+    if (!warp_ok(warp, c->W, c->H, &req->ow, &req->oh)) return fail(c, FR_E_INVALID, name + kBadWarp);
+    req->h = warp->h;
+  }
+  if (dev) {
+    if (!dev->ptr || (reinterpret_cast<uintptr_t>(dev->ptr) & 15u))
+      return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
+    if (dev->bytes != (size_t)req->ow * req->oh * 4) return fail(c, FR_E_INVALID, name + ": bytes != the output's width * height * 4");
+  }
+  const bool blended = form == Form::Blended;
+  if (blended && !blend_ok(blend, &req->blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
+  req->phys = presentable(c, blended ? blend->inner_buffer : buffer_id);
+  req->outer = blended ? presentable(c, blend->outer_buffer) : req->phys;
+  if (req->phys < 0 || req->outer < 0)
     return fail(c, FR_E_INVALID, name + ": the buffer is not FR_BUF_SHADING, FR_BUF_SIBSON, FR_BUF_PULLPUSH or FR_BUF_ATROUS");
   if (c->group_refs > 0 || c->U.shard_count > 1)
     return fail(c, FR_E_UNSUPPORTED, name + ": the context is a rank of a group or sharded");
-  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
+  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, name + kRingOff);
+  if (form == Form::Reprojected && !c->present.reproject) return fail(c, FR_E_STATE, name + kReprojectOff);
   return FR_OK;
 }
 
 // The present stream behind what wrote the image (the head of this file), then the pack into dst, then the fence
-// its next writer waits for: of each source, when the present blends two. begin / packed: a slot's timing events, or
-// NULL. warp: NULL for the plain pack, else the checked homography with its output size ow x oh (the kernels take warp
-// and blend by value: nothing is read after the call). rp: the checked reprojection, whose fallback `warp` then is.
-int enqueue_pack(fr_ctx* c, const Source& src, const fr_present_reproject* rp, const fr_present_warp* warp, int ow, int oh,
-                 void* dst, hipEvent_t begin, hipEvent_t packed) {
+// its next writer waits for (the table at the head of this file). begin / packed: a slot's timing events, or NULL.
+int enqueue_pack(fr_ctx* c, const Request& req, void* dst, hipEvent_t begin, hipEvent_t packed) {
   fr_ctx::Present& P = c->present;
   HIP_TRY(c, hipEventRecord(P.ev_fork, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(P.stream, P.ev_fork, 0));
   for (const Fence& f : c->recon_done) HIP_TRY(c, f.peek(P.stream));
   if (begin) HIP_TRY(c, hipEventRecord(begin, P.stream));
-  if (rp)
-    launch_present_reproject(c->img[src.phys], c->img[P_pos(c)], c->W, c->H, P.format, rp->vp, warp->h, ow, oh, P.keys, dst,
-                             P.stream);
-  else if (src.blended)
-    launch_present_blend(c->img[src.phys], c->img[src.outer], c->W, c->H, P.format, src.blend, warp ? warp->h : nullptr, ow, oh,
-                         dst, P.stream);
-  else if (warp)
-    launch_present_warp(c->img[src.phys], c->W, c->H, P.format, warp->h, ow, oh, dst, P.stream);
-  else
-    launch_present_pack(c->img[src.phys], c->W, c->H, P.format, dst, P.stream);
+  const f4* src = c->img[req.phys];
+  switch (req.form) {
+    case Form::Plain: launch_present_pack(src, c->W, c->H, P.format, dst, P.stream); break;
+    case Form::Warped: launch_present_warp(src, c->W, c->H, P.format, req.h, req.ow, req.oh, dst, P.stream); break;
+    case Form::Blended:
+      launch_present_blend(src, c->img[req.outer], c->W, c->H, P.format, req.blend, req.h, req.ow, req.oh, dst, P.stream);
+      break;
+    case Form::Reprojected:
+      launch_present_reproject(src, c->img[P_pos(c)], c->W, c->H, P.format, req.vp, req.h, req.ow, req.oh, P.keys, dst, P.stream);
+      break;
+  }
   if (int rc = check_launch(c)) return rc;
   if (packed) HIP_TRY(c, hipEventRecord(packed, P.stream));
   const int shd = P_shd(c);
-  if (rp || src.phys == shd || src.outer == shd) HIP_TRY(c, c->present_read_shd[c->slot].record(P.stream));
-  if (src.phys != shd || src.outer != shd) HIP_TRY(c, c->present_read.record(P.stream));
+  if (req.form == Form::Reprojected || req.phys == shd || req.outer == shd) HIP_TRY(c, c->present_read_shd[c->slot].record(P.stream));
+  if (req.phys != shd || req.outer != shd) HIP_TRY(c, c->present_read.record(P.stream));
   return FR_OK;
 }
 
-// fr_present_enqueue (warp NULL), fr_present_enqueue_warped and (blended: the sources are the blend's, buffer_id is not
-// used) fr_present_enqueue_blended: into the next free slot and on to its pinned image. reproject:
-// fr_present_enqueue_reprojected, the warp is rp's fallback.
-int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
-                 const fr_present_warp* warp, bool warped, uint64_t* ticket, const fr_present_reproject* rp = nullptr,
-                 bool reproject = false) {
+// The host forms: into the next free slot and on to its pinned image.
+int enqueue_host(fr_ctx* c, const std::string& name, Form form, int buffer_id, const fr_present_blend* blend,
+                 const fr_present_warp* warp, const fr_present_reproject* rp, uint64_t* ticket) {
   if (!c || !ticket) return FR_E_INVALID;
-  int ow = c->W, oh = c->H;
-  if (reproject) {
-    if (!reproject_ok(rp, c->W, c->H, &ow, &oh)) return fail(c, FR_E_INVALID, name + kBadReproject);
-    warp = &rp->fallback;
-  } else if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
-    return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
-  Source src;
-  if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
-  if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
+  Request req;
+  if (int rc = check_request(c, name, form, buffer_id, blend, warp, rp, nullptr, &req)) return rc;
   fr_ctx::Present& P = c->present;
-  if (reproject && !P.reproject) return fail(c, FR_E_STATE, name + kReprojectOff);
   uint64_t t = 0;
   const int s = P.ring.enqueue(&t);
   if (s < 0) return fail(c, FR_E_STATE, name + ": every slot of the ring is held (fr_present_release)");
   hipSetDevice(c->cfg.device);
   // (the slot's last copy is earlier work of the present stream: the pack overwrites the staging image behind it)
-  int rc = enqueue_pack(c, src, reproject ? rp : nullptr, warped || reproject ? warp : nullptr, ow, oh, P.stage[s],
-                        P.ev[s].begin, P.ev[s].packed);
-  if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], (size_t)ow * oh * 4, hipMemcpyDeviceToHost, P.stream) != hipSuccess)
+  int rc = enqueue_pack(c, req, P.stage[s], P.ev[s].begin, P.ev[s].packed);
+  if (rc == FR_OK && hipMemcpyAsync(P.host[s], P.stage[s], (size_t)req.ow * req.oh * 4, hipMemcpyDeviceToHost, P.stream) != hipSuccess)
     rc = fail(c, FR_E_HIP, name + ": the copy to the host could not be enqueued");
   if (rc == FR_OK && hipEventRecord(P.ev[s].done, P.stream) != hipSuccess) rc = fail(c, FR_E_HIP, name + ": event record failed");
   if (rc != FR_OK) {
@@ -206,31 +225,53 @@ int enqueue_host(fr_ctx* c, const std::string& name, int buffer_id, const fr_pre
   return FR_OK;
 }
 
-// fr_present_enqueue_device (warp NULL), fr_present_enqueue_warped_device and (blended) fr_present_enqueue_blended_device:
-// straight into the caller's memory. reproject: fr_present_enqueue_reprojected_device, the warp is rp's fallback.
-int enqueue_device(fr_ctx* c, const std::string& name, int buffer_id, const fr_present_blend* blend, bool blended,
-                   const fr_present_warp* warp, bool warped, void* device_dst, size_t bytes,
-                   const fr_present_reproject* rp = nullptr, bool reproject = false) {
+// The device forms: straight into the caller's memory, with the fence fr_present_done hands on.
+int enqueue_device(fr_ctx* c, const std::string& name, Form form, int buffer_id, const fr_present_blend* blend,
+                   const fr_present_warp* warp, const fr_present_reproject* rp, void* device_dst, size_t bytes) {
   if (!c) return FR_E_INVALID;
-  int ow = c->W, oh = c->H;
-  if (reproject) {
-    if (!reproject_ok(rp, c->W, c->H, &ow, &oh)) return fail(c, FR_E_INVALID, name + kBadReproject);
-    warp = &rp->fallback;
-  } else if (warped && !warp_ok(warp, c->W, c->H, &ow, &oh))
-    return fail(c, FR_E_INVALID, name + ": the warp is NULL, has a non-finite coefficient or an output size outside 1..W x 1..H");
-  if (!device_dst || (reinterpret_cast<uintptr_t>(device_dst) & 15u))
-    return fail(c, FR_E_INVALID, name + ": device_dst is NULL or not 16-byte aligned");
-  if (bytes != (size_t)ow * oh * 4) return fail(c, FR_E_INVALID, name + ": bytes != the output's width * height * 4");
-  Source src;
-  if ((src.blended = blended) && !blend_ok(blend, &src.blend)) return fail(c, FR_E_INVALID, name + kBadBlend);
-  if (int rc = check_enqueue(c, name, buffer_id, blended ? blend : nullptr, &src)) return rc;
-  if (reproject && !c->present.reproject) return fail(c, FR_E_STATE, name + kReprojectOff);
+  const DeviceDst dev{device_dst, bytes};
+  Request req;
+  if (int rc = check_request(c, name, form, buffer_id, blend, warp, rp, &dev, &req)) return rc;
   hipSetDevice(c->cfg.device);
-  if (int rc = enqueue_pack(c, src, reproject ? rp : nullptr, warped || reproject ? warp : nullptr, ow, oh, device_dst, nullptr,
-                            nullptr))
-    return rc;
+  if (int rc = enqueue_pack(c, req, device_dst, nullptr, nullptr)) return rc;
   HIP_TRY(c, c->present_dev.record(c->present.stream));
   return FR_OK;
+}
+
+// The slot of a ticket of the ring in place, for the calls that take one.
+int slot_of(fr_ctx* c, const std::string& name, uint64_t ticket, int* s) {
+  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, name + kRingOff);
+  *s = c->present.ring.find(ticket);
+  if (*s < 0) return fail(c, FR_E_INVALID, name + ": unknown or released ticket");
+  return FR_OK;
+}
+
+// What every host rule refuses: a NULL image or output, a size outside 1..32767, an unknown format.
+bool rule_args_ok(int width, int height, int format, std::initializer_list<const void*> pointers) {
+  for (const void* p : pointers) if (!p) return false;
+  return width >= 1 && height >= 1 && width <= 32767 && height <= 32767 && format_ok(format);
+}
+
+// An RGBA32F image of `width` texels a row as the rules of fr_math.h fetch it.
+auto image_fetch(const float* img, int width) {
+  return [img, width](int i, int row) {
+    const float* t = img + ((size_t)row * width + i) * 4;
+    return mk4(t[0], t[1], t[2], t[3]);
+  };
+}
+
+// The output side of every host rule: word(x, y) of image row y = r, or oh - 1 - r (top_down), as the four bytes of
+// texel x of output row r.
+template <class Word>
+void pack_rows(int ow, int oh, bool top_down, uint8_t* out, Word word) {
+  for (int r = 0; r < oh; r++) {
+    const int y = top_down ? oh - 1 - r : r;
+    uint8_t* o = out + (size_t)r * ow * 4;
+    for (int x = 0; x < ow; x++) {
+      const uint32_t w = word(x, y);
+      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
+    }
+  }
 }
 }  // namespace
 
@@ -270,36 +311,20 @@ void present_destroy(fr_ctx* c) {
 extern "C" {
 
 int fr_present_pack(const float* rgba, int width, int height, int format, uint8_t* out) {
-  if (!rgba || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format)) return FR_E_INVALID;
-  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
-  for (int r = 0; r < height; r++) {
-    const float* in = rgba + (size_t)(top_down ? height - 1 - r : r) * width * 4;
-    uint8_t* o = out + (size_t)r * width * 4;
-    for (int x = 0; x < width; x++) {
-      const uint32_t w = present_texel(mk4(in[4 * x], in[4 * x + 1], in[4 * x + 2], in[4 * x + 3]), bgra);
-      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
-    }
-  }
+  if (!rule_args_ok(width, height, format, {rgba, out})) return FR_E_INVALID;
+  const PresentFormat f = present_format(format);
+  const auto fetch = image_fetch(rgba, width);
+  pack_rows(width, height, f.top_down, out, [&](int x, int y) { return present_texel(fetch(x, y), f.bgra); });
   return FR_OK;
 }
 
 int fr_present_warp_pack(const float* rgba, int width, int height, int format, const fr_present_warp* warp, uint8_t* out) {
-  if (!rgba || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format)) return FR_E_INVALID;
+  if (!rule_args_ok(width, height, format, {rgba, out})) return FR_E_INVALID;
   int ow, oh;
   if (!warp_ok(warp, width, height, &ow, &oh)) return FR_E_INVALID;
-  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
-  const auto fetch = [rgba, width](int i, int row) {
-    const float* t = rgba + ((size_t)row * width + i) * 4;
-    return mk4(t[0], t[1], t[2], t[3]);
-  };
-  for (int r = 0; r < oh; r++) {
-    const int y = top_down ? oh - 1 - r : r;
-    uint8_t* o = out + (size_t)r * ow * 4;
-    for (int x = 0; x < ow; x++) {
-      const uint32_t w = present_warp_texel(fetch, width, height, warp->h, x, y, bgra);
-      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
-    }
-  }
+  const PresentFormat f = present_format(format);
+  const auto fetch = image_fetch(rgba, width);
+  pack_rows(ow, oh, f.top_down, out, [&](int x, int y) { return present_warp_texel(fetch, width, height, warp->h, x, y, f.bgra); });
   return FR_OK;
 }
 
@@ -324,20 +349,19 @@ int fr_present_enable(fr_ctx* c, int slots, int format) {
 }
 
 int fr_present_enqueue(fr_ctx* c, int buffer_id, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue", buffer_id, nullptr, false, nullptr, false, ticket);
+  return enqueue_host(c, "fr_present_enqueue", Form::Plain, buffer_id, nullptr, nullptr, nullptr, ticket);
 }
 
 int fr_present_enqueue_warped(fr_ctx* c, int buffer_id, const fr_present_warp* warp, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue_warped", buffer_id, nullptr, false, warp, true, ticket);
+  return enqueue_host(c, "fr_present_enqueue_warped", Form::Warped, buffer_id, nullptr, warp, nullptr, ticket);
 }
 
 int fr_present_acquire(fr_ctx* c, uint64_t ticket, int wait, const void** host) {
   if (!c || !host) return FR_E_INVALID;
   const std::string name = "fr_present_acquire";
   fr_ctx::Present& P = c->present;
-  if (P.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
-  const int s = P.ring.find(ticket);
-  if (s < 0) return fail(c, FR_E_INVALID, name + ": unknown or released ticket");
+  int s;
+  if (int rc = slot_of(c, name, ticket, &s)) return rc;
   if (P.ring.state[s] != PresentRing::HELD) {
     hipSetDevice(c->cfg.device);
     const hipError_t e = wait ? hipEventSynchronize(P.ev[s].done) : hipEventQuery(P.ev[s].done);
@@ -351,20 +375,17 @@ int fr_present_acquire(fr_ctx* c, uint64_t ticket, int wait, const void** host) 
 
 int fr_present_release(fr_ctx* c, uint64_t ticket) {
   if (!c) return FR_E_INVALID;
-  fr_ctx::Present& P = c->present;
-  if (P.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_release: presenting is not enabled (fr_present_enable)");
-  const int s = P.ring.find(ticket);
-  if (s < 0) return fail(c, FR_E_INVALID, "fr_present_release: unknown or released ticket");
-  P.ring.release(s);
+  int s;
+  if (int rc = slot_of(c, "fr_present_release", ticket, &s)) return rc;
+  c->present.ring.release(s);
   return FR_OK;
 }
 
 int fr_present_times(fr_ctx* c, uint64_t ticket, float* pack_ms, float* copy_ms) {
   if (!c) return FR_E_INVALID;
   fr_ctx::Present& P = c->present;
-  if (P.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_times: presenting is not enabled (fr_present_enable)");
-  const int s = P.ring.find(ticket);
-  if (s < 0) return fail(c, FR_E_INVALID, "fr_present_times: unknown or released ticket");
+  int s;
+  if (int rc = slot_of(c, "fr_present_times", ticket, &s)) return rc;
   if (P.ring.state[s] != PresentRing::HELD) return fail(c, FR_E_STATE, "fr_present_times: the ticket is not acquired");
   hipSetDevice(c->cfg.device);
   float a = 0.0f, b = 0.0f;
@@ -376,11 +397,11 @@ int fr_present_times(fr_ctx* c, uint64_t ticket, float* pack_ms, float* copy_ms)
 }
 
 int fr_present_enqueue_device(fr_ctx* c, int buffer_id, void* device_dst, size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_device", buffer_id, nullptr, false, nullptr, false, device_dst, bytes);
+  return enqueue_device(c, "fr_present_enqueue_device", Form::Plain, buffer_id, nullptr, nullptr, nullptr, device_dst, bytes);
 }
 
 int fr_present_enqueue_warped_device(fr_ctx* c, int buffer_id, const fr_present_warp* warp, void* device_dst, size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_warped_device", buffer_id, nullptr, false, warp, true, device_dst, bytes);
+  return enqueue_device(c, "fr_present_enqueue_warped_device", Form::Warped, buffer_id, nullptr, warp, nullptr, device_dst, bytes);
 }
 
 int fr_present_blend_default(fr_ctx* c, fr_present_blend* blend) {
@@ -396,75 +417,52 @@ int fr_present_blend_default(fr_ctx* c, fr_present_blend* blend) {
 
 int fr_present_blend_pack(const float* inner, const float* outer, int width, int height, int format,
                           const fr_present_blend* blend, const fr_present_warp* warp, uint8_t* out) {
-  if (!inner || !outer || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format))
-    return FR_E_INVALID;
+  if (!rule_args_ok(width, height, format, {inner, outer, out})) return FR_E_INVALID;
   int ow = width, oh = height;
   if (warp && !warp_ok(warp, width, height, &ow, &oh)) return FR_E_INVALID;
   PresentBlend b;
   if (!blend_ok(blend, &b)) return FR_E_INVALID;
-  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
-  const auto texel = [width](const float* img) {
-    return [img, width](int i, int row) {
-      const float* t = img + ((size_t)row * width + i) * 4;
-      return mk4(t[0], t[1], t[2], t[3]);
-    };
-  };
-  const auto fi = texel(inner), fo = texel(outer);
+  const PresentFormat f = present_format(format);
+  const auto fi = image_fetch(inner, width), fo = image_fetch(outer, width);
   const auto fetch = [&fi, &fo, &b](int i, int row) { return present_blend_fetch(fi, fo, i, row, b); };
-  for (int r = 0; r < oh; r++) {
-    const int y = top_down ? oh - 1 - r : r;
-    uint8_t* o = out + (size_t)r * ow * 4;
-    for (int x = 0; x < ow; x++) {
-      const uint32_t w = warp ? present_warp_texel(fetch, width, height, warp->h, x, y, bgra) : present_texel(fetch(x, y), bgra);
-      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
-    }
-  }
+  pack_rows(ow, oh, f.top_down, out, [&](int x, int y) {
+    return warp ? present_warp_texel(fetch, width, height, warp->h, x, y, f.bgra) : present_texel(fetch(x, y), f.bgra);
+  });
   return FR_OK;
 }
 
 int fr_present_enqueue_blended(fr_ctx* c, const fr_present_blend* blend, const fr_present_warp* warp, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue_blended", 0, blend, true, warp, warp != nullptr, ticket);
+  return enqueue_host(c, "fr_present_enqueue_blended", Form::Blended, 0, blend, warp, nullptr, ticket);
 }
 
 int fr_present_enqueue_blended_device(fr_ctx* c, const fr_present_blend* blend, const fr_present_warp* warp, void* device_dst,
                                       size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_blended_device", 0, blend, true, warp, warp != nullptr, device_dst, bytes);
+  return enqueue_device(c, "fr_present_enqueue_blended_device", Form::Blended, 0, blend, warp, nullptr, device_dst, bytes);
 }
 
 int fr_present_reproject_pack(const float* rgba, const float* position, int width, int height, int format,
                               const fr_present_reproject* rp, uint8_t* out) {
-  if (!rgba || !position || !out || width < 1 || height < 1 || width > 32767 || height > 32767 || !format_ok(format))
-    return FR_E_INVALID;
+  if (!rule_args_ok(width, height, format, {rgba, position, out})) return FR_E_INVALID;
   int ow, oh;
   if (!reproject_ok(rp, width, height, &ow, &oh)) return FR_E_INVALID;
-  const bool bgra = (format & ~FR_PRESENT_TOP_DOWN) == FR_PRESENT_BGRA8, top_down = (format & FR_PRESENT_TOP_DOWN) != 0;
-  const auto texel = [width](const float* img) {
-    return [img, width](int i, int row) {
-      const float* t = img + ((size_t)row * width + i) * 4;
-      return mk4(t[0], t[1], t[2], t[3]);
-    };
-  };
-  const auto fetch = texel(rgba), fpos = texel(position);
+  const PresentFormat f = present_format(format);
+  const auto fetch = image_fetch(rgba, width), fpos = image_fetch(position, width);
   std::vector<uint64_t> keys((size_t)ow * oh, PRESENT_KEY_EMPTY);  // the clear
   for (int j = 0; j < height; j++)                                   // the splat
     for (int i = 0; i < width; i++) {
       int ox, oy;
       uint32_t depth;
       if (!present_splat_place(fpos(i, j), rp->vp, ow, oh, &ox, &oy, &depth)) continue;
-      const uint64_t key = present_splat_key(depth, present_texel(fetch(i, j), bgra));
+      const uint64_t key = present_splat_key(depth, present_texel(fetch(i, j), f.bgra));
       uint64_t& k = keys[(size_t)oy * ow + ox];
       if (key < k) k = key;
     }
   const auto key = [&keys, ow](int i, int row) { return keys[(size_t)row * ow + i]; };
-  for (int r = 0; r < oh; r++) {  // the resolve
-    const int y = top_down ? oh - 1 - r : r;
-    uint8_t* o = out + (size_t)r * ow * 4;
-    for (int x = 0; x < ow; x++) {
-      uint32_t w;
-      if (!present_resolve_word(key(x, y), key, ow, oh, x, y, &w)) w = present_warp_texel(fetch, width, height, rp->fallback.h, x, y, bgra);
-      o[4 * x] = (uint8_t)w; o[4 * x + 1] = (uint8_t)(w >> 8); o[4 * x + 2] = (uint8_t)(w >> 16); o[4 * x + 3] = (uint8_t)(w >> 24);
-    }
-  }
+  pack_rows(ow, oh, f.top_down, out, [&](int x, int y) {  // the resolve
+    uint32_t w;
+    if (!present_resolve_word(key(x, y), key, ow, oh, x, y, &w)) w = present_warp_texel(fetch, width, height, rp->fallback.h, x, y, f.bgra);
+    return w;
+  });
   return FR_OK;
 }
 
@@ -476,7 +474,7 @@ int fr_present_reproject_enable(fr_ctx* c, int on) {
     P.reproject = false;
     return FR_OK;
   }
-  if (P.ring.n == 0) return fail(c, FR_E_STATE, name + ": presenting is not enabled (fr_present_enable)");
+  if (P.ring.n == 0) return fail(c, FR_E_STATE, name + kRingOff);
   if (!P.keys) {
     if (int rc = quiesce(c)) return rc;
     if (int rc = present_sync(c)) return rc;
@@ -493,18 +491,18 @@ int fr_present_reproject_enable(fr_ctx* c, int on) {
 }
 
 int fr_present_enqueue_reprojected(fr_ctx* c, int buffer_id, const fr_present_reproject* rp, uint64_t* ticket) {
-  return enqueue_host(c, "fr_present_enqueue_reprojected", buffer_id, nullptr, false, nullptr, false, ticket, rp, true);
+  return enqueue_host(c, "fr_present_enqueue_reprojected", Form::Reprojected, buffer_id, nullptr, nullptr, rp, ticket);
 }
 
 int fr_present_enqueue_reprojected_device(fr_ctx* c, int buffer_id, const fr_present_reproject* rp, void* device_dst,
                                           size_t bytes) {
-  return enqueue_device(c, "fr_present_enqueue_reprojected_device", buffer_id, nullptr, false, nullptr, false, device_dst,
-                        bytes, rp, true);
+  return enqueue_device(c, "fr_present_enqueue_reprojected_device", Form::Reprojected, buffer_id, nullptr, nullptr, rp, device_dst,
+                        bytes);
 }
 
 int fr_present_done(fr_ctx* c, void* stream) {
   if (!c) return FR_E_INVALID;
-  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, "fr_present_done: presenting is not enabled (fr_present_enable)");
+  if (c->present.ring.n == 0) return fail(c, FR_E_STATE, std::string("fr_present_done") + kRingOff);
   if (!c->present_dev.pending) return FR_OK;
   hipSetDevice(c->cfg.device);
   HIP_TRY(c, c->present_dev.peek(static_cast<hipStream_t>(stream)));

@@ -7,13 +7,10 @@
 // travels by value in the kernels' arguments. No LDS, no scratch.
 #include <hip/hip_runtime.h>
 
-#include "fr_device.h"
 #include "k_launch.h"
+#include "k_present.h"
 
 namespace fr {
-
-#define REPROJECT_BX 64  // lanes along a row: one wave per block row
-#define REPROJECT_BY 4   // rows per block
 
 struct SplatArgs {
   float vp[16];
@@ -29,11 +26,11 @@ struct SplatArgs {
 // segments and few lanes share a key (several to one only where the display camera is farther away or a surface is
 // seen at a flatter angle). ox, oy are inside the ow x oh output by present_splat_place's test, and ow * oh <= W * H
 // keys are allocated.
-__global__ __launch_bounds__(REPROJECT_BX* REPROJECT_BY) void k_present_splat(const f4* __restrict__ src,
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_splat(const f4* __restrict__ src,
                                                                               const f4* __restrict__ pos, const SplatArgs a,
                                                                               unsigned long long* __restrict__ keys) {
-  const int i = (int)(blockIdx.x * REPROJECT_BX + threadIdx.x);
-  const int j = (int)(blockIdx.y * REPROJECT_BY + threadIdx.y);
+  const int i = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int j = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
   if (i >= a.W || j >= a.H) return;
   const size_t at = (size_t)j * a.W + i;
   const f4 p = pos[at];
@@ -45,24 +42,15 @@ __global__ __launch_bounds__(REPROJECT_BX* REPROJECT_BY) void k_present_splat(co
   (void)atomicMin(keys + ((size_t)oy * a.ow + ox), key);
 }
 
-struct ResolveArgs {
-  float h[9];
-  int W, H, ow, oh, lanes;  // lanes = ceil(ow / 4)
-  bool bgra, top_down;
-};
-
-// k_present_pack's shape on the ow x oh output: one lane per four consecutive texels of one output row, one 16-byte
-// store when ow is a multiple of four (ALIGNED), word stores otherwise, the last lane of a row taking the ow & 3
-// texels left. A lane loads its four keys (32 contiguous bytes) together, before the first of them is looked at; a
-// texel reads its four neighbours only where its own key is empty (one of the lane's own where it is one), and the
-// source through the fallback homography only where the crack rule fails as well.
-template <bool ALIGNED>
-__global__ __launch_bounds__(REPROJECT_BX* REPROJECT_BY) void k_present_resolve(const f4* __restrict__ src,
-                                                                                const unsigned long long* __restrict__ keys,
-                                                                                const ResolveArgs a,
-                                                                                uint32_t* __restrict__ out) {
-  const int j = (int)(blockIdx.x * REPROJECT_BX + threadIdx.x);
-  const int r = (int)(blockIdx.y * REPROJECT_BY + threadIdx.y);
+// The output side of k_present.h on the ow x oh output, written out. A full lane loads its four keys (32 contiguous bytes) together,
+// before the first of them is looked at; a texel reads its four neighbours only where its own key is empty (one of the
+// lane's own where it is one), and the source through the fallback homography only where the crack rule fails as well.
+__global__ __launch_bounds__(PRESENT_BX* PRESENT_BY) void k_present_resolve(const f4* __restrict__ src,
+                                                                            const unsigned long long* __restrict__ keys,
+                                                                            const WarpArgs a, uint32_t* __restrict__ out) {
+  // (present_lane's steps in place: through the descriptor the compiler took one more scalar register)
+  const int j = (int)(blockIdx.x * PRESENT_BX + threadIdx.x);
+  const int r = (int)(blockIdx.y * PRESENT_BY + threadIdx.y);
   if (j >= a.lanes || r >= a.oh) return;
   const int x = 4 * j;
   const int y = a.top_down ? a.oh - 1 - r : r;
@@ -91,39 +79,24 @@ __global__ __launch_bounds__(REPROJECT_BX* REPROJECT_BY) void k_present_resolve(
       if (present_resolve_word(c, own, ow, a.oh, xx, y, &w)) return w;
       return present_warp_texel(fetch, W, a.H, a.h, xx, y, a.bgra);
     };
-    const uint4 q = make_uint4(texel4(c0, x), texel4(c1, x + 1), texel4(c2, x + 2), texel4(c3, x + 3));
-    if (ALIGNED) {
-      *reinterpret_cast<uint4*>(o) = q;
-    } else {
-      o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
-    }
+    present_store(o, make_uint4(texel4(c0, x), texel4(c1, x + 1), texel4(c2, x + 2), texel4(c3, x + 3)));
   } else {
     for (int k = 0; x + k < ow; k++) o[k] = texel(key(x + k, y), x + k);
   }
 }
 
-// format as launch_present_pack; the callers have checked the sizes (1 <= ow <= W <= 32767, 1 <= oh <= H <= 32767, so
-// both grids' y extents are at most 8192), vp and h. keys: W * H keys, 8-byte aligned; out: ow * oh words, 16-byte
-// aligned.
+// format as launch_present_pack; the callers have checked the sizes (1 <= ow <= W <= 32767, 1 <= oh <= H <= 32767), vp
+// and h. keys: W * H keys, 8-byte aligned; out: ow * oh words, 16-byte aligned.
 void launch_present_reproject(const f4* src, const f4* pos, int W, int H, int format, const float* vp, const float* h,
                               int ow, int oh, unsigned long long* keys, void* out, hipStream_t stream) {
-  const bool bgra = (format & 0xFF) == 1, top_down = (format & 0x100) != 0;
-  const dim3 block(REPROJECT_BX, REPROJECT_BY);
   if (hipMemsetAsync(keys, 0xFF, (size_t)ow * oh * sizeof(unsigned long long), stream) != hipSuccess) return;
+  const WarpArgs a = warp_args(h, W, H, ow, oh, format);
   SplatArgs s;
   for (int k = 0; k < 16; k++) s.vp[k] = vp[k];
-  s.W = W; s.H = H; s.ow = ow; s.oh = oh; s.bgra = bgra;
-  const dim3 sgrid((unsigned)((W + REPROJECT_BX - 1) / REPROJECT_BX), (unsigned)((H + REPROJECT_BY - 1) / REPROJECT_BY));
-  hipLaunchKernelGGL(k_present_splat, sgrid, block, 0, stream, src, pos, s, keys);
-  ResolveArgs a;
-  for (int k = 0; k < 9; k++) a.h[k] = h[k];
-  a.W = W; a.H = H; a.ow = ow; a.oh = oh; a.lanes = (ow + 3) / 4;
-  a.bgra = bgra; a.top_down = top_down;
-  const dim3 rgrid((unsigned)((a.lanes + REPROJECT_BX - 1) / REPROJECT_BX), (unsigned)((oh + REPROJECT_BY - 1) / REPROJECT_BY));
-  if ((ow & 3) == 0)
-    hipLaunchKernelGGL(k_present_resolve<true>, rgrid, block, 0, stream, src, keys, a, static_cast<uint32_t*>(out));
-  else
-    hipLaunchKernelGGL(k_present_resolve<false>, rgrid, block, 0, stream, src, keys, a, static_cast<uint32_t*>(out));
+  s.W = W; s.H = H; s.ow = ow; s.oh = oh; s.bgra = a.bgra;
+  hipLaunchKernelGGL(k_present_splat, present_grid(W, H), present_block(), 0, stream, src, pos, s, keys);
+  hipLaunchKernelGGL(k_present_resolve, present_grid(a.lanes, oh), present_block(), 0, stream, src, keys, a,
+                     static_cast<uint32_t*>(out));
 }
 
 }  // namespace fr

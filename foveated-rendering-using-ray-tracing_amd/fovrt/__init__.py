@@ -494,6 +494,7 @@ class PathTracer:
     def __init__(self, config: Config | None = None):
         self.config = config or Config()
         self._ctx = None
+        self._ticket_shapes = {}  # (rows, columns) of the present tickets whose image is not the screen's
 
     # bool initialize(int w, int h)
     def initialize(self, width=None, height=None):
@@ -1094,13 +1095,20 @@ class PathTracer:
         (FR_PRESENT_RGBA8 or FR_PRESENT_BGRA8, FR_PRESENT_TOP_DOWN or-ed in); slots=0 turns presenting off."""
         self._check(_lib.fr_present_enable(self._ctx, int(slots), int(format)))
 
+    def _present_ticket(self, enqueue, *args, shape=None) -> int:
+        """enqueue(ctx, *args, &ticket), checked; `shape`: what present_acquire gives the ticket's image (rows, columns)
+        when that is not the screen's. Returns the ticket."""
+        t = C.c_uint64()
+        self._check(enqueue(self._ctx, *args, C.byref(t)))
+        if shape is not None:
+            self._ticket_shapes[t.value] = shape
+        return t.value
+
     def present(self, buffer) -> int:
         """fr_present_enqueue: the buffer (SHADING, SIBSON, PULLPUSH or ATROUS) as it stands at this place of the
         stream order, on its way to the host without waiting for the GPU; returns the ticket. FovrtError with
         FR_E_STATE when every slot is held."""
-        t = C.c_uint64()
-        self._check(_lib.fr_present_enqueue(self._ctx, int(buffer), C.byref(t)))
-        return t.value
+        return self._present_ticket(_lib.fr_present_enqueue, int(buffer))
 
     def present_acquire(self, ticket, wait=True):
         """fr_present_acquire: the frame of `ticket` as an (H, W, 4) uint8 view over the slot's pinned image, valid
@@ -1110,7 +1118,7 @@ class PathTracer:
         if rc == FR_PRESENT_PENDING:
             return None
         self._check(rc)
-        h, w = self.__dict__.get("_warped_shapes", {}).get(int(ticket), (self.height, self.width))
+        h, w = self._ticket_shapes.get(int(ticket), (self.height, self.width))
         buf = (C.c_uint8 * (w * h * 4)).from_address(p.value)
         a = np.frombuffer(buf, np.uint8).reshape(h, w, 4)
         a.flags.writeable = False
@@ -1119,15 +1127,13 @@ class PathTracer:
     def present_release(self, ticket):
         """fr_present_release: the slot of `ticket` is free again (acquired or not); its view is no longer valid."""
         self._check(_lib.fr_present_release(self._ctx, int(ticket)))
-        self.__dict__.get("_warped_shapes", {}).pop(int(ticket), None)
+        self._ticket_shapes.pop(int(ticket), None)
 
     def present_warped(self, buffer, warp) -> int:
         """fr_present_enqueue_warped: as present(), through the homography `warp` (a PresentWarp): late reprojection,
         crop or scale. present_acquire gives the ticket's image in the warp's output shape."""
-        t = C.c_uint64()
-        self._check(_lib.fr_present_enqueue_warped(self._ctx, int(buffer), C.byref(warp.c_struct()), C.byref(t)))
-        self.__dict__.setdefault("_warped_shapes", {})[t.value] = warp.shape(self.width, self.height)
-        return t.value
+        return self._present_ticket(_lib.fr_present_enqueue_warped, int(buffer), C.byref(warp.c_struct()),
+                                    shape=warp.shape(self.width, self.height))
 
     def present_warped_to(self, buffer, warp, tensor):
         """fr_present_enqueue_warped_device: as present_to(), through `warp`; the tensor holds the output's
@@ -1147,12 +1153,9 @@ class PathTracer:
         """fr_present_enqueue_blended: as present(), of the virtual image that is blend.inner_buffer around the gaze,
         blend.outer_buffer in the periphery and their smoothstep mix between the radii (a PresentBlend); through
         `warp` (a PresentWarp) when one is given. Returns the ticket."""
-        t = C.c_uint64()
-        self._check(_lib.fr_present_enqueue_blended(self._ctx, C.byref(blend.c_struct()),
-                                                    None if warp is None else C.byref(warp.c_struct()), C.byref(t)))
-        if warp is not None:
-            self.__dict__.setdefault("_warped_shapes", {})[t.value] = warp.shape(self.width, self.height)
-        return t.value
+        return self._present_ticket(_lib.fr_present_enqueue_blended, C.byref(blend.c_struct()),
+                                    None if warp is None else C.byref(warp.c_struct()),
+                                    shape=None if warp is None else warp.shape(self.width, self.height))
 
     def present_blended_to(self, blend, tensor, warp=None):
         """fr_present_enqueue_blended_device: as present_to() / present_warped_to(), of the blended image."""
@@ -1169,10 +1172,8 @@ class PathTracer:
     def present_reprojected(self, buffer, rp) -> int:
         """fr_present_enqueue_reprojected: as present_warped(), with every texel moved to where the display camera of
         `rp` (a PresentReproject) sees its POSITION; rp.fallback fills where nothing lands. Returns the ticket."""
-        t = C.c_uint64()
-        self._check(_lib.fr_present_enqueue_reprojected(self._ctx, int(buffer), C.byref(rp.c_struct()), C.byref(t)))
-        self.__dict__.setdefault("_warped_shapes", {})[t.value] = rp.fallback.shape(self.width, self.height)
-        return t.value
+        return self._present_ticket(_lib.fr_present_enqueue_reprojected, int(buffer), C.byref(rp.c_struct()),
+                                    shape=rp.fallback.shape(self.width, self.height))
 
     def present_reprojected_to(self, buffer, rp, tensor):
         """fr_present_enqueue_reprojected_device: as present_warped_to(), reprojected by `rp`."""

@@ -1,6 +1,6 @@
 """GPU suite for present (8-bit frames delivered in stream order): the pack kernel (k_present_pack) in bytes against the
 numpy restatement, presents between pipelined frames against a twin context that reads the float image after the same
-frame, the ring's semantics, presents around other calls, and the refusals.
+frame, the ring's semantics, presents around other calls, the refusals, and the order in which every enqueue refuses.
 
 Scene 1 (the bunny preset), procedural detail 1, 100 x 70 unless a size is given, 2 spp. No test here synchronises a
 presenting context between an enqueue and its acquire: the acquire is the only wait."""
@@ -369,3 +369,127 @@ def test_refusals_enqueue_nothing(fovrt_mod):
     assert (dst.cpu().numpy() == 7).all()
     g.destroy()
     t.destroy(); twin.destroy(); other.destroy()
+
+
+# ---------------------------------------------------------------------------------------------
+# 9. The order of the refusals
+# ---------------------------------------------------------------------------------------------
+def test_refusal_order(fovrt_mod):
+    """Two faults at once through each of the eight enqueue entry points, on a 16 x 12 screen: the call answers with
+    the code and the text of the fault that comes first in the order NULL context or ticket; reprojection or warp;
+    (device forms) device_dst, then bytes; blend; buffer ids; group or sharded; ring off; reprojection not enabled;
+    ring full. The ticket word stays untouched, nothing is written to the destination, and a plain present afterwards
+    gives the right bytes with the next ticket."""
+    import torch
+    TN = fovrt_mod.TextureName
+    lib = fovrt_mod.load_library()
+    INV, STATE, UNS = fovrt_mod.FR_E_INVALID, fovrt_mod.FR_E_STATE, fovrt_mod.FR_E_UNSUPPORTED
+    w, h = 16, 12
+    t = mk(fovrt_mod, w, h)
+    full = w * h * 4
+    dst = torch.full((full + 64,), 7, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    dp = dst.data_ptr()
+    SIB, POS = int(TN.SIBSON), int(TN.POSITION)
+    tk = C.c_uint64(99)
+    keep = []
+    FORMS = {"plain": "", "warped": "_warped", "blended": "_blended", "reprojected": "_reprojected"}
+    BAD_WARP = {"plain": None, "warped": "the warp is NULL", "blended": "the warp is NULL",
+                "reprojected": "the reprojection is NULL"}
+    BAD_DST, BAD_BYTES, BAD_BLEND = "device_dst is NULL or not", "bytes != the output's", "the blend is NULL"
+    BAD_BUFFER, GROUP, RING_OFF = "the buffer is not", "a rank of a group or sharded", "presenting is not enabled"
+    REPROJECT_OFF, RING_FULL = "reprojected presents are not enabled", "every slot of the ring is held"
+
+    def ref_to(x):
+        keep.append(x.c_struct())
+        return C.byref(keep[-1])
+
+    def warp(bad):
+        hm = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
+        if bad:
+            hm[4] = np.nan
+        return fovrt_mod.PresentWarp(hm)
+
+    def args(form, device, faults):
+        buf = POS if "buffer" in faults else SIB
+        if form == "plain":
+            a = [buf]
+        elif form == "warped":
+            a = [buf, ref_to(warp("warp" in faults))]
+        elif form == "blended":
+            a = [ref_to(fovrt_mod.PresentBlend((8.0, 6.0), 9.0 if "blend" in faults else 3.0, 6.0, buf, TN.ATROUS)),
+                 ref_to(warp("warp" in faults))]
+        else:
+            vp = np.eye(4, dtype=np.float32).reshape(16)
+            if "warp" in faults:
+                vp[5] = np.inf
+            a = [buf, ref_to(fovrt_mod.PresentReproject(vp, warp(False)))]
+        if device:
+            return a + [C.c_void_p(dp + (4 if "dst" in faults else 0)), full + (4 if "bytes" in faults else 0)]
+        return a + [None if "ticket" in faults else C.byref(tk)]
+
+    def refused(form, device, faults, code, text):
+        """text: what the message holds behind the entry point's name; None: no message is left (NULL ticket)."""
+        name = "fr_present_enqueue" + FORMS[form] + ("_device" if device else "")
+        what = (name, faults)
+        before = t.last_error()
+        assert getattr(lib, name)(t._ctx, *args(form, device, faults.split())) == code, what
+        assert tk.value == 99, what
+        msg = t.last_error()
+        if text is None:
+            assert msg == before, (what, msg)
+        else:
+            assert msg.startswith(name + ":") and text in msg, (what, msg)
+        if device:
+            assert (dst.cpu().numpy() == 7).all(), what
+
+    # the ring off, reprojected presents never enabled, no group
+    for form in FORMS:  # (first: the context's message is none of the ones that a wrong order would leave here)
+        refused(form, False, "ticket buffer" if form == "plain" else "ticket warp", INV, None)
+    for form in FORMS:
+        for device in (False, True):
+            if BAD_WARP[form]:
+                refused(form, device, "warp", INV, BAD_WARP[form])  # ... and the ring is off
+                refused(form, device, "warp buffer", INV, BAD_WARP[form])
+            refused(form, device, "buffer", INV, BAD_BUFFER)  # ... and the ring is off
+            refused(form, device, "", STATE, RING_OFF)  # ... and (reprojected) the reprojection was never enabled
+        if BAD_WARP[form]:
+            refused(form, True, "warp dst", INV, BAD_WARP[form])
+            refused(form, True, "warp bytes", INV, BAD_WARP[form])
+        refused(form, True, "dst bytes", INV, BAD_DST)
+        refused(form, True, "dst", INV, BAD_DST)  # ... and the ring is off
+        refused(form, True, "bytes buffer", INV, BAD_BYTES)
+    for device in (False, True):
+        refused("blended", device, "warp blend", INV, BAD_WARP["blended"])
+        refused("blended", device, "blend buffer", INV, BAD_BLEND)
+        refused("blended", device, "blend", INV, BAD_BLEND)  # ... and the ring is off
+    refused("blended", True, "dst blend", INV, BAD_DST)
+    refused("blended", True, "bytes blend", INV, BAD_BYTES)
+    # a rank of a group, the ring still off
+    g = fovrt_mod.Group([t], views=1, tile=16)
+    for form in FORMS:
+        for device in (False, True):
+            refused(form, device, "buffer", INV, BAD_BUFFER)
+            refused(form, device, "", UNS, GROUP)
+    g.destroy()
+    # one slot, held: the ring is full; reprojected presents still not enabled
+    img = pnp.image(pnp.values(), w, h)
+    want = pnp.pack(img, pnp.BGRA8 | pnp.TOP_DOWN)
+    t.write(TN.SIBSON, img)
+    t.present_enable(1, pnp.BGRA8 | pnp.TOP_DOWN)
+    held = t.present(TN.SIBSON)
+    for form in FORMS:
+        if BAD_WARP[form]:
+            refused(form, False, "warp", INV, BAD_WARP[form])
+        refused(form, False, "buffer", INV, BAD_BUFFER)
+        refused(form, False, "", STATE, REPROJECT_OFF if form == "reprojected" else RING_FULL)
+    refused("blended", False, "blend", INV, BAD_BLEND)
+    refused("reprojected", True, "", STATE, REPROJECT_OFF)
+    t.present_reproject_enable()
+    refused("reprojected", False, "", STATE, RING_FULL)
+    assert held == 1
+    take(t, held, want, "the held ticket")
+    ticket = t.present(TN.SIBSON)  # no refusal took a ticket
+    assert ticket == 2
+    take(t, ticket, want, "after the refusals")
+    t.destroy()
